@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- benchmarks of the MI355X SZ 2.1 hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|c4]
+    python bench.py --gpus N --steps K --warmup W [--config headline|c4] [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line; every other measurement and check of the headline config (the
+decompression and its error, `concurrent`, `m_field`, `other_paths`, `omp_container`, `e2e`, `e2e_default`, `cpu_baseline`) runs only with
+--full, and its keys are null without it (--timed-only still runs its decompression and the `omp_container` object).
+--dump-outputs DIR writes what the last timed step returned to its caller (the stream rank 0 wrote) as DIR/<name>.npy: `stream_length`
+(float64, one value) and `stream_bytes` (the stream's bytes as float32, exact; a stream longer than 8 Mi bytes is sampled: its first
+MiB, then 7 Mi bytes at positions drawn with a fixed seed from the rest, in stream order).  The inputs are the same from run to run.
 
 --config headline (default; BASELINE.json configs[1]/[2], the configuration the metric is quoted on).  A "step" is one pass of
 the hot path as SZ_compress_args runs it -- value-range scan, regression fit + predictor selection, interval optimiser,
@@ -11,7 +18,7 @@ predict/quantise, Huffman encode into the reference's SZ 2.1 stream -- over one 
 an (N*512)x512x512 array (weak scaling, no data-path collective) and the step ends with one all-gather of the variable-length
 sub-streams (RCCL), launched asynchronously so that it overlaps the next step's compression; every gather is completed inside
 the timed region.  Since round 5 the timed region is ONE BLOCKING CALL AFTER THE OTHER (`--inflight 1`: what a caller of SZ_compress_args sees;
-`value` = `value_single_call`; `step_ms` lists every step); `concurrent` gives 1 / 2 / 4 arrays in flight.  Rank 0 prints ONE JSON line.  Extra objects on that line:
+`value` = `value_single_call`; `step_ms` lists every step); `concurrent` gives 1 / 2 / 4 arrays in flight.  Rank 0 prints ONE JSON line.  Extra objects on that line (all but `roofline` with --full only):
   roofline     -- the predict+quantise wavefront kernel: algorithmic bytes (N*4, the array read once) / its average duration
                   measured with HIP events on the library's stream, against the 8 TB/s HBM3E peak.
   m_field      -- BASELINE configs[2]: the same step on the 512^3 "M-field" (half of the blocks choose the regression predictor: k_reg_points, the
@@ -219,6 +226,21 @@ def _sync(torch):
         torch.cuda.synchronize()
 
 
+DUMP_HEAD = 1 << 20          # stream bytes dumped verbatim from the start
+DUMP_BYTES = 8 << 20         # stream bytes dumped at most (as float32: 32 MB)
+
+
+def dump_outputs(out_dir, stream):
+    """--dump-outputs: the stream (uint8 tensor of its exact length) as DIR/stream_bytes.npy + DIR/stream_length.npy"""
+    b = stream.cpu().numpy()
+    if b.size > DUMP_BYTES:
+        rest = np.random.default_rng(0).integers(DUMP_HEAD, b.size, DUMP_BYTES - DUMP_HEAD)
+        b = np.concatenate([b[:DUMP_HEAD], b[np.sort(rest)]])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stream_bytes.npy"), b.astype(np.float32))
+    np.save(os.path.join(out_dir, "stream_length.npy"), np.array([stream.numel()], dtype=np.float64))
+
+
 def run_headline(args, torch, dist, world, rank, local_rank, dev):
     import ctypes
     import sz_amd
@@ -341,6 +363,8 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     run_steps(inflight, max(args.warmup, inflight), True)
     gather_host_s[0] = 0.0
     elapsed, stats_all, (size, ob) = run_steps(inflight, args.steps, True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ob[:size])
     step_ms = [round((b - a) * 1e3, 3) for a, b in zip([0.0] + step_done_s[:-1], step_done_s)]
     gather_ms_per_step = gather_host_s[0] / args.steps * 1e3
     quant_ms = [st.ms_quant for st in stats_all]
@@ -371,18 +395,20 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     single_call = {"GB/s": round(world * nbytes_in / (single_el / args.steps) / 1e9, 3), "ms": round(single_el / args.steps * 1e3, 4),
                    "quant_ms": round(float(np.mean([t.ms_quant for t in single_stats])), 4)}
 
-    # ---- quality of the result (outside the timed region): decompress on the GPU, compare with the input
-    dec = torch.empty_like(x)
-    dst = ctx.decompress(ob.data_ptr(), True, size, 4 + 28 + 8, (n, n, n), np.float32, dec.data_ptr(), True)
-    err = (dec - x).abs()
-    max_abs_err = float(err.max().item())
-    mse = float((err * err).double().sum().item()) / x.numel()
-    psnr = 20 * np.log10(float((x.max() - x.min()).item())) - 10 * np.log10(mse)
-    del err
-    _sync(torch); td = time.perf_counter()
-    for _ in range(3):
-        ctx.decompress(ob.data_ptr(), True, size, 4 + 28 + 8, (n, n, n), np.float32, dec.data_ptr(), True)
-    _sync(torch); td = (time.perf_counter() - td) / 3
+    # ---- quality of the result (outside the timed region; --full, or --timed-only's one decompression): decompress on the GPU, compare with the input
+    max_abs_err = psnr = td = dst = None
+    if args.full or args.timed_only:
+        dec = torch.empty_like(x)
+        dst = ctx.decompress(ob.data_ptr(), True, size, 4 + 28 + 8, (n, n, n), np.float32, dec.data_ptr(), True)
+        err = (dec - x).abs()
+        max_abs_err = float(err.max().item())
+        mse = float((err * err).double().sum().item()) / x.numel()
+        psnr = 20 * np.log10(float((x.max() - x.min()).item())) - 10 * np.log10(mse)
+        del err
+        _sync(torch); td = time.perf_counter()
+        for _ in range(3):
+            ctx.decompress(ob.data_ptr(), True, size, 4 + 28 + 8, (n, n, n), np.float32, dec.data_ptr(), True)
+        _sync(torch); td = (time.perf_counter() - td) / 3
 
     if rank != 0:
         if world > 1:
@@ -416,7 +442,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     # ---- arrays in flight: the same args.steps compressions with 1 / 2 / 4 lanes (outside the timed region), with the sweep kernel's own
     # time per K so that interference is visible; and every stream of the last run against the one a single blocking call gives
     concurrent = None
-    if world == 1 and not getattr(args, "dry_run", False) and not args.timed_only:
+    if world == 1 and args.full and not getattr(args, "dry_run", False) and not args.timed_only:
         ref_size, _, ref_ob = one_step()
         _sync(torch)
         ref_bytes = ref_ob[:ref_size].clone()
@@ -440,7 +466,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
 
     # ---- BASELINE configs[2]: the adaptive case proper -- 512^3 M-field, half of the blocks regression (single GPU, outside the timed region)
     mfield = None
-    if world == 1 and n == EDGE and not args.no_m_field:
+    if world == 1 and n == EDGE and args.full and not args.no_m_field:
         xm = torch.from_numpy(m_field(n)).to(dev)
         for _ in range(5):                                        # (the first calls create the chain threads and size the workspaces of the regression path)
             one_step(xm)
@@ -497,7 +523,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     # ---- the other paths of the same library, one line each (optional; outside the timed region; single GPU only): the SZ 1.4 container
     #      (withLinearRegression = NO) on the same array, a 2-D array through the SZ 2.1 path, a 1-D series
     other = None
-    if not args.no_other_paths and not args.timed_only and world == 1 and n == EDGE:
+    if args.full and not args.no_other_paths and not args.timed_only and world == 1 and n == EDGE:
         def timed(fn, reps=3):
             fn(); _sync(torch); t = time.perf_counter()
             for _ in range(reps):
@@ -544,7 +570,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     if omp_boxes < 0:                                              # default: boxes of 32^3 (4096 at 512^3) when the edge allows
         nb1 = n // 32
         omp_boxes = nb1 ** 3 if (n % 32 == 0 and nb1 >= 2 and nb1 & (nb1 - 1) == 0 and not args.no_omp and not getattr(args, "dry_run", False)) else 0
-    if omp_boxes and world == 1:
+    if omp_boxes and world == 1 and (args.full or args.timed_only):
         meta_o = sz_amd.make_meta(np.float32, err_mode=sz_amd.ABS, abs_bound=EB, vmin=0.0, vmax=0.0)
         meta_o = bytes([meta_o[0], meta_o[1], meta_o[2], 0xC0]) + bytes(meta_o[4:])
         y_o = torch.empty_like(x)
@@ -580,7 +606,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
 
     # ---- host-pointer API, PCIe included (never the headline value)
     e2e = None
-    if world == 1 and n == EDGE and not args.timed_only:
+    if world == 1 and n == EDGE and args.full and not args.timed_only:
         assert sz_amd.SZ_Init(os.path.join(ROOT, "tests", "golden", "sz_speed.config")) == 0
         L = sz_amd.lib()
         dims = (0, 0, n, n, n)
@@ -613,7 +639,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
     # ---- the same two calls under the mode the reference SHIPS (example/sz.config: szMode = SZ_BEST_COMPRESSION, the zstd stage behind the SZ stream, conf.c:114,
     #      utility.c:174-214), and the unmodified reference doing the same on one core: what a caller who changes nothing gets
     e2e_default = None
-    if world == 1 and n == EDGE and not args.timed_only:
+    if world == 1 and n == EDGE and args.full and not args.timed_only:
         import hashlib
         cfg_def = os.path.join(ROOT, "tests", "golden", "sz_default.config")
         assert sz_amd.SZ_Init(cfg_def) == 0
@@ -683,7 +709,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
                 e2e_default["decoded_md5_equal"] = bool(dec_md5 is not None and dec_md5 == ref_dec_md5 == back_md5)
 
     cpu, cpu_mt = (None, None)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu, cpu_mt = cpu_baselines(host, n, size)
 
     line = {"metric": f"compression GB/s (input), {n}^3 float32 ABS 1e-4", "value": round(value, 3), "unit": "GB/s",
@@ -696,9 +722,9 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
                                       f"{inflight} compressions in flight per GPU, every lane on its own copy of the field (szhip_pool, one context per lane; "
                                       "`single_call_GBps` = one blocking call after the other, `concurrent` gives 1 / 2 / 4)"),
                        "error_bound_mode": "ABS", "abs_err_bound": EB, "slabs": world, "arrays_in_flight": inflight},
-            "ratio": round(nbytes_in / size, 6), "out_bytes": size, "max_abs_err": max_abs_err, "psnr": round(psnr, 6),
+            "ratio": round(nbytes_in / size, 6), "out_bytes": size, "max_abs_err": max_abs_err, "psnr": None if psnr is None else round(psnr, 6),
             "intervals": stats.intervals, "reg_blocks": stats.n_reg_blocks, "unpredictable": stats.n_unpred,
-            "decompress_GBps": round(nbytes_in / td / 1e9, 3),
+            "decompress_GBps": None if td is None else round(nbytes_in / td / 1e9, 3),
             "value_single_call": single_call["GB/s"], "single_call_GBps": single_call["GB/s"], "single_call": single_call, "step_ms": step_ms,
             # (the HIP runtime stalls a call for 3 - 5 ms now and then -- one step in about a hundred, profiles/r05_timed_region_five_runs.txt and the step lists of
             #  the round's lines --; `value` is the contract's K steps over their total time and carries such a step when it meets one; the median step is beside it)
@@ -706,7 +732,7 @@ def run_headline(args, torch, dist, world, rank, local_rank, dev):
             "value_from_median_step": round(world * nbytes_in / (float(np.median(step_ms)) * 1e-3) / 1e9, 3) if step_ms else None,
             "phase_ms": {"prequant": round(stats.ms_prequant, 3), "quant": round(stats.ms_quant, 3),
                          "entropy": round(stats.ms_entropy, 3), "host_glue": round(stats.ms_host, 3), "compress_call_total": round(stats.ms_total, 3),
-                         "decompress_quant": round(dst.ms_quant, 3), "decompress_total": round(dst.ms_total, 3)},
+                         "decompress_quant": None if dst is None else round(dst.ms_quant, 3), "decompress_total": None if dst is None else round(dst.ms_total, 3)},
             "per_rank": per_rank,
             "roofline": roofline, "concurrent": concurrent, "m_field": mfield, "other_paths": other, "omp_container": omp, "e2e": e2e, "e2e_default": e2e_default, "cpu_baseline": cpu, "cpu_baseline_mt": cpu_mt}
     print(json.dumps(line))
@@ -773,6 +799,8 @@ def run_c4(args, torch, dist, world, rank, local_rank, dev):
         parts = gather.end(pending.pop(0))
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ob[:size])
     # every rank decompresses its OWN sub-stream (from the gathered set when there is one) and checks the bound
     eb = eb_box[0]
     dec = torch.empty_like(x)
@@ -849,6 +877,9 @@ def main():
     ap.add_argument("--config", default="headline", choices=["headline", "c4"])
     ap.add_argument("--edge", type=int, default=EDGE, help="cube edge of the headline config (512 = the BASELINE config)")
     ap.add_argument("--c4-edge", type=int, default=1024)
+    ap.add_argument("--full", action="store_true", help="also every other measurement and check of the headline config: the decompression and its error, "
+                    "arrays in flight, M-field, other paths, OpenMP container, host-memory calls, CPU baselines (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the stream of the last timed step (rank 0) to DIR as .npy files")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--other-paths", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--no-other-paths", action="store_true", help="skip the SZ 1.4 container, the 2-D array and the 1-D series (one line each)")

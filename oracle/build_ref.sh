@@ -7,6 +7,7 @@
 #   libSZ_omp_O1.so  the same at -O1: the reference's DOUBLE OpenMP entry point runs off the end of a non-void function, which gcc -O3 turns
 #                 into a trap; at -O1 it returns (round 4: what the float64 pin of the OpenMP container is recorded from; -O1 does not
 #                 contract or reassociate either, the arithmetic is the same)
+#   sz_cli.o, sz_openmp_cli.o  the reference's two command-line tools, compiled against include/ (the tests link them)
 # One plain compiler line per library: gcc -O3 for baseline x86-64 (no FMA contraction: what the reference's own CMake Release
 # build gives), the vendored zstd 1.3.5 and zlib 1.2.11 compiled in.  config.h is the reference's own template
 # config.h.cmake with its four HAVE_* switches set (sys/time.h, unistd.h, clock_gettime, gettimeofday: all present on Linux) --
@@ -23,6 +24,16 @@ ZSTD=$(ls "$REF"/zstd/common/*.c "$REF"/zstd/compress/*.c "$REF"/zstd/decompress
 ZLIB=$(ls "$REF"/zlib/*.c)
 INC="-I$OUT -I$REF/sz/include -I$REF/zstd -I$REF/zstd/common -I$REF/zlib"
 CC=${CC:-gcc}
+# the reference's command-line tools (example/sz.c, example/sz_openmp.c) compiled UNCHANGED against this repository's include/ into
+# objects: tests/test_reference_cli.py and tests/test_reference_omp_cli.py link them against the product library and its CPU shim
+INCDIR="$(cd "$HERE/.." && pwd)/include"
+cli() {  # <source under example/> <object> [flags]
+  local src="$REF/example/$1" obj="$OUT/$2"; shift 2
+  if [ -f "$obj" ] && [ -z "$(find "$src" "$INCDIR" -newer "$obj" | head -1)" ]; then return 0; fi
+  $CC -O1 -w "$@" -I"$INCDIR" -c "$src" -o "$obj"
+}
+cli sz.c sz_cli.o
+cli sz_openmp.c sz_openmp_cli.o -fopenmp
 FLAGS="-O3 -fPIC -shared -w -std=gnu99 -DNDEBUG"
 stamp="$OUT/.built_from"
 sig="$(cd "$REF" && (git rev-parse HEAD 2>/dev/null || find sz/src zstd zlib -name '*.[ch]' | sort | xargs cat | md5sum | cut -d' ' -f1))"

@@ -291,3 +291,43 @@ def test_bench_entry_starts_its_own_ranks_for_gpus_gt_1():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["out_bytes"] > 0
+
+
+def test_bench_dump_outputs_are_the_last_steps_stream_and_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR` (rehearsed on the shim, --dry-run): the stream of the last timed step as float32 bytes plus its
+    length, within 64 MB, the same in two runs; a plain run leaves the decompression and the other objects out of the line."""
+    import json
+    import subprocess
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sim_lib
+    env = dict(os.environ, SZ_AMD_LIB=sim_lib.shim_path())
+    env.pop("WORLD_SIZE", None); env.pop("RANK", None)
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run", "--edge", "24",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and len(d["step_ms"]) == 3 and d["ms_per_step"] > 0
+        assert d["max_abs_err"] is None and d["omp_container"] is None and d["cpu_baseline"] is None
+        files = sorted(os.listdir(out))
+        assert files == ["stream_bytes.npy", "stream_length.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        b, n = np.load(out / "stream_bytes.npy"), np.load(out / "stream_length.npy")
+        assert b.dtype == np.float32 and n.dtype == np.float64 and n.tolist() == [d["out_bytes"]] and b.size == d["out_bytes"]
+        assert np.array_equal(b, np.round(b)) and b.min() >= 0 and b.max() <= 255
+        dumps.append((b, n))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_bench_dump_of_a_long_stream_is_a_fixed_sample(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    s = torch.from_numpy(np.random.default_rng(5).integers(0, 256, 20 << 20, dtype=np.uint8))
+    bench.dump_outputs(str(tmp_path / "a"), s)
+    bench.dump_outputs(str(tmp_path / "b"), s)
+    a, b = np.load(tmp_path / "a" / "stream_bytes.npy"), np.load(tmp_path / "b" / "stream_bytes.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_BYTES and np.array_equal(a, b)
+    assert np.array_equal(a[:bench.DUMP_HEAD], s[:bench.DUMP_HEAD].numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "stream_length.npy").tolist() == [20 << 20]

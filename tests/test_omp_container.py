@@ -57,7 +57,8 @@ def test_box_grid_and_uneven_shapes_round_trip(oracle):
         assert float(np.abs(dec.astype(np.float64) - d.astype(np.float64)).max()) <= eb, (shape, threads)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libSZ_omp.so")), reason="the reference build lives in the build container only")
-def test_recorded_outputs_are_what_the_reference_library_gives_today():
+def test_recorded_outputs_are_what_the_reference_library_gives_today(built):
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libSZ_omp.so")):
+        pytest.skip("oracle/_ref was not built: the reference sources were not there when build() ran")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "record_reference_omp.py"), "--check"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-600:] + r.stderr[-600:]

@@ -1,6 +1,6 @@
 """the reference's only caller of its OpenMP container, example/sz_openmp.c, built UNCHANGED against include/ (it includes
-"sz_omp.h", round 5) and this library.  The source is read where it lies under /root/reference (this container only: the test skips elsewhere);
-nothing of it is copied.  Linked against the CPU shim of the product code it compresses a 3-D array with `-k` (the OpenMP container), and the
+"sz_omp.h", round 5) and this library.  build() compiles the source where it lies into oracle/_ref/sz_openmp_cli.o (oracle/build_ref.sh; only
+where the reference sources are, the test skips where that object is missing); nothing of it is copied.  Linked against the CPU shim of the product code it compresses a 3-D array with `-k` (the OpenMP container), and the
 stream is the oracle's restatement of sz_omp.c for the same box count, byte for byte, and decompresses within the bound."""
 import os
 import subprocess
@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CLI = "/root/reference/example/sz_openmp.c"
+REF_CLI = os.path.join(ROOT, "oracle", "_ref", "sz_openmp_cli.o")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CLI), reason="the reference tree is only in the build container")
 def test_reference_openmp_cli_links_unchanged_and_round_trips_on_the_shim(built, tmp_path):
+    if not os.path.exists(REF_CLI):
+        pytest.skip("oracle/_ref/sz_openmp_cli.o was not built: the reference sources were not there when build() ran")
     import sim_lib
     from sz_amd.fields import s_field
     simdir = os.path.dirname(sim_lib.shim_path())

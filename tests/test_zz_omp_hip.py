@@ -337,7 +337,7 @@ def test_bench_omp_object_rehearsal_on_cpu_shim(built):
     import sim_lib
     env = dict(os.environ, SZ_AMD_LIB=sim_lib.shim_path())
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dry-run", "--edge", "32",
-                        "--omp-boxes", "8"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--omp-boxes", "8"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-800:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
     o = line["omp_container"]
