@@ -163,8 +163,7 @@ int szhip_decompress_sz14(szhip_ctx *ctx, int dtype, const unsigned char *stream
  * `body_off` of the inverse: offset of the thread_num field (4 + MetaDataByteLength).
  * Status (round 4): on MI355X byte-identical to the oracle (oracle/szo_omp_impl.h) and md5-identical to 12 recorded outputs of the reference built
  * with -fopenmp (8 float32; 4 float64 from the same sources at -O1).  Boxes with 32 x 32 faces run the column-per-lane sweep of szh_ompcol.h
- * (k_omp_col: 0.16 ms at 512^3 f32, the whole call 0.69 ms = 777 GB/s); other shapes the first form (k_omp_box).  SZ_HIP_OMP_COL=0 /
- * SZ_HIP_OMP_LEAN=0 select the round-3 kernels for comparison.
+ * (k_omp_col: 0.16 ms at 512^3 f32, the whole call 0.69 ms = 777 GB/s); other shapes the first form (k_omp_box).
  */
 int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
                        int thread_num, const szhip_params *params, const unsigned char *meta, size_t meta_len,

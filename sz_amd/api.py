@@ -15,7 +15,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 
 
 def lib_path():
-    """The product library; SZ_AMD_LIB names another build of it (development: libszhip_dev.so, variants)."""
+    """The product library; SZ_AMD_LIB names another build of it (variants)."""
     return os.environ.get("SZ_AMD_LIB") or os.path.join(_CSRC, "libszhip.so")
 
 

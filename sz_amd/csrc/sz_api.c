@@ -415,7 +415,7 @@ static int finish_lossless(unsigned char *tmp, size_t tmpSize, unsigned char **n
 /* ---- compression ---- */
 static unsigned char *omp_compress_at(int dataType, const void *data, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size);
 static int omp_pick_threads(size_t r1, size_t r2, size_t r3);
-#define SZ_HIP_OMP_MARK 0x4f      /* stream byte 19 (parameter byte 15, which convertSZParamsToBytes never writes: ByteToolkit.c:874-972) of an OpenMP container that
+#define SZH_OMP_MARK 0x4f         /* stream byte 19 (parameter byte 15, which convertSZParamsToBytes never writes: ByteToolkit.c:874-972) of an OpenMP container that
                                    * SZ_compress_args wrote under SZ_HIP_MODE=omp: how SZ_decompress of THIS library tells it from an SZ 2.1 stream (same flag byte) */
 static int compress_fp(int dataType, int withRegression, unsigned char **newByteData, void *oriData,
                        size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, size_t *outSize,
@@ -588,7 +588,7 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
             size_t osz = 0;
             unsigned char *o = omp_compress_at(dataType, d_in, 1, r3, r2, r1, realPrecision, &osz);
             if (!o) return SZ_NSCS;
-            o[19] = SZ_HIP_OMP_MARK;
+            o[19] = SZH_OMP_MARK;
             return finish_lossless(o, osz, newByteData, outSize, status);
         }
     }
@@ -870,7 +870,7 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
     hint_huge_pages(out, dataLength * esz);
     if (!out) { printf("Error: out of memory.\n"); if (owned) free(sz); return NULL; }
     int ok = 1;
-    if ((same & 0x80) && !(same & 0x31) && sz[19] == SZ_HIP_OMP_MARK && computeDimension(r5, r4, r3, r2, r1) == 3) {
+    if ((same & 0x80) && !(same & 0x31) && sz[19] == SZH_OMP_MARK && computeDimension(r5, r4, r3, r2, r1) == 3) {
         /* an OpenMP container written by SZ_compress_args of this library under SZ_HIP_MODE=omp (see compress_fp); its body starts behind
          * 4 + MetaDataByteLength bytes for both types (sz_omp.c:221, :733) */
         void *o2 = NULL;

@@ -38,9 +38,6 @@
 #pragma once
 // (included by szhip_kernels.h after szh_ribbon.h and szh_ompcol.h, whose helpers it uses)
 
-#ifndef SZH_DEV
-#define SZH_DEV 0
-#endif
 namespace szh_bm {
 using szh_oc::mask_t;
 using szh_oc::lane_mask;

@@ -226,100 +226,11 @@ __global__ __launch_bounds__(1024) void k_omp_box(szh_omp_geom g, const T *__res
     }
 }
 
-// the values the quantiser kept verbatim, in the box's row-major order, behind those of the boxes before it (sz_omp.c:246-262)
-template <class T>
-__global__ __launch_bounds__(256) void k_omp_gather(szh_omp_geom g, const T *__restrict__ data, const uint16_t *__restrict__ codes,
-                                                    const unsigned *__restrict__ ucount, const u64 *__restrict__ uoff, T *__restrict__ unpred)
-{
-    __shared__ u64 sh[8];
-    const int b = blockIdx.x;
-    if (ucount[b] == 0) return;                               // uniform
-    const T *box = reinterpret_cast<const T *>(szh_omp_box_origin_bytes(g, b, sizeof(T), data));
-    const uint16_t *cb = codes + (int64_t)b * g.bel;
-    T *dst = unpred + uoff[b];
-    u64 done = 0;
-    for (int base = 0; base < g.bel; base += 256 * 8) {
-        const int p0 = base + (int)threadIdx.x * 8;
-        unsigned mask = 0;
-        for (int e = 0; e < 8; ++e) if (p0 + e < g.bel && cb[p0 + e] == 0) mask |= 1u << e;
-        u64 tot;
-        u64 rank = done + block_excl_scan_256((u64)__builtin_popcount(mask), sh, &tot);
-        for (int e = 0; e < 8; ++e) if (mask >> e & 1u) {
-            const int p = p0 + e, k = p / (g.c1 * g.c2), r = p - k * (g.c1 * g.c2), i = r / g.c2, j = r - i * g.c2;
-            dst[rank++] = box[(int64_t)k * g.d0 + (int64_t)i * g.d1 + j];
-        }
-        done += tot;
-    }
-}
-
 // ---- Huffman packing with one byte-aligned payload per box (sz_omp.c:300-330: `encode` per box into its own buffer, then memcpy)
 __device__ __forceinline__ void omp_load8(const uint16_t *__restrict__ cb, int p0, int bel, bool aligned, uint16_t (&c)[8])
 {
     if (aligned && p0 + 8 <= bel) { const uint4 w = *reinterpret_cast<const uint4 *>(cb + p0); __builtin_memcpy(c, &w, 16); }
     else { for (int q = 0; q < 8; ++q) c[q] = p0 + q < bel ? cb[p0 + q] : (uint16_t)0; }
-}
-// bits of chunk q of box b -> chunk_bits[b * cpb + q]
-__global__ __launch_bounds__(256) void k_omp_chunk_bits(szh_omp_geom g, const uint16_t *__restrict__ codes, const uint8_t *__restrict__ len, u64 *chunk_bits)
-{
-    __shared__ u64 sh[4];
-    const int c = blockIdx.x, b = c / g.cpb, q = c - b * g.cpb;
-    const uint16_t *cb = codes + (int64_t)b * g.bel;
-    const int p0 = q * SZH_ENC_CHUNK + (int)threadIdx.x * 8;
-    uint16_t cc[8];
-    omp_load8(cb, p0, g.bel, (g.bel & 7) == 0, cc);
-    unsigned s = 0;
-    for (int e = 0; e < 8; ++e) if (p0 + e < g.bel) s += len[cc[e]];
-    const u64 ws = wave_sum_u64((u64)s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_bits[c] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-// bytes of box b = its bits rounded up (Huffman.c encode: the last byte is padded with zero bits)
-__global__ __launch_bounds__(256) void k_omp_box_bytes(int nb, int cpb, const u64 *__restrict__ chunk_off, const u64 *__restrict__ total_bits, u64 *box_bytes)
-{
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= nb) return;
-    const u64 lo = chunk_off[(int64_t)b * cpb], hi = b + 1 < nb ? chunk_off[(int64_t)(b + 1) * cpb] : *total_bits;
-    box_bytes[b] = (hi - lo + 7) >> 3;
-}
-// out32: 4-byte aligned base of the stream buffer (zeroed); bit0: bit position of the first box's payload in it
-__global__ __launch_bounds__(256) void k_omp_encode(szh_omp_geom g, const uint16_t *__restrict__ codes, const u64 *__restrict__ code,
-                                                    const uint8_t *__restrict__ len, const u64 *__restrict__ chunk_off,
-                                                    const u64 *__restrict__ box_off, u64 bit0, unsigned *out32)
-{
-    __shared__ unsigned buf[SZH_ENC_CHUNK * 2 + 2];
-    __shared__ u64 sh[8];
-    const int c = blockIdx.x, b = c / g.cpb, q = c - b * g.cpb;
-    const uint16_t *cb = codes + (int64_t)b * g.bel;
-    const int p0 = q * SZH_ENC_CHUNK + (int)threadIdx.x * 8;
-    uint16_t cc[8];
-    omp_load8(cb, p0, g.bel, (g.bel & 7) == 0, cc);
-    const u64 gbit = bit0 + box_off[b] * 8 + (chunk_off[c] - chunk_off[(int64_t)b * g.cpb]);
-    const unsigned lead = (unsigned)(gbit & 31);
-    unsigned l[8]; unsigned s = 0;
-    for (int e = 0; e < 8; ++e) { l[e] = p0 + e < g.bel ? (unsigned)len[cc[e]] : 0u; s += l[e]; }
-    u64 tot;
-    const u64 ex = block_excl_scan_256((u64)s, sh, &tot);
-    for (unsigned w = threadIdx.x; w < (unsigned)((lead + tot + 31) >> 5) + 1; w += 256) buf[w] = 0;
-    __syncthreads();
-    unsigned pos = lead + (unsigned)ex;
-    u64 acc = 0; int accn = 0;
-    for (int e = 0; e < 8; ++e) {
-        if (!l[e]) continue;
-        const u64 cw = code[cc[e]];
-        if (accn + (int)l[e] > 64) { lds_put_bits(buf, pos, acc, accn); pos += accn; acc = 0; accn = 0; }
-        acc = l[e] == 64 ? cw : ((acc << l[e]) | (cw & ((1ull << l[e]) - 1)));
-        accn += (int)l[e];
-    }
-    if (accn) lds_put_bits(buf, pos, acc, accn);
-    __syncthreads();
-    const unsigned nwords = (unsigned)((lead + tot + 31) >> 5);
-    const u64 w0 = gbit >> 5;
-    for (unsigned w = threadIdx.x; w < nwords; w += 256) {
-        const unsigned v = __builtin_bswap32(buf[w]);
-        if (w == 0 || w == nwords - 1) { if (v) atomicOr(&out32[w0 + w], v); }
-        else out32[w0 + w] = v;
-    }
 }
 
 // ---- Huffman decoding, a workgroup per box.  A box's payload starts at a byte boundary and holds `bel` symbols, so the boxes are
@@ -401,7 +312,8 @@ __global__ __launch_bounds__(256) void k_omp_hdec(int bel, const unsigned char *
 
 // =====================================================================================================================
 // Round 4: the entropy stage with ONE pass over the codes on either side of the code book (measured before, 512^3 f32, 4096 boxes:
-// k_hist_u16 0.07-0.2 + k_omp_gather 0.22 + k_omp_chunk_bits 0.10 + two scans + k_omp_encode 0.22 ms; k_omp_hdec 1.96 ms).
+// k_hist_u16 0.07-0.2 + a gather of the verbatim values 0.22 + per-chunk bit counts 0.10 + two scans + per-chunk packing 0.22 ms;
+// k_omp_hdec 1.96 ms).
 //   k_omp_hist_box   a workgroup per box: the box's histogram (LDS, lane-private copies) -> hist_box[b][*] and the global histogram
 //   k_omp_box_bits   bytes of a box's payload = sum of hist_box[b][s] * len[s], rounded up      (or, large alphabets: from its codes)
 //   k_omp_encode_box a workgroup per box walks the box's chunks with a running bit position (no chunk table, no chunk scan) and
@@ -622,7 +534,6 @@ struct szh_omp_tables {
     const unsigned char *hdr; unsigned hdr_len;
     u64 off_ucount, off_first, off_unpred, off_sizes;
     const void *first;
-    int dbg;                           // development: 1 = no verbatim values, 2 = no packing, 4 = no read-out, 8 = no counting pass (wrong streams: timing only)
 };
 // the e-th point after one at (row offset off0, column j0) of a box, e < 64: over the row's end into the next rows / the next plane
 __device__ __forceinline__ int64_t omp_point_off(const szh_omp_geom &g, int64_t off0, int j0, int e)
@@ -706,7 +617,7 @@ __global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T
         unsigned zm = 0;
         T vals[4]; int nv = 0;                                      // (a thread with more than four of them fetches the rest at the end)
         int64_t zoff0 = 0; int zj0 = 0;
-        if (z && !(tb.dbg & 1)) {
+        if (z) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned wv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
@@ -726,7 +637,7 @@ __global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T
         }
         __syncthreads();
         // ---- pack: acc holds `nb` pending bits (top-aligned at bit nb - 1); a full word leaves as soon as there are 32
-        if (s && !(tb.dbg & 2)) {
+        if (s) {
             const unsigned bitpos = lead + (unsigned)ex2;
             unsigned wpos = bitpos >> 5, nb = bitpos & 31u;
             u64 acc = 0;
@@ -757,7 +668,7 @@ __global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T
         }
         __syncthreads();
         const u64 w0 = gbit >> 5;
-        if (!(tb.dbg & 4)) for (unsigned w = tid; w < nwords; w += 256) {
+        for (unsigned w = tid; w < nwords; w += 256) {
             const unsigned x = __builtin_bswap32(win[w]);
             if (w == 0 || w == nwords - 1) { if (x) atomicOr(&out32[w0 + w], x); }
             else out32[w0 + w] = x;
@@ -784,13 +695,14 @@ __global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T
 // [the look-up table SZH_LUT_BYTES][the node table when tab_lds].  The box's 256 stretches find their starts as in k_omp_hdec.
 __global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned char *__restrict__ payload, unsigned bytes_before, const u64 *__restrict__ box_off,
                                                       const u64 *__restrict__ box_bytes, const unsigned *__restrict__ table, int n_nodes, int tab_lds,
-                                                      const uint4 *__restrict__ lut, unsigned stage_bytes, uint16_t *__restrict__ codes, unsigned *__restrict__ bad, int nb, int per_wg)
+                                                      const uint4 *__restrict__ lut, unsigned stage_bytes, uint16_t *__restrict__ codes, unsigned *__restrict__ bad)
 {
     SZH_DYN_SMEM(smem);
     __shared__ unsigned s_start[257], s_flag[2];
     __shared__ u64 sh[8];
     const int tid = threadIdx.x;
-    // the tables once per workgroup; then `per_wg` boxes one after the other (small boxes: 20 KB of tables per 1 KB of payload otherwise)
+    // the tables, then the box.  (Several small boxes per workgroup, sharing its copy of the tables, measured slower: 1.59 against
+    // 1.42 ms for 32 768 boxes.)
     const unsigned lds_words = (stage_bytes + 16) / 4;
     char *q = smem + ((SZH_HDEC_SWZ(lds_words) * 4 + 15) / 16 * 16);
     const SZH_LDS void *lutw = (const SZH_LDS void *)(q + SZH_LUT_SIZE * 16);
@@ -799,8 +711,8 @@ __global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned ch
     q += SZH_LUT_BYTES;
     const SZH_LDS unsigned *ltab = nullptr;
     if (tab_lds) { hdec_copy16<false>(reinterpret_cast<uint4 *>(q), reinterpret_cast<const uint4 *>(table), (2 * n_nodes + 3) / 4); ltab = (const SZH_LDS unsigned *)q; }
-    for (int b = (int)blockIdx.x * per_wg; b < nb && b < ((int)blockIdx.x + 1) * per_wg; ++b) {
-    __syncthreads();                                               // (the previous box's payload has been read)
+    const int b = (int)blockIdx.x;
+    __syncthreads();                                               // (the tables are in LDS)
     uint16_t *out = codes + (int64_t)b * bel;
     const unsigned nbytes = (unsigned)box_bytes[b];
     // ---- staging: from a 16-byte aligned address at or below the payload's first byte
@@ -842,5 +754,4 @@ __global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned ch
     int64_t oend = wr ? (int64_t)o + cnt : (int64_t)o;
     if (oend > bel) oend = bel;
     hdec_run_lut<true>(l, total, ltab, table, lut4, wr ? start : 0u, wr ? limit : 0u, &e, out, (int64_t)o, oend, wr);
-    }
 }

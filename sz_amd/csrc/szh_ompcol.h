@@ -146,7 +146,6 @@ template <class T> struct sweep_args {
     uint16_t *codes;
     unsigned *ucount; szh_u64 *ucount64; T *first;        // M_CMP: written; inverse: `first` read, `ucount` = ONE error counter
     const szh_u64 *uoff;               // inverse: ranks of the boxes' verbatim values (which variant a wavefront runs)
-    int dbg_no_code_stores;            // development (timing only, wrong streams): the sweep without its 2 N bytes of code stores
     const unsigned *vflags; int fw;    // inverse: per box `fw` words, bit (row / RPL) = that group of rows holds a verbatim value (k_omp_scatter); fw = 0: none
 };
 
@@ -226,7 +225,7 @@ struct sweep {
             constexpr int w = decltype(W)::value, d = S::dco(w);
             static_assert(fdiv(d, LINE) == 1 && fdiv(d + 1, LINE) == 1, "a finished row leaves during the next iteration");
             if constexpr (PHASE != PH_FIRST && fmod(d + 1, LINE) == U)
-                if (!a.dbg_no_code_stores) st_stream<NT_ST>(cptr + ((int64_t)(it - 1) * C1 + S::RPC * w) * S::CROW, wq);
+                st_stream<NT_ST>(cptr + ((int64_t)(it - 1) * C1 + S::RPC * w) * S::CROW, wq);
             if constexpr (PHASE != PH_FIRST && fmod(d, LINE) == U) {
                 constexpr int loff = -fdiv(d, LINE);
                 wq = lds_get16(ring, slot_off(ls_of(loff), (unsigned)(S::RPC * w + 1) + cev_r) + cev_lds);

@@ -73,13 +73,10 @@ template <class T> struct szh_qargs {
     int ndim3;                // fmt 2: 1 = a 3-D array (one boundary case of ITS compressor has no fabs, sz_float.c:2459)
     int backoff;              // FILL wavefront: sleep units between two rounds that delivered nothing
     int wide;                 // 1: the granule rows of a tile lie within 4 GB of the tile's first row: 16-byte buffer accesses with 32-bit offsets
-    int trace_tile;           // development: (TI << 16) | TJ of the tile whose left-hand hand-off is logged round by round (SZH_TRACE_LOG)
     const T *xr;              // k_beam, compress, arrays with regression blocks: the RECONSTRUCTIONS of their points (k_reg_points), natural layout
     int pub_lines;            // k_beam with tile_done: lines between two progress words of a wavefront (a multiple of 8; 0: 32)
     const uint8_t *ptflags;   // k_beam, arrays with regression blocks: per point, 1 = the point lies in a regression block (k_reg_points; zeros elsewhere)
     const unsigned *reg_ready; // k_beam, when its inputs are made in slices beside the sweep (compress: k_reg_points; decompress: k_permute<1> + k_unpred): planes whose inputs are in memory (nullptr: all, before the launch)
-    int dbg;                  // development: 1 = no hand-off at all (timing only, results become WRONG), 4 = no issue priorities
-    szh_u64 *trace;           // optional (development): per pencil {t_start, t_start, t_first_trip, t_end, wait spins, -, xcc, 0} + per-trip detail
 };
 
 template <class T> struct szh_gran;
@@ -124,13 +121,6 @@ template <class T> struct szh_tile_lds {
     int *scratch;             // [2][64] helper wavefronts (STORE, FILL): per-row values for a per-slot minimum
 };
 #define SZH_FROWS 17
-
-// development plumbing (timing-only "free run", per-pencil trace stamps) is compiled out of the production library; `make dev`
-// builds libszhip_dev.so with it (SZ_HIP_DBG / SZ_HIP_TRACE, tools/gpu_trace.py)
-#ifndef SZH_DEV
-#define SZH_DEV 0
-#endif
-#define SZH_TRACE_LOG 2048   /* entries {clock, value} per hand-off log (development): producer steps, STORE rounds, FILL rounds, consumer steps */
 
 #define SZH_U 16 /* steps per loop trip: a trip first requests all of its inputs (values and halo granules), then steps */
 #if defined(__HIPCC__)
@@ -218,7 +208,7 @@ SZH_HD int szh_msst_state(const szh_qargs<T> &a, double quotient)
 
 // B: back end. Requires: NL, lane(l), shfl_up(dst,src,d), shfl_up1(dst,src) (d = 1; lanes with lane % 8 == 0 may receive anything),
 //    readlane(src,lane), all(pred), lds_order(), touch(v) (the value must be in its register here),
-//    ld_gran(p), st_gran(p,v), ld_flag(p), st_flag(p,v), backoff(n), nap(), clock(), where(),
+//    ld_gran(p), st_gran(p,v), ld_flag(p), st_flag(p,v), backoff(n), nap(),
 //    gbuf_t, make_gbuf(base), ld_gran2_b(buf, byte offset, a, b), st_gran2_b(...): two granules in one 16-byte access relative to a wavefront-uniform base,
 //    ld16(p, T(&)[16/sizeof T]), st16(p, const T(&)[...]) -- one 16-byte vector access (4-byte aligned for 4/8-byte T),
 //    lds_ld(p), lds_st(p,v), lds_ld_u(p) (wavefront-uniform address), lds_fence() (orders this wavefront's LDS accesses),
@@ -244,15 +234,12 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
     const int nbz = G.g2.num;
     const int cap_lor = a.cap - 2, cap_reg = a.cap, radius = a.radius;
     const T eb = a.eb, recip = a.recip, mean = a.mean;
-    const bool free_run = SZH_DEV && a.dbg == 1;   // development: no hand-off at all (timing only, results are wrong)
-    szh_u64 *const trace = SZH_DEV ? a.trace : nullptr;
     const int pi = I % B::TPI, pj = J % B::TPJ;
-    const bool cut = SZH_DEV && a.dbg == 2;     // development: tiles cut apart (no hand-off across tile boundaries; timing only, results are wrong)
-    const bool pubJ = (J + 1 < a.nJ) && !free_run && !(cut && pj == B::TPJ - 1), pubI = (I + 1 < a.nI) && !free_run && !(cut && pi == B::TPI - 1);
+    const bool pubJ = J + 1 < a.nJ, pubI = I + 1 < a.nI;
     const int myslot = szh_slot<B>(I, J);
     uint16_t *const cring = L.cring + (size_t)myslot * (SZH_XC + 1) * 64;
     // producers: a pencil of this tile, or the virtual producer the FILL wavefront keeps filled
-    const bool hasPJ = J > 0 && !free_run && !(cut && pj == 0), hasPI = I > 0 && !free_run && !(cut && pi == 0);
+    const bool hasPJ = J > 0, hasPI = I > 0;
     const int slotPJ = pj > 0 ? myslot - 1 : szh_vslot_left<B>(I), slotPI = pi > 0 ? myslot - B::TPJ : szh_vslot_top<B>(J);
     // consumers: a pencil of this tile (its step counter tells which ring slots it has read), or the STORE wavefront
     const bool consJ_in = pubJ && pj + 1 < B::TPJ, consI_in = pubI && pi + 1 < B::TPI;
@@ -345,10 +332,8 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
     // Only those positions need the pre-scattered value, so a lane fetches its 16 values of a trip only when one of them does.
     unsigned zcols[NL];
     SZH_FORL zcols[l] = 0;
-    const bool no_ld = SZH_DEV && (a.dbg == 3 || a.dbg == 5), no_st = SZH_DEV && (a.dbg == 3 || a.dbg == 4);   // development: the sweep loads / stores nothing (timing only, results are wrong)
     auto load_x = [&](int t0, xbuf_t &xr) {
         const T *src = DEC ? a.out : a.data;
-        if (no_ld) { SZH_FORL { SZH_UNROLL for (int s = 0; s < SZH_U; ++s) xr[s][l] = (T)0; } return; }
         // interior trips: the SZH_U columns of every lane (skews 0..14) lie inside its row, so the whole wavefront takes the vector
         // path -- a wavefront-uniform branch (a per-lane choice between the two paths makes hipcc wait for the vector loads before
         // it issues the other path's loads into the same registers, which would undo the prefetch).  Lanes outside the array load
@@ -382,7 +367,6 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
         }
     };
     auto store_out = [&](int t0, xbuf_t &xr) {
-        if (no_st) return;
         const bool interior = t0 >= SZH_U && t0 + SZH_U <= r2;   // wavefront-uniform, as in load_x
         if (interior) {
             SZH_FORL {
@@ -415,7 +399,6 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
         return i < r0 && j < r1;
     };
     auto move_codes = [&](int c0) {
-        if (no_st) return;
         if (vec_codes && c0 + 8 <= r2) {
             SZH_FORL {
                 const int row = B::lane(l);
@@ -452,17 +435,15 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
         }
     };
     // bounded wait until an LDS counter reaches `need`; returns the value seen.  A lost hand-off ends the launch, it must not hang the GPU
-    szh_u64 tr_spins = 0;
     auto wait_ctr = [&](const unsigned *ctr, int need) -> int {
         int v = (int)B::lds_ld_u(ctr);
         unsigned spins = 0;
-        while (v < need && !free_run) {
+        while (v < need) {
             if (++spins > (1u << 24)) { SZH_FORL { if (B::lane(l) == 0) B::st_flag(a.err, 1u); } break; }
             if ((spins & 4095u) == 0 && B::ld_flag(a.err) != 0) break;
             B::backoff(1);
             v = (int)B::lds_ld_u(ctr);
         }
-        if (SZH_DEV) tr_spins += spins;
         return v;
     };
 
@@ -473,22 +454,10 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
 
     const int tsteps = r2 + 14;
     int flushed = 0, filled = 0;   // code-ring columns already written back (compress) / already brought in (decompress)
-    szh_u64 tr_start = 0, tr_first = 0;
-    if (trace) tr_start = B::clock();
-    const bool detail = trace && I == a.nI / 2 && J == a.nJ / 2;
-    szh_u64 *steplog = nullptr;   // development: clock at the end of every step of the observed producer / consumer pencil
-    if (trace) {
-        const int oTI = a.trace_tile >> 16, oTJ = a.trace_tile & 0xffff;
-        szh_u64 *logs = trace + (int64_t)a.nI * a.nJ * 8 + 256;
-        if (I == oTI * B::TPI && J == oTJ * B::TPJ - 1) steplog = logs;                              // producer: last pencil column of the tile to the left
-        if (I == oTI * B::TPI && J == oTJ * B::TPJ) steplog = logs + 3 * 2 * SZH_TRACE_LOG;         // consumer: first pencil of the observed tile
-    }
-    szh_u64 *dt = trace ? trace + (int64_t)a.nI * a.nJ * 8 : nullptr;
     // (decompress learns which values it needs from the trip's own codes: it asks at the top of the trip; double has no registers to spare for
     //  a second buffer next to 2 x 4 pencils per workgroup)
     constexpr bool PREFETCH = !DEC && sizeof(T) == 4;
     auto trip = [&](const int t0, xbuf_t &xr, xbuf_t &xnext) {
-        if (detail && t0 / SZH_U < 64) { SZH_FORL { if (B::lane(l) == 0) dt[(t0 / SZH_U) * 4 + 0] = B::clock(); } }
         // ring space: the consumers must have read the slots this trip overwrites.  A pencil of the tile reads column k no later
         // than its step k+7; the STORE wavefront counts the columns it has forwarded.  (This trip writes columns <= t0 + SZH_U - 8.)
         if (pubJ) { if (consJ_in) wait_ctr(L.cstep + myslot + 1, t0 + SZH_U - B::RL); else wait_ctr(L.spubJ + myslot, t0 + SZH_U - 7 - B::RL); }
@@ -515,7 +484,6 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
             stb1[l] = st1[l] >= ftrash0 ? st1[l] : st1[l] + w0;
             stb2[l] = st2[l] >= ftrash0 ? st2[l] : st2[l] + w0;
         }
-        if (detail && t0 / SZH_U < 64) { SZH_FORL { if (B::lane(l) == 0) dt[(t0 / SZH_U) * 4 + 1] = B::clock(); } }
         SZH_UNROLL
         for (int s = 0; s < SZH_U; ++s) {
             const int t = t0 + s;
@@ -648,13 +616,9 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
             // store needs no wait behind the face stores -- only the compiler must keep the order (lds_order)
             B::lds_order();
             SZH_FORL { B::lds_st(L.cstep + myslot, (unsigned)(t + 1)); }
-            if (SZH_DEV && steplog && t < SZH_TRACE_LOG) { SZH_FORL { if (B::lane(l) == 0) { steplog[2 * t] = B::clock(); steplog[2 * t + 1] = (szh_u64)(pstepJ < pstepI ? pstepJ : pstepI); } } }
             // half-way through the trip: write back the code columns that are complete (keeps the 32-column ring from wrapping)
         }
-        if (detail && t0 / SZH_U < 64) { SZH_FORL { if (B::lane(l) == 0) dt[(t0 / SZH_U) * 4 + 2] = B::clock(); } }
         if (DEC) store_out(t0, xr);
-        if (detail && t0 / SZH_U < 64) { SZH_FORL { if (B::lane(l) == 0) dt[(t0 / SZH_U) * 4 + 3] = B::clock(); } }
-        if (trace && t0 == 0) tr_first = B::clock();
     };
     if (PREFETCH) {
         load_x(0, xr0);
@@ -666,15 +630,6 @@ SZH_HD void szh_pencil_body(const szh_qargs<T> &a, int I, int J, const szh_tile_
         for (int t0 = 0; t0 < tsteps; t0 += SZH_U) trip(t0, xr0, xr0);
     }
     if (!DEC) { for (; flushed < r2; flushed += 8) move_codes(flushed); }
-    if (trace) {
-        const szh_u64 tr_end = B::clock();
-        SZH_FORL {
-            if (B::lane(l) == 0) {
-                szh_u64 *tp = trace + ((int64_t)I * a.nJ + J) * 8;
-                tp[0] = tr_start; tp[1] = tr_start; tp[2] = tr_first; tp[3] = tr_end; tp[4] = tr_spins; tp[6] = B::where(); tp[7] = 0;
-            }
-        }
-    }
 }
 
 // does pencil (I,J) touch a regression block?  (collective over the wavefront's lanes)
@@ -797,7 +752,7 @@ SZH_HD void szh_tile_store(const szh_qargs<T> &a, int TI, int TJ, const szh_tile
         const szh_rowmap<B> m(B::lane(l));
         // J-face rows come from the pencils of the tile's LAST column, I-face rows from its LAST row
         const int I = m.isJ ? TI * B::TPI + m.pp : TI * B::TPI + B::TPI - 1, J = m.isJ ? TJ * B::TPJ + B::TPJ - 1 : TJ * B::TPJ + m.pp;
-        en[l] = m.valid && I < a.nI && J < a.nJ && !(SZH_DEV && (a.dbg == 1 || a.dbg == 2));
+        en[l] = m.valid && I < a.nI && J < a.nJ;
         if (m.isJ) en[l] = en[l] && J + 1 < a.nJ && 8 * I + m.r < r0;
         else en[l] = en[l] && I + 1 < a.nI && (m.r < 8 ? 8 * J + m.r < r1 : J > 0);
         penc[l] = (int64_t)I * a.nJ + J;
@@ -809,7 +764,6 @@ SZH_HD void szh_tile_store(const szh_qargs<T> &a, int TI, int TJ, const szh_tile
     int reported[NL];
     SZH_FORL reported[l] = -1;
     unsigned idle = 0;
-    int slog = 0;
     for (;;) {
         bool none[NL], fin[NL];
         int steps[NL];
@@ -852,10 +806,6 @@ SZH_HD void szh_tile_store(const szh_qargs<T> &a, int TI, int TJ, const szh_tile
             pk[l] += n;
             none[l] = n == 0; fin[l] = pk[l] >= r2;
             steps[l] = en[l] ? (pk[l] >= r2 ? (1 << 29) : pk[l] + m.sr) : (1 << 30);
-        }
-        if (SZH_DEV && a.trace && TI == (a.trace_tile >> 16) && TJ + 1 == (a.trace_tile & 0xffff) && slog < SZH_TRACE_LOG) {
-            SZH_FORL { if (B::lane(l) == 0) { szh_u64 *lg = a.trace + (int64_t)a.nI * a.nJ * 8 + 256 + 1 * 2 * SZH_TRACE_LOG; lg[2 * slog] = B::clock(); lg[2 * slog + 1] = (szh_u64)pk[l]; } }
-            ++slog;
         }
         // per pencil: ring space for the producer (columns forwarded on every row) and the progress word for the consumers' FILL
         int cols[NL], gcols[NL], gsteps[NL];
@@ -912,7 +862,7 @@ SZH_HD void szh_tile_fill(const szh_qargs<T> &a, int TI, int TJ, const szh_tile_
         const szh_rowmap<B> m(B::lane(l));
         // J-face rows feed the pencils of the tile's FIRST column (from the tile to the left), I-face rows its FIRST row (from above)
         const int I = m.isJ ? TI * B::TPI + m.pp : TI * B::TPI, J = m.isJ ? TJ * B::TPJ : TJ * B::TPJ + m.pp;
-        en[l] = m.valid && I < a.nI && J < a.nJ && !(SZH_DEV && (a.dbg == 1 || a.dbg == 2));
+        en[l] = m.valid && I < a.nI && J < a.nJ;
         if (m.isJ) en[l] = en[l] && J > 0 && 8 * I + m.r < r0;
         else en[l] = en[l] && I > 0 && (m.r < 8 ? 8 * J + m.r < r1 : J > 0);
         const int64_t pp = m.isJ ? (int64_t)I * a.nJ + (J - 1) : (int64_t)(I - 1) * a.nJ + J;   // the producing pencil
@@ -929,7 +879,6 @@ SZH_HD void szh_tile_fill(const szh_qargs<T> &a, int TI, int TJ, const szh_tile_
         } else { wa = B::ld_gran(p); wb = B::ld_gran(p + 1); }
     };
     unsigned idle = 0;
-    int flog = 0;
     for (;;) {
         // how far have the producers got?  (every lane asks for its own row's producer: a handful of distinct words per round)
         szh_u64 g[KF][NW][NL];
@@ -981,10 +930,6 @@ SZH_HD void szh_tile_fill(const szh_qargs<T> &a, int TI, int TJ, const szh_tile_
             none[l] = lead == 0; fin[l] = fk[l] >= r2;
             // the consumer reads column k of this row at its step k + hs: "steps covered" on the scale of the step counters (+7)
             vsteps[l] = en[l] ? (fk[l] >= r2 ? (1 << 29) : fk[l] + m.hs + 7) : (1 << 30);
-        }
-        if (SZH_DEV && a.trace && TI == (a.trace_tile >> 16) && TJ == (a.trace_tile & 0xffff) && flog < SZH_TRACE_LOG) {
-            SZH_FORL { if (B::lane(l) == 0) { szh_u64 *lg = a.trace + (int64_t)a.nI * a.nJ * 8 + 256 + 2 * 2 * SZH_TRACE_LOG; lg[2 * flog] = B::clock(); lg[2 * flog + 1] = (szh_u64)fk[l]; } }
-            ++flog;
         }
         B::lds_fence();          // the values are in the ring before the counter says so
         int gv[NL];

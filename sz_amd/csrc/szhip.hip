@@ -14,7 +14,6 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
-#include <future>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -34,7 +33,6 @@ double now_ms()
 
 } // namespace
 
-struct szhip_sweep_gate { std::mutex m; hipEvent_t last = nullptr; int lanes = 2; };
 // compress calls of this process that are inside the library right now, whatever their context: the chain / kernel overlap of an array with
 // regression blocks is only taken by a call that starts alone (see compress_impl)
 static std::atomic<int> g_compress_calls{0};
@@ -124,6 +122,7 @@ struct szhip_chain_pool {
     }
 };
 
+constexpr int SZH_STAGE_T = 4;                   // host threads of a staged copy (staged_copy)
 struct szhip_ctx {
     int device = 0;
     int cus = 256;                               // compute units of `device` (hipDeviceAttributeMultiprocessorCount): persistent kernels launch one workgroup per CU at most
@@ -131,7 +130,6 @@ struct szhip_ctx {
     hipStream_t stream2 = nullptr;   // the fit + selection pass runs here, concurrently with the interval optimiser's sampling and host decisions
     hipEvent_t ev_in = nullptr, ev_fit = nullptr, ev_feed = nullptr, ev_sec = nullptr;
     int settle_probes = 0, settle_rejected = 0;   // settle_streams: queue probes made, streams replaced
-    int side_prio = 0;               // 1: stream2 at the lowest, stream3 at the highest stream priority (create_ctx)
     hipStream_t stream3 = nullptr;   // the block-ordering pass of finished tile rows, while the sweep is still running on `stream` (created on first use)
     hipEvent_t ev_perm = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -140,21 +138,19 @@ struct szhip_ctx {
     // Huffman decode: two rounds without asking the device in between (checked with the caller's next synchronisation); a call whose
     // start guesses were still moving after them is repeated once with a synchronisation per round (with_ticket_fallback)
     bool hdec_sync_rounds = false, hdec_unconverged = false;
-    // arrays in flight (szhip_pool), SZ_HIP_SWEEP_GATE=1: the sweeps of the lanes take turns instead of sharing the CUs.  Measured at 512^3
-    // with two lanes over 60 steps: 294 - 303 GB/s gated against 305 - 319 free-running, so it is OFF by default.  The gate belongs to the
-    // pool (nullptr for a lone context).
-    struct szhip_sweep_gate *gate = nullptr;
-    hipEvent_t ev_gate = nullptr;
+    // a lane of a pool (several arrays in flight, szhip_pool); false for a lone context.  (The lanes' sweeps share the CUs: taking turns
+    // measured slower at 512^3 with two lanes over 60 steps, 294 - 303 GB/s against 305 - 319.)
+    bool gate = false;
     unsigned long long *hdec_res = nullptr;      // pinned: {symbols the payload holds, starts still moving after round 1}, copied asynchronously
     // workspaces (grow-only)
-    DevBuf lor_bits, reg_flags, reg_rank, coef_compact, in, out, codes_nat, codes_blk, coef, blk_lor, faceI, faceJ, rb_down, rb_right, rb_vals, pt_flags, feed_word, progress, trace, order, small, hist, col_zeros, col_zeros64,
+    DevBuf lor_bits, reg_flags, reg_rank, coef_compact, in, out, codes_nat, codes_blk, coef, blk_lor, faceI, faceJ, rb_down, rb_right, rb_vals, pt_flags, feed_word, progress, order, small, hist, col_zeros, col_zeros64,
         seg_bits, seg_zeros, seg_bitoff, seg_zoff, seg_hist, seg_tab, col_off, partial, samples, unpred, stream_buf, chunk_bits, chunk_off, code_tab, len_tab, dec_tab,
         starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe;
     void *pinned = nullptr; size_t pinned_cap = 0;
     void *pinned2 = nullptr; size_t pinned2_cap = 0;   // target of the second stream's copies (indicator bits, regression-block count)
     // bulk copies between the caller's pageable arrays and the device: SZH_STAGE_T host threads, two pinned buffers + events each
-    void *stage_buf[8][2] = {};
-    hipEvent_t stage_ev[8][2] = {};
+    void *stage_buf[SZH_STAGE_T][2] = {};
+    hipEvent_t stage_ev[SZH_STAGE_T][2] = {};
     void *pinned3 = nullptr; size_t pinned3_cap = 0;
     int streams_independent = -1;                      // -1 not probed yet; 1: work on stream2 proceeds while a kernel on stream is running
     void *coh = nullptr; size_t coh_cap = 0;           // host-coherent (uncached on the GPU) pinned memory the wavefront kernel reads while the host writes   // the regression coefficients on their way to the host chain and back
@@ -215,12 +211,9 @@ static int with_ticket_fallback(szhip_ctx *ctx, F &&run)
 extern "C" {
 
 
-// side_prio: the second / third stream at the lowest / highest priority the device offers.  HIP maps the streams of one priority onto a few
-// hardware queues, and whether two streams of a context share one is the luck of what else the process has created (measured, round 4, one call
-// after the other at 512^3: 236 - 241 GB/s when the fit pass and the sampling chain, or the sweep and the slices' passes, sat on one queue,
-// 274 - 279 otherwise); streams of different priorities never share one.  Lanes of a pool keep equal priorities (a lane whose main stream
-// outranks the other's would always be dispatched first).
-static int create_ctx(szhip_ctx **out, int device, int side_prio, int main_high = 0)
+// Every stream of a context has the default priority (which streams share a hardware queue is settled by settle_streams instead; streams
+// of different priorities were tried for that, round 4).
+static int create_ctx(szhip_ctx **out, int device)
 {
     if (!out) return SZHIP_ERR_ARG;
     int count = 0;
@@ -233,18 +226,11 @@ static int create_ctx(szhip_ctx **out, int device, int side_prio, int main_high 
     szhip_ctx *ctx = new szhip_ctx();
     ctx->device = device;
     { int c = 0; if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && c > 0) ctx->cus = c; }
-    int mlo = 0, mhi = 0;
-    if (hipSetDevice(device) != hipSuccess || (main_high && hipDeviceGetStreamPriorityRange(&mlo, &mhi) != hipSuccess) ||
-        (main_high ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, mhi) : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx; return SZHIP_ERR_NODEVICE;
     }
     for (int i = 0; i < 6; ++i) if (hipEventCreate(&ctx->ev[i]) != hipSuccess) { delete ctx; return SZHIP_ERR_NODEVICE; }
-    // (SZ_HIP_STREAM_PRIO: 0 = equal priorities, 1 = second stream low / third high, 2 = the other way round)
-    const int sprio = tune_int("SZ_HIP_STREAM_PRIO", side_prio);
-    ctx->side_prio = sprio;
-    int plo = 0, phi = 0;
-    if (sprio && hipDeviceGetStreamPriorityRange(&plo, &phi) != hipSuccess) { plo = 0; phi = 0; }
-    if ((sprio ? hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, sprio == 2 ? phi : plo) : hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking)) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fit, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_feed, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_sec, hipEventDisableTiming) != hipSuccess) { delete ctx; return SZHIP_ERR_NODEVICE; }
@@ -254,7 +240,7 @@ static int create_ctx(szhip_ctx **out, int device, int side_prio, int main_high 
 
 int szhip_create(szhip_ctx **out, int device)
 {
-    const int rc = create_ctx(out, device, 0);
+    const int rc = create_ctx(out, device);
     if (rc == SZHIP_OK) settle_streams(*out, nullptr, 0);
     return rc;
 }
@@ -265,7 +251,7 @@ void szhip_destroy(szhip_ctx *ctx)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     delete ctx->chain_pool; ctx->chain_pool = nullptr;
-    DevBuf *bufs[] = {&ctx->lor_bits, &ctx->reg_flags, &ctx->reg_rank, &ctx->coef_compact, &ctx->in, &ctx->out, &ctx->codes_nat, &ctx->codes_blk, &ctx->coef, &ctx->blk_lor, &ctx->faceI, &ctx->faceJ, &ctx->rb_down, &ctx->rb_right, &ctx->rb_vals, &ctx->pt_flags, &ctx->feed_word, &ctx->progress, &ctx->trace,
+    DevBuf *bufs[] = {&ctx->lor_bits, &ctx->reg_flags, &ctx->reg_rank, &ctx->coef_compact, &ctx->in, &ctx->out, &ctx->codes_nat, &ctx->codes_blk, &ctx->coef, &ctx->blk_lor, &ctx->faceI, &ctx->faceJ, &ctx->rb_down, &ctx->rb_right, &ctx->rb_vals, &ctx->pt_flags, &ctx->feed_word, &ctx->progress,
                       &ctx->order, &ctx->small, &ctx->hist, &ctx->col_zeros, &ctx->col_zeros64, &ctx->seg_bits, &ctx->seg_zeros, &ctx->seg_bitoff, &ctx->seg_zoff, &ctx->seg_hist, &ctx->seg_tab, &ctx->col_off, &ctx->partial,
                       &ctx->samples, &ctx->unpred, &ctx->stream_buf, &ctx->chunk_bits, &ctx->chunk_off, &ctx->code_tab,
                       &ctx->len_tab, &ctx->dec_tab, &ctx->starts, &ctx->ends, &ctx->counts, &ctx->offs, &ctx->dirty, &ctx->zcnt, &ctx->zpos,
@@ -276,8 +262,7 @@ void szhip_destroy(szhip_ctx *ctx)
     if (ctx->pinned3) hipHostFree(ctx->pinned3);
     if (ctx->coh) hipHostFree(ctx->coh);
     if (ctx->hdec_res) hipHostFree(ctx->hdec_res);
-    if (ctx->ev_gate) hipEventDestroy(ctx->ev_gate);
-    for (int w = 0; w < SZH_STAGE_TMAX; ++w) for (int k = 0; k < 2; ++k) { if (ctx->stage_buf[w][k]) hipHostFree(ctx->stage_buf[w][k]); if (ctx->stage_ev[w][k]) hipEventDestroy(ctx->stage_ev[w][k]); }
+    for (int w = 0; w < SZH_STAGE_T; ++w) for (int k = 0; k < 2; ++k) { if (ctx->stage_buf[w][k]) hipHostFree(ctx->stage_buf[w][k]); if (ctx->stage_ev[w][k]) hipEventDestroy(ctx->stage_ev[w][k]); }
     for (int i = 0; i < 6; ++i) if (ctx->ev[i]) hipEventDestroy(ctx->ev[i]);
     if (ctx->ev_in) hipEventDestroy(ctx->ev_in);
     if (ctx->ev_fit) hipEventDestroy(ctx->ev_fit);
@@ -299,7 +284,6 @@ struct szhip_pool_job {
     int out_on_device; unsigned char *out; size_t out_size; szhip_stats stats; int rc; bool done;
 };
 struct szhip_pool {
-    szhip_sweep_gate gate;
     std::vector<szhip_ctx *> ctx;
     std::vector<std::thread> workers;
     std::mutex mu;
@@ -332,11 +316,9 @@ int szhip_pool_create(szhip_pool **out, int device, int lanes)
     szhip_pool *p = new szhip_pool();
     for (int i = 0; i < lanes; ++i) {
         szhip_ctx *c = nullptr;
-        // (SZ_HIP_LANE_PRIO=1, development: every other lane's main stream at the highest priority, so that two lanes never share a hardware queue)
-        const int rc = create_ctx(&c, device, 0, lanes > 1 && tune_int("SZ_HIP_LANE_PRIO", 0) ? (i & 1) : 0);
+        const int rc = create_ctx(&c, device);
         if (rc != SZHIP_OK) { for (szhip_ctx *x : p->ctx) szhip_destroy(x); delete p; return rc; }
-        p->gate.lanes = lanes;
-        if (lanes > 1) { c->gate = &p->gate; if (hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming) != hipSuccess) c->gate = nullptr; }
+        c->gate = lanes > 1;
         // (against the earlier lanes' main AND second streams: a lane's fit pass behind another lane's sweep is as bad as two sweeps in a row)
         { std::vector<hipStream_t> mains; for (szhip_ctx *x : p->ctx) { mains.push_back(x->stream); mains.push_back(x->stream2); } settle_streams(c, mains.data(), (int)mains.size(), lanes == 1); }
         p->ctx.push_back(c);
@@ -574,7 +556,7 @@ int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes)
     if (!ctx || !dst) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     DevBuf *bufs[] = {&ctx->coef, &ctx->blk_lor, &ctx->codes_nat, &ctx->codes_blk, &ctx->hist, &ctx->col_zeros, &ctx->col_off,
-                      &ctx->unpred, &ctx->stream_buf, &ctx->trace, &ctx->rb_down, &ctx->rb_right, &ctx->small};
+                      &ctx->unpred, &ctx->stream_buf, &ctx->rb_down, &ctx->rb_right, &ctx->small};
     if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0]))) return SZHIP_ERR_ARG;
     if (!bufs[which]->p || bufs[which]->cap < bytes) return SZHIP_ERR_ARG;
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -199,12 +199,6 @@ struct GpuBackend {
         uint4 w; __builtin_memcpy(&w, v, 16);
         *reinterpret_cast<uint4 *>(p) = w;
     }
-    __device__ static szh_u64 clock() { return wall_clock64(); } // 100 MHz, chip-wide
-#ifdef SZH_HIPSIM
-    __device__ static szh_u64 where() { return 0; }
-#else
-    __device__ static szh_u64 where() { unsigned x = 0; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x)); return x; }
-#endif
     __device__ static void nap() { __builtin_amdgcn_s_sleep(40); } // ~1 us
 };
 
@@ -698,13 +692,9 @@ __global__ __launch_bounds__(256) void k_hist_u16(const uint16_t *__restrict__ c
 #define SZH_ZCAP 128
 template <int DIR>
 __device__ __forceinline__ void permute_body(const szh_geom3 &G, const uint16_t *__restrict__ src, uint16_t *__restrict__ dst,
-                                             unsigned *col_zeros, int segb, unsigned *zcnt, unsigned *zpos,
-                                             unsigned *hist, unsigned hist_bins, int tile_elems, int col0, int dbg, const int segi, const int nseg_all)
-{   // dbg (development, timing only): 1 = no loads in the gather, 2 = no LDS stores in the gather, 4 = no block-order side, 8 = return after the prologue
-   // col0: the launch covers block columns col0 .. col0 + gridDim.x - 1 (a slice of the array along dim 0)
-    // hist (DIR 0 only, hist_bins > 0): the code histogram of Huffman.c:165-174 is taken here, while the codes sit in LDS anyway (one
-    // pass over the code array less): per workgroup in LDS behind the tile, the peak symbol (radius = hist_bins / 2, most of a smooth
-    // field) counted by ballot instead of by atomics, non-empty bins added to the global histogram at the end
+                                             unsigned *col_zeros, int segb, unsigned *zcnt, unsigned *zpos, int col0, const int segi, const int nseg_all)
+{   // col0: the launch covers block columns col0 .. col0 + gridDim.x - 1 (a slice of the array along dim 0)
+    // (taking the code histogram here as well, while the codes sit in LDS, measured no faster than the separate pass beside this one)
     __shared__ unsigned zc_s, zp_s[SZH_ZCAP];
     if (threadIdx.x == 0) zc_s = 0;
     __syncthreads();
@@ -742,13 +732,7 @@ __device__ __forceinline__ void permute_body(const szh_geom3 &G, const uint16_t 
         if (e < eregion) { const int bl = qdiv(e, esz, m_esz); const int rem = e - bl * esz; s2 = G.g2.early; koff = bl * s2; row = qdiv(rem, s2, m_e2); kk = rem - row * s2; }
         else { const int e2 = e - eregion; const int bl = qdiv(e2, lsz, m_lsz); const int rem = e2 - bl * lsz; s2 = G.g2.late; koff = nE * G.g2.early + bl * s2; row = qdiv(rem, s2, m_l2); kk = rem - row * s2; }
     };
-    if (dbg & 8) return;
     unsigned zeros = 0;
-    unsigned *const lh = reinterpret_cast<unsigned *>(tile + ((tile_elems + 1) & ~1));
-    const bool do_hist = DIR == 0 && hist_bins > 0;
-    const unsigned peak = hist_bins / 2;
-    unsigned peak_cnt = 0;
-    if (do_hist) { for (unsigned b = threadIdx.x; b < hist_bins; b += 256) lh[b] = 0; }
     const int head = (int)(base & 7);                             // elements of the first 16-byte group that belong to the previous segment
     if (DIR == 0) {
         for (int r = wid; r < rows; r += 4) {
@@ -760,29 +744,26 @@ __device__ __forceinline__ void permute_body(const szh_geom3 &G, const uint16_t 
         __syncthreads();
     }
     // block-order side: the segment is one contiguous range [base, base + total); 16-byte groups by absolute address
-    if (!(dbg & 4)) {
-        const int ngroups = (head + total + 7) / 8;
-        for (int g = threadIdx.x; g < ngroups; g += 256) {
-            const int e0 = g * 8 - head;                           // may be negative in the first group
-            int elo = e0 < 0 ? 0 : e0, ehi = e0 + 8 > total ? total : e0 + 8;
-            int row, kk, s2, koff;
-            locate(elo, row, kk, s2, koff);
-            uint16_t v[8];
-            if (DIR == 1) {
-                if (ehi - elo == 8) { const uint4 w = *reinterpret_cast<const uint4 *>(src + base + e0); __builtin_memcpy(v, &w, 16); }
-                else { for (int e = elo; e < ehi; ++e) v[e - e0] = src[base + e]; }
-            }
-            for (int e = elo; e < ehi; ++e) {
-                const int ti = row * kp + kshift + koff + kk;
-                if (DIR == 0) v[e - e0] = tile[ti]; else tile[ti] = v[e - e0];
-                if (v[e - e0] == 0) { ++zeros; const unsigned q = atomicAdd(&zc_s, 1u); if (q < SZH_ZCAP) zp_s[q] = (unsigned)e; }
-                if (do_hist) { const unsigned c = v[e - e0]; if (c == peak) ++peak_cnt; else if (c < hist_bins) atomicAdd(&lh[c], 1u); }
-                if (++kk == s2) { kk = 0; if (++row == rows && e + 1 < ehi) locate(e + 1, row, kk, s2, koff); }
-            }
-            if (DIR == 0) {
-                if (ehi - elo == 8) { uint4 w; __builtin_memcpy(&w, v, 16); *reinterpret_cast<uint4 *>(dst + base + e0) = w; }
-                else { for (int e = elo; e < ehi; ++e) dst[base + e] = v[e - e0]; }
-            }
+    const int ngroups = (head + total + 7) / 8;
+    for (int g = threadIdx.x; g < ngroups; g += 256) {
+        const int e0 = g * 8 - head;                               // may be negative in the first group
+        int elo = e0 < 0 ? 0 : e0, ehi = e0 + 8 > total ? total : e0 + 8;
+        int row, kk, s2, koff;
+        locate(elo, row, kk, s2, koff);
+        uint16_t v[8];
+        if (DIR == 1) {
+            if (ehi - elo == 8) { const uint4 w = *reinterpret_cast<const uint4 *>(src + base + e0); __builtin_memcpy(v, &w, 16); }
+            else { for (int e = elo; e < ehi; ++e) v[e - e0] = src[base + e]; }
+        }
+        for (int e = elo; e < ehi; ++e) {
+            const int ti = row * kp + kshift + koff + kk;
+            if (DIR == 0) v[e - e0] = tile[ti]; else tile[ti] = v[e - e0];
+            if (v[e - e0] == 0) { ++zeros; const unsigned q = atomicAdd(&zc_s, 1u); if (q < SZH_ZCAP) zp_s[q] = (unsigned)e; }
+            if (++kk == s2) { kk = 0; if (++row == rows && e + 1 < ehi) locate(e + 1, row, kk, s2, koff); }
+        }
+        if (DIR == 0) {
+            if (ehi - elo == 8) { uint4 w; __builtin_memcpy(&w, v, 16); *reinterpret_cast<uint4 *>(dst + base + e0) = w; }
+            else { for (int e = elo; e < ehi; ++e) dst[base + e] = v[e - e0]; }
         }
     }
     if (DIR == 1) {
@@ -801,12 +782,7 @@ __device__ __forceinline__ void permute_body(const szh_geom3 &G, const uint16_t 
     }
     zeros = wave_sum_u32(zeros);
     if ((threadIdx.x & 63) == 0 && zeros) atomicAdd(&col_zeros[col], zeros);
-    if (do_hist) {
-        peak_cnt = wave_sum_u32(peak_cnt);
-        if ((threadIdx.x & 63) == 0 && peak_cnt) atomicAdd(&lh[peak], peak_cnt);
-    }
     __syncthreads();
-    if (do_hist) { for (unsigned b = threadIdx.x; b < hist_bins; b += 256) { const unsigned c = lh[b]; if (c) atomicAdd(&hist[b], c); } }
     const unsigned zc = zc_s;
     const size_t slot = (size_t)col * nseg_all + segi;
     if (threadIdx.x == 0) zcnt[slot] = zc;
@@ -816,12 +792,11 @@ __device__ __forceinline__ void permute_body(const szh_geom3 &G, const uint16_t 
 // segment, launching the 21 675 workgroups of a 512^3 array and their prologues was 0.08 of the pass's 0.3 ms.
 template <int DIR>
 __global__ __launch_bounds__(256) void k_permute(szh_geom3 G, const uint16_t *__restrict__ src, uint16_t *__restrict__ dst,
-                                                 unsigned *col_zeros, int segb, unsigned *zcnt, unsigned *zpos,
-                                                 unsigned *hist, unsigned hist_bins, int tile_elems, int col0, int dbg = 0)
+                                                 unsigned *col_zeros, int segb, unsigned *zcnt, unsigned *zpos, int col0)
 {
     const int nseg_all = (G.g2.num + segb - 1) / segb;
     for (int segi = (int)blockIdx.y; segi < nseg_all; segi += (int)gridDim.y) {
-        permute_body<DIR>(G, src, dst, col_zeros, segb, zcnt, zpos, hist, hist_bins, tile_elems, col0, dbg, segi, nseg_all);
+        permute_body<DIR>(G, src, dst, col_zeros, segb, zcnt, zpos, col0, segi, nseg_all);
         __syncthreads();                                           // (the tile and the workgroup's counters are reused)
     }
 }

@@ -39,7 +39,7 @@ static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, si
 // the column-per-lane sweep of szh_ompcol.h serves 32 x 32 box faces (any number of planes), two boxes to a wavefront, rows read 16 bytes at a time
 static bool omp_col_applies(const szh_omp_geom &g, const void *base, size_t row_pitch_bytes)
 {
-    return g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0 && ((uintptr_t)base & 15u) == 0 && row_pitch_bytes % 16 == 0 && tune_int("SZ_HIP_OMP_COL", 1) != 0;
+    return g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0 && ((uintptr_t)base & 15u) == 0 && row_pitch_bytes % 16 == 0;
 }
 
 template <class T>
@@ -114,14 +114,13 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
     unsigned *d_ucount = (unsigned *)ctx->zcnt.p; T *d_first = (T *)ctx->samples.p;
     u64 *d_ucount64 = (u64 *)ctx->col_zeros64.p, *d_uoff = (u64 *)ctx->col_off.p;
     const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
-    const bool lean = tune_int("SZ_HIP_OMP_LEAN", 1) != 0;                     // (0: the entropy stage of round 3, kept for comparison)
-    const bool box_hist = lean && intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
+    const bool box_hist = intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
     bool sweep_counted = true;
     HIPCHK(hipEventRecord(ctx->ev[2], st));
     if (omp_col_applies(g, d_in, r2 * sizeof(T))) {        // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
         szh_oc::sweep_args<T> oa;
         oa.g = g; oa.data = d_in; oa.out = nullptr; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
-        oa.ucount = d_ucount; oa.ucount64 = d_ucount64; oa.first = d_first; oa.uoff = nullptr; oa.vflags = nullptr; oa.fw = 0; oa.dbg_no_code_stores = tune_int("SZ_HIP_OMP_DBG_NOSTORE", 0);
+        oa.ucount = d_ucount; oa.ucount64 = d_ucount64; oa.first = d_first; oa.uoff = nullptr; oa.vflags = nullptr; oa.fw = 0;
         // (with a histogram per box coming anyway, the boxes' counts of verbatim values are its bins 0: the sweep leaves the counting out --
         //  two vector instructions per step of a kernel that is bound by exactly those)
         if (box_hist) { sweep_counted = false; hipLaunchKernelGGL((k_omp_col<T, 32, 32, false, false>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa); }
@@ -200,7 +199,7 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
     TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8));
     u64 *d_box_bytes = (u64 *)ctx->reg_flags.p, *d_box_off = (u64 *)ctx->reg_rank.p;
     const size_t lds3 = (size_t)intervals * 8 + ((size_t)SZH_OMP_R3 * maxlen / 32 + 4) * 4 + 16;
-    const bool fast = box_hist && maxlen <= 32 && intervals <= 2048 && lds3 <= 60 * 1024 && tune_int("SZ_HIP_OMP_ENC", 3) == 3;
+    const bool fast = box_hist && maxlen <= 32 && intervals <= 2048 && lds3 <= 60 * 1024;
     if (fast) {
         // ---- the usual case (code words of at most 32 bits, a histogram per box): ONE upload -- the header and the packed code table
         // `code << 8 | len` --, one launch for the boxes' sizes and places (k_omp_layout), one that packs the codes and writes every table
@@ -222,7 +221,7 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
         HIPCHK(hipGetLastError());
         szh_omp_tables tb;
         tb.stream = d_stream; tb.hdr = (const unsigned char *)ctx->code_tab.p; tb.hdr_len = (unsigned)hdr_len;
-        tb.off_ucount = off_ucount; tb.off_first = off_first; tb.off_unpred = off_unpred; tb.off_sizes = off_sizes; tb.first = d_first; tb.dbg = tune_int("SZ_HIP_OMP_DBG", 0);
+        tb.off_ucount = off_ucount; tb.off_first = off_first; tb.off_unpred = off_unpred; tb.off_sizes = off_sizes; tb.first = d_first;
         hipLaunchKernelGGL((k_omp_encode_box3<T>), dim3((unsigned)g.nb), dim3(256), lds3, st, g, d_in, (const uint16_t *)d_codes, d_packed, intervals, maxlen, (const u64 *)d_box_off,
                            (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8, (unsigned *)d_stream,
                            (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR), tb);
@@ -230,7 +229,7 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
         // (the verbatim values go through an aligned buffer: their table lies at whatever byte offset the tree's size gives it, and byte
         //  stores from the kernel were half of its 0.1 ms for them)
         if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
-    } else if (lean) {
+    } else {
         TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
         TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
         HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
@@ -257,40 +256,12 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
                                (unsigned *)d_stream, (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR));
         HIPCHK(hipGetLastError());
         if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
-    } else {
-    TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
-    TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
-    HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_stream + off_ucount, d_ucount, (size_t)g.nb * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_stream + off_first, d_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (E > 0) {
-        TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T)));
-        hipLaunchKernelGGL((k_omp_gather<T>), dim3((unsigned)g.nb), dim3(256), 0, st, g, d_in, (const uint16_t *)d_codes, (const unsigned *)d_ucount, (const u64 *)d_uoff, (T *)ctx->unpred.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
-    }
-    const int64_t nchunks = (int64_t)g.nb * g.cpb;
-    TRY(ensure(ctx, ctx->chunk_bits, (size_t)nchunks * 8)); TRY(ensure(ctx, ctx->chunk_off, (size_t)nchunks * 8));
-    hipLaunchKernelGGL(k_omp_chunk_bits, dim3((unsigned)nchunks), dim3(256), 0, st, g, (const uint16_t *)d_codes, (const uint8_t *)ctx->len_tab.p, (u64 *)ctx->chunk_bits.p);
-    HIPCHK(hipGetLastError());
-    TRY(scan_u64(ctx, (const u64 *)ctx->chunk_bits.p, nchunks, (u64 *)ctx->chunk_off.p, sm + SM_TOTAL_BITS));
-    hipLaunchKernelGGL(k_omp_box_bytes, dim3((unsigned)((g.nb + 255) / 256)), dim3(256), 0, st, g.nb, g.cpb, (const u64 *)ctx->chunk_off.p, (const u64 *)(sm + SM_TOTAL_BITS), d_box_bytes);
-    HIPCHK(hipGetLastError());
-    TRY(scan_u64(ctx, (const u64 *)d_box_bytes, g.nb, d_box_off, sm + SM_SCRATCH));
-    HIPCHK(hipMemcpyAsync(d_stream + off_sizes, d_box_bytes, (size_t)g.nb * 8, hipMemcpyDeviceToDevice, st));
-    if (total_bits > 0) {
-        hipLaunchKernelGGL(k_omp_encode, dim3((unsigned)nchunks), dim3(256), 0, st, g, (const uint16_t *)d_codes, (const u64 *)ctx->code_tab.p, (const uint8_t *)ctx->len_tab.p,
-                           (const u64 *)ctx->chunk_off.p, (const u64 *)d_box_off, (u64)off_pay * 8, (unsigned *)d_stream);
-        HIPCHK(hipGetLastError());
-    }
     }
     HIPCHK(hipEventRecord(ctx->ev[4], st));
     u64 h_small[SM_COUNT];
     HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if ((!lean && h_small[SM_TOTAL_BITS] != total_bits) || h_small[SM_TOTAL_UNPRED] != E || (lean && (unsigned)h_small[SM_ERR] != 0) ||
+    if (h_small[SM_TOTAL_UNPRED] != E || (unsigned)h_small[SM_ERR] != 0 ||
         h_small[SM_SCRATCH] < (total_bits + 7) / 8 || h_small[SM_SCRATCH] > (total_bits + 7) / 8 + (u64)g.nb)
         FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: entropy stage mismatch");
     const size_t total_len = off_pay + (size_t)h_small[SM_SCRATCH];
@@ -402,15 +373,14 @@ int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stre
         const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
         const int tab_lds_lut = (size_t)n_nodes_dec * 8 <= 13 * 1024;
         const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds_lut ? ((size_t)n_nodes_dec * 8 + 15) / 16 * 16 : 0);
-        if (single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024 && tune_int("SZ_HIP_OMP_LEAN", 1) != 0) {
+        if (single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024) {
             const size_t lut_off = (dtab.size() * 4 + 63) / 64 * 64;
             TRY(ensure(ctx, ctx->dec_tab, lut_off + SZH_LUT_BYTES));          // (grown before the table went up: see the copy above)
             hipLaunchKernelGGL(k_hdec_build_lut, dim3(SZH_LUT_SIZE / 256), dim3(256), 0, st, (const unsigned *)ctx->dec_tab.p, (uint4 *)((char *)ctx->dec_tab.p + lut_off));
             HIPCHK(hipGetLastError());
-            const int per_wg = std::max(1, tune_int("SZ_HIP_OMP_HDEC_PER_WG", 1));         // (several small boxes per workgroup, sharing its copy of the tables: measured slower, 1.59 against 1.42 ms for 32 768 boxes)
-            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)((g.nb + per_wg - 1) / per_wg)), dim3(256), lds_lut, st, g.bel, (const unsigned char *)(d_stream + off_pay), (unsigned)off_pay,
+            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)g.nb), dim3(256), lds_lut, st, g.bel, (const unsigned char *)(d_stream + off_pay), (unsigned)off_pay,
                                (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, n_nodes_dec, tab_lds_lut,
-                               (const uint4 *)((char *)ctx->dec_tab.p + lut_off), stage_bytes, d_codes, (unsigned *)(sm + SM_ERR), g.nb, per_wg);
+                               (const uint4 *)((char *)ctx->dec_tab.p + lut_off), stage_bytes, d_codes, (unsigned *)(sm + SM_ERR));
         } else {
         const int tab_lds = dtab.size() * 4 <= 16384;            // node table and payload in LDS when they are small (the usual case: 2 - 3 bits per code)
         const unsigned pay_cap = (unsigned)std::min<u64>(max_box, 24576);
@@ -442,7 +412,7 @@ int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stre
             HIPCHK(hipGetLastError());
         }
         szh_oc::sweep_args<T> oa;
-        oa.vflags = d_vflags; oa.fw = fw; oa.dbg_no_code_stores = 0;
+        oa.vflags = d_vflags; oa.fw = fw;
         oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
         oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = (T *)ctx->samples.p; oa.uoff = (const u64 *)ctx->col_off.p;
         hipLaunchKernelGGL((k_omp_col<T, 32, 32, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);

@@ -109,7 +109,6 @@ int probe_streams(szhip_ctx *ctx)
     return SZHIP_OK;
 }
 
-int tune_int(const char *name, int def);
 // Do kernels on `b` run while a kernel on `a` is still running?  (As above, with a kernel instead of the copy.)  *shared = 1: no, the two
 // streams sit on one hardware queue.
 static int probe_pair(szhip_ctx *ctx, hipStream_t a, hipStream_t b, int *shared)
@@ -140,7 +139,7 @@ static int probe_pair(szhip_ctx *ctx, hipStream_t a, hipStream_t b, int *shared)
 // 248 GB/s against 340.  So a new context PROBES: a kernel that waits (bounded, ~4 ms) on the one stream, a trivial kernel on the other; a side
 // stream that does not get through is replaced by a freshly created one (the rejected streams stay alive until the search is over, so that the
 // runtime's next choice is another queue), a few times over.  `mains`: the main streams of the pool's earlier lanes (a lane's streams must
-// not share a queue with those either).  SZ_HIP_SETTLE=0: take the streams as they come.
+// not share a queue with those either).
 static void settle_one(szhip_ctx *ctx, hipStream_t *victim, const std::vector<hipStream_t> &against, std::vector<hipStream_t> &rejected, int *probes)
 {
     for (int attempt = 0; attempt < 6; ++attempt) {
@@ -164,7 +163,6 @@ static void settle_streams(szhip_ctx *ctx, const hipStream_t *mains, int n_mains
 #ifdef SZH_SYNC_LAUNCH
     (void)ctx; (void)mains; (void)n_mains; (void)third;             // (the CPU shim runs every kernel at its launch)
 #else
-    if (!tune_int("SZ_HIP_SETTLE", 1)) return;
     std::vector<hipStream_t> rejected, against(mains, mains + n_mains);
     int probes = 0;
     if (n_mains) settle_one(ctx, &ctx->stream, against, rejected, &probes);      // this lane's main stream against the earlier lanes'
@@ -174,7 +172,6 @@ static void settle_streams(szhip_ctx *ctx, const hipStream_t *mains, int n_mains
     if (third && ctx->stream3) { against.push_back(ctx->stream2); settle_one(ctx, &ctx->stream3, against, rejected, &probes); }
     ctx->settle_probes = probes; ctx->settle_rejected = (int)rejected.size();
     for (hipStream_t r : rejected) hipStreamDestroy(r);
-    if (tune_int("SZ_HIP_SETTLE_LOG", 0)) fprintf(stderr, "szhip: streams settled after %d probes, %d streams replaced\n", probes, (int)rejected.size());
 #endif
 }
 
@@ -185,19 +182,18 @@ static void settle_streams(szhip_ctx *ctx, const hipStream_t *mains, int n_mains
 // host threads each own two pinned buffers and take every SZH_STAGE_T-th chunk: memcpy into (out of) a pinned buffer, asynchronous DMA on
 // the context's stream, the other buffer meanwhile.  The call returns when the last byte has arrived.
 int tune_int(const char *name, int def);
-constexpr int SZH_STAGE_T = 4, SZH_STAGE_TMAX = 8;     // default / most threads (SZ_HIP_STAGE_THREADS)
 constexpr size_t SZH_STAGE_CHUNK = 8u << 20;
 int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool to_device)
 {
     hipStream_t st = ctx->stream;
     // (SZ_HIP_STAGE_CHUNK_KB: smaller chunks, so that tests reach this path with small arrays)
     const size_t chunk = std::min(SZH_STAGE_CHUNK, (size_t)std::max(1, tune_int("SZ_HIP_STAGE_CHUNK_KB", (int)(SZH_STAGE_CHUNK >> 10))) << 10);
-    if (bytes < 4 * chunk || tune_int("SZ_HIP_STAGED_COPY", 1) == 0) {
+    if (bytes < 4 * chunk) {
         HIPCHK(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return SZHIP_OK;
     }
-    const int nthr = std::min(SZH_STAGE_TMAX, std::max(1, tune_int("SZ_HIP_STAGE_THREADS", SZH_STAGE_T)));
+    constexpr int nthr = SZH_STAGE_T;
     for (int w = 0; w < nthr; ++w)
         for (int k = 0; k < 2; ++k)
             if (!ctx->stage_buf[w][k]) {
@@ -245,7 +241,7 @@ int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool t
     return SZHIP_OK;
 }
 
-// launch tuning knobs (development): environment overrides of the wavefront kernel's wait parameters
+// an environment switch (INTEGRATION.md lists them), read on every call so that tests can set it between calls
 int tune_int(const char *name, int def)
 {
     const char *e = getenv(name);
@@ -268,14 +264,14 @@ int scan_u64(szhip_ctx *ctx, const u64 *in, int64_t n, u64 *out, u64 *total_dev,
 
 // layout of the "small" device scratch (u64 slots)
 
+constexpr size_t SZH_PERM_TILE_BYTES = 32 * 1024;   // the tile budget of k_permute (choose_segb)
 int choose_segb(const szh_geom3 &G, size_t elem, size_t budget)
 {
     const size_t rows = (size_t)G.g0.early * G.g1.early;
     size_t per_block = rows * (size_t)G.g2.early * elem;
     int segb = (int)(budget / (per_block ? per_block : 1));
     if (segb < 1) segb = 1;
-    const int cap = std::max(1, tune_int("SZ_HIP_PERM_SEGB_MAX", 32));
-    if (segb > cap) segb = cap;
+    if (segb > 32) segb = 32;
     if (segb > G.g2.num) segb = G.g2.num;
     return segb;
 }
@@ -296,7 +292,6 @@ int prepare_pencil(szhip_ctx *ctx, const szh_geom3 &G, int nw, int tpi, int tpj,
     TRY(ensure(ctx, ctx->faceI, (size_t)nI * nJ * 9 * rowg + 64, true));   // + 64: a 16-byte granule pair may reach one granule past a row's end
     TRY(ensure(ctx, ctx->faceJ, (size_t)nI * nJ * 8 * rowg + 64, true));
     TRY(ensure(ctx, ctx->progress, (size_t)nI * nJ * 2 * sizeof(u64), true));
-    if (tune_int("SZ_HIP_TRACE", 0)) TRY(ensure(ctx, ctx->trace, ((size_t)nI * nJ * 8 + 256 + 4 * 2 * SZH_TRACE_LOG) * sizeof(u64), true));
     const int nTI = (nI + tpi - 1) / tpi, nTJ = (nJ + tpj - 1) / tpj;
     if (ctx->order_nI != nTI || ctx->order_nJ != nTJ) {
         std::vector<unsigned> ord((size_t)nTI * nTJ);
@@ -310,12 +305,20 @@ int prepare_pencil(szhip_ctx *ctx, const szh_geom3 &G, int nw, int tpi, int tpj,
     return SZHIP_OK;
 }
 
+// k_pencil's FILL wavefront: sleep units between two rounds that delivered nothing
+constexpr int SZH_FILL_BACKOFF = 4;
+// k_pencil: the granule rows of a tile lie within 4 GB of the tile's first row (16-byte buffer accesses with 32-bit offsets)
+template <class T> static int pencil_wide(const szh_geom3 &G, int nJ)
+{
+    using TS = szh_tile_shape<T>;
+    return (double)TS::TPI * nJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9 && (double)TS::TPJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9;
+}
 // k_pencil's grid: one workgroup per tile (a lone context: the inverse sweep at 512^3 takes 1.47 ms either way), or that many persistent
 // workgroups drawing tiles from the ticket counter (a pool lane: fewer workgroups that only poll for their predecessors -- two M-field
-// arrays in flight 111 -> 136 GB/s with 512, 127 with 256).  SZ_HIP_PENCIL_WGS overrides (0 = one per tile).
+// arrays in flight 111 -> 136 GB/s with 512, 127 with 256).
 template <class QA> static unsigned pencil_grid(szhip_ctx *ctx, QA &a, int ntiles)
 {
-    const int cap = tune_int("SZ_HIP_PENCIL_WGS", ctx->gate ? 512 : 0);
+    const int cap = ctx->gate ? 512 : 0;
     a.persist = cap > 0 && cap < ntiles;
     return (unsigned)(a.persist ? cap : ntiles);
 }
@@ -343,13 +346,13 @@ int launch_beam(szhip_ctx *ctx, const szh_geom3 &G, szh_qargs<T> a, hipStream_t 
     a.faceI = (szh_u64 *)ctx->rb_down.p; a.faceJ = (szh_u64 *)ctx->rb_right.p;
     a.nI = g.nKB; a.nJ = g.nJG;
     if (a.ticket_mode == 2) a.ticket_mode = 1;
-    if (ctx->gate && tune_int("SZ_HIP_RB_POOL_ATOMIC", 1)) a.ticket_mode = 0;
+    if (ctx->gate) a.ticket_mode = 0;
 #ifdef SZH_SYNC_LAUNCH
     const unsigned wgs = (unsigned)tiles;      // (the CPU shim runs workgroups one after the other: a workgroup per tile, in ticket order)
 #else
     // persistent workgroups in ticket order: as many as are resident at once (a tile's predecessors hold smaller tickets)
-    const int per_cu = std::max(1, tune_int("SZ_HIP_BEAM_WG_PER_CU", sizeof(T) == 4 ? 2 : 1));
-    const unsigned wgs = (unsigned)std::min<size_t>(tiles, (size_t)std::max(1, tune_int("SZ_HIP_BEAM_WGS", ctx->cus * per_cu)));
+    const int per_cu = sizeof(T) == 4 ? 2 : 1;
+    const unsigned wgs = (unsigned)std::min<size_t>(tiles, (size_t)ctx->cus * per_cu);
 #endif
     // arrays with regression blocks: their points are quantised / reconstructed by k_reg_points (no neighbour involved); the sweep takes
     // their reconstructions as its neighbours (compress: from a.xr; the inverse: they are in the output array already) and passes them through

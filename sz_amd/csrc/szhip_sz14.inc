@@ -48,8 +48,7 @@ int launch_pencil14(szhip_ctx *ctx, const szh_geom3 &G, u64 *sm, bool dec, const
     a.faceI = (szh_u64 *)ctx->faceI.p; a.faceJ = (szh_u64 *)ctx->faceJ.p; a.epoch = ++ctx->epoch;
     a.nI = nI; a.nJ = nJ; a.order = (const unsigned *)ctx->order.p;
     a.ticket = (unsigned *)(sm + SM_TICKET); a.err = (unsigned *)(sm + SM_ERR); a.ticket_mode = ctx->ticket_atomic ? 0 : tune_int("SZ_HIP_TICKET_MODE", 2);
-    a.progress = (szh_u64 *)ctx->progress.p; a.backoff = tune_int("SZ_HIP_BACKOFF", 4); a.wide = tune_int("SZ_HIP_WIDE", 1) && (double)TS::TPI * nJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9 && (double)TS::TPJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9;
-    a.trace = nullptr; a.dbg = 0;
+    a.progress = (szh_u64 *)ctx->progress.p; a.backoff = SZH_FILL_BACKOFF; a.wide = pencil_wide<T>(G, nJ);
     HIPCHK(hipEventRecord(ctx->ev[2], st));
     const unsigned pgrid = pencil_grid(ctx, a, ntiles);
     if (mt && dec) hipLaunchKernelGGL((k_pencil<T, true, true>), dim3(pgrid), dim3((TS::TPI * TS::TPJ + 2) * 64), 0, st, a);

@@ -263,7 +263,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         //  rounds of tools/gpu_pool_dbg.py -- errors, not wrong streams; none in 480 rounds with the serial order.  The lanes overlap one
         //  array's chain with the other's kernels anyway.
         //  A lone context takes the overlap only when no other compress call of the process is under way as this one starts.)
-        overlap = !beam_applies<T>(G, d_in, reg_count) && !two_d && !ctx->gate && !ctx->no_chain_overlap && g_compress_calls.load() <= 1 && tune_int("SZ_HIP_CHAIN_THREADS", 1) && tune_int("SZ_HIP_CHAIN_OVERLAP", 1);
+        overlap = !beam_applies<T>(G, d_in, reg_count) && !two_d && !ctx->gate && !ctx->no_chain_overlap && g_compress_calls.load() <= 1;
         if (overlap) { TRY(probe_streams(ctx)); overlap = ctx->streams_independent == 1; }
 #endif
         // (round 5) the beam sweep FED while it runs: the chains deliver block rows in the order the beam's planes need them, so the sweep is launched
@@ -273,7 +273,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         // Only where the chains are long (>= 65536 regression blocks = 0.25 ms): with a short chain there is nothing to hide, and the slices' kernels beside
         // the sweep cost more than they save (BASELINE configs[3]'s float64 slab, a few thousand regression blocks: 4.24 ms unfed, 5.36 fed).
         feed = beam_applies<T>(G, d_in, reg_count) && !ctx->gate && !ctx->no_chain_overlap && g_compress_calls.load() <= 1 && tune_int("SZ_HIP_BEAM_FEED", 1) &&
-               tune_int("SZ_HIP_CHAIN_THREADS", 1) && tune_int("SZ_HIP_CHAIN_POOL", 1) && G.g0.num >= 2 && reg_count >= (size_t)tune_int("SZ_HIP_FEED_MIN_REG", 65536);
+               G.g0.num >= 2 && reg_count >= (size_t)tune_int("SZ_HIP_FEED_MIN_REG", 65536);
 #ifndef SZH_SYNC_LAUNCH
         feed = feed && (G.d0 % 128) == 0;      // (a plane = whole cache lines of values, flags and codes: a line is never loaded while part of it is still to come)
 #endif
@@ -291,7 +291,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
             ~AvailAll() { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
         } avail_all{&chain_avail, reg_count};
         const size_t first_piece = (size_t)std::max(1, tune_int("SZ_HIP_CHAIN_EARLY_PIECE", 32768));
-        const bool two_pieces = feed && reg_count >= 4 * first_piece && tune_int("SZ_HIP_CHAIN_EARLY", 1);
+        const bool two_pieces = feed && reg_count >= 4 * first_piece;
         if (two_pieces) {
             for (int e = 0; e < 4; ++e)
                 HIPCHK(hipMemcpyAsync(hcoef + (size_t)e * reg_count, (const T *)ctx->coef_compact.p + (size_t)e * reg_count, first_piece * sizeof(T), hipMemcpyDeviceToHost, st));
@@ -338,7 +338,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
                     szhost_coeff_chain_one_p(is_double, chain_in, ind, reg_count, use_mean, e, &cf, &chain_done[e]);
                     make_section(e);
                 });
-        } else if (tune_int("SZ_HIP_CHAIN_THREADS", 1) && tune_int("SZ_HIP_CHAIN_POOL", 1)) {
+        } else {
             if (!ctx->chain_pool) { ctx->chain_pool = new szhip_chain_pool(); ctx->chain_pool->start(); }
             pool_busy = true;
             for (int e = 0; e < 4; ++e) chain_done[e] = feed && e >= ncoef ? reg_count : 0;
@@ -355,21 +355,6 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
                 __atomic_store_n(&chain_avail, reg_count, __ATOMIC_RELEASE);
             }
             if (!feed) ctx->chain_pool->wait_chains();           // the decoded coefficients are final: the main thread may ship them (the sections follow on the workers)
-        } else if (tune_int("SZ_HIP_CHAIN_THREADS", 1)) {
-            std::vector<std::promise<void>> chained(ncoef);
-            std::vector<std::future<void>> chained_f;
-            for (int e = 0; e < ncoef; ++e) chained_f.push_back(chained[e].get_future());
-            for (int e = 0; e < ncoef; ++e)
-                section_threads.emplace_back([&, e, chain_in, ind = all_reg.data()](std::promise<void> done) {
-                    chain_t0[e] = now_ms() - t_begin;
-                    szhost_coeff_chain_one(is_double, chain_in, ind, reg_count, use_mean, e, &cf);
-                    chain_t1[e] = now_ms() - t_begin;
-                    done.set_value();                     // the decoded coefficients of e are final: the main thread may ship them
-                    make_section(e);
-                }, std::move(chained[e]));
-            for (auto &f : chained_f) f.wait();
-        } else {
-            for (int e = 0; e < ncoef; ++e) { szhost_coeff_chain_one(is_double, chain_in, all_reg.data(), reg_count, use_mean, e, &cf); make_section(e); }
         }
         if (!feed) host_ms += now_ms() - h0;
         TP("chain done");
@@ -407,7 +392,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     if (segenc) {
         bool ok = intervals < 65536;
         const size_t fixed = ((size_t)intervals + 1) * 8 + 16 + szh_se::seg_window_words(G, 32) * 4 + 64;
-        const size_t lds_cap = (size_t)std::max(16, tune_int("SZ_HIP_SEG_LDS_KB", 63)) * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 24)) * 1024;
+        const size_t lds_cap = (size_t)63 * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 24)) * 1024;
         if (ok && fixed + szh_se::seg_tile_bytes(G, 1, se_vw) > lds_cap) ok = false;
         if (ok) {
             const size_t budget = std::min(lds_cap - fixed, std::max(want, szh_se::seg_tile_bytes(G, 1, se_vw)));
@@ -416,7 +401,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
             // a round of k_col_encode is 256 threads x NR runs: segments of just under a whole number of rounds of the usual block column's runs (the last one takes the rest)
             const int rows_typ = (2 * G.g0.split > G.g0.num ? G.g0.early : G.g0.late) * (2 * G.g1.split > G.g1.num ? G.g1.early : G.g1.late);
             const int per_round = std::max(1, 256 * szh_se::NR / std::max(1, rows_typ));
-            if (tune_int("SZ_HIP_SEG_ROUNDS", 1) && sb >= per_round) sb = sb / per_round * per_round;
+            if (sb >= per_round) sb = sb / per_round * per_round;
             if (const int f = tune_int("SZ_HIP_SEG_SEGB", 0)) sb = std::max(1, std::min(f, sb));
             se_segb = sb;
             se_nseg = (G.g2.num + se_segb - 1) / se_segb;
@@ -447,10 +432,10 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     // kernels take 2 - 4 x their lone time beside the sweep and slow it by ~0.1 ms; more slices, more of that).
     const int slices_req = tune_int("SZ_HIP_SLICES", ctx->gate ? tune_int("SZ_HIP_SLICES_POOL", 2) : 4);
     // (round 5) the beam sweep: every wavefront publishes how many of its lines have their codes in memory (szh_beam.h, `tile_done`: a word per
-    // wavefront, written every SZ_HIP_BEAM_PUB lines after write-through code stores and a vmcnt(0) -- a system-scope RELEASE per word cost ~35 us
+    // wavefront, written every 32 lines after write-through code stores and a vmcnt(0) -- a system-scope RELEASE per word cost ~35 us
     // each and took the sweep from 1.05 to 1.58 ms); a slice = the block rows whose lines every wavefront has passed.  Measured at 512^3, one call:
-    // S-field 2.12 ms unsliced, 1.94 - 1.96 with 3 - 6 slices; M-field 3.94 -> 3.82 (profiles/r05_beam_slices.txt).  SZ_HIP_BEAM_SLICES=0: off.
-    const bool sliced = use_beam && tune_int("SZ_HIP_BEAM_SLICES", 1) && slices_req > 1 && !tune_int("SZ_HIP_FUSE_HIST", 0) && !seghist;
+    // S-field 2.12 ms unsliced, 1.94 - 1.96 with 3 - 6 slices; M-field 3.94 -> 3.82 (profiles/r05_beam_slices.txt).
+    const bool sliced = use_beam && slices_req > 1 && !seghist;
     unsigned *tile_done = nullptr;
     const szh_bm::grid_t bgrid = szh_bm::make_grid(G);
     const size_t beam_words = (size_t)bgrid.nKB * bgrid.nJG * szh_bm::WPG;
@@ -458,26 +443,18 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         const size_t tiles = beam_words;
         TRY(ensure_coherent(ctx, 512 + tiles * 4));
         tile_done = (unsigned *)((char *)ctx->coh + 512);
-        if (!ctx->stream3) {
-            const int sprio = ctx->side_prio;
-            int plo = 0, phi = 0;
-            if (sprio && hipDeviceGetStreamPriorityRange(&plo, &phi) != hipSuccess) { plo = 0; phi = 0; }
-            if (sprio) HIPCHK(hipStreamCreateWithPriority(&ctx->stream3, hipStreamNonBlocking, sprio == 2 ? plo : phi));
-            else HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
-        }
+        if (!ctx->stream3) HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
         if (!ctx->ev_perm) HIPCHK(hipEventCreateWithFlags(&ctx->ev_perm, hipEventDisableTiming));
     }
     {
         szh_qargs<T> a; memset(&a, 0, sizeof(a));
-        a.tile_done = tile_done; a.pub_lines = tune_int("SZ_HIP_BEAM_PUB", 32);
+        a.tile_done = tile_done; a.pub_lines = 32;
         a.G = G; a.data = d_in; a.out = nullptr; a.codes = d_nat; a.blk_lor = d_lor; a.coef = d_coef; a.coef_stride = nb;
         a.eb = eb; a.recip = 1 / eb; a.mean = mean; a.cap = (int)intervals; a.radius = (int)intervals / 2; a.use_mean = use_mean;
         a.faceI = (szh_u64 *)ctx->faceI.p; a.faceJ = (szh_u64 *)ctx->faceJ.p; a.epoch = ++ctx->epoch;
-        a.nI = nI; a.nJ = nJ; a.order = (const unsigned *)ctx->order.p; a.no_reg = reg_count == 0 && tune_int("SZ_HIP_NO_REG_HINT", 1);
+        a.nI = nI; a.nJ = nJ; a.order = (const unsigned *)ctx->order.p; a.no_reg = reg_count == 0;
         a.ticket = (unsigned *)(sm + SM_TICKET); a.err = (unsigned *)(sm + SM_ERR); a.ticket_mode = ctx->ticket_atomic ? 0 : tune_int("SZ_HIP_TICKET_MODE", 2);
-        a.progress = (szh_u64 *)ctx->progress.p; a.backoff = tune_int("SZ_HIP_BACKOFF", 4); a.wide = tune_int("SZ_HIP_WIDE", 1) && (double)TS::TPI * nJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9 && (double)TS::TPJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9;
-        a.trace = tune_int("SZ_HIP_TRACE", 0) ? (szh_u64 *)ctx->trace.p : nullptr;
-        a.dbg = tune_int("SZ_HIP_DBG", 0); a.trace_tile = tune_int("SZ_HIP_TRACE_TILE", 1);
+        a.progress = (szh_u64 *)ctx->progress.p; a.backoff = SZH_FILL_BACKOFF; a.wide = pencil_wide<T>(G, nJ);
         a.coef_progress = nullptr;
         szh_u64 *coh_prog = nullptr;
         T *dec = nullptr;                                          // the decoded coefficients as the kernel reads them
@@ -499,18 +476,12 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
             a.coef_progress = coh_prog;
             a.coef = dec; a.coef_stride = nbp;
         }
-        {
-        std::unique_lock<std::mutex> gate_lock;
-        if (ctx->gate && tune_int("SZ_HIP_SWEEP_GATE", 0)) {
-            gate_lock = std::unique_lock<std::mutex>(ctx->gate->m);
-            if (ctx->gate->last && ctx->gate->last != ctx->ev_gate) HIPCHK(hipStreamWaitEvent(st, ctx->gate->last, 0));   // the other lane's sweep first
-        }
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         if (use_beam) {
             // the feed (see above): slices of block rows; a slice goes out when every chain has passed its last regression block
             auto feed_slices = [&]() -> int {
                 const double h1 = now_ms();
-                const int NF = std::max(2, std::min(G.g0.num, tune_int("SZ_HIP_FEED_SLICES", 12)));
+                const int NF = std::max(2, std::min(G.g0.num, 12));
                 const int64_t per_row = (int64_t)G.g1.num * G.g2.num;
                 size_t r_lo = 0; int b0_lo = 0;
                 for (int sl = 0; sl < NF; ++sl) {
@@ -564,8 +535,6 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        if (gate_lock.owns_lock()) { HIPCHK(hipEventRecord(ctx->ev_gate, st)); ctx->gate->last = ctx->ev_gate; }
-        }
         TP("pencil launched");
         S.quant_kernel_launches = 1;
         if (overlap) {
@@ -628,9 +597,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
         return SZHIP_OK;
     };
-    // (SZ_HIP_FUSE_HIST=1 takes the histogram inside k_permute instead: measured equal in kernel time -- 393 against 322 + 69 us -- and
-    //  without the overlap, so it is off)
-    const bool fuse_hist = !segenc && intervals <= 4096 && tune_int("SZ_HIP_FUSE_HIST", 0);
+    // (the histogram inside k_permute instead measured equal in kernel time -- 393 against 322 + 69 us -- and lost the overlap)
     if (seghist) {
         // (behind the sweep, on its stream: beside it the pass took from the sweep what it saved behind it -- 512^3: sweep 0.70 -> 0.76 ms with four slices of the older histogram)
         TRY(ensure(ctx, ctx->seg_hist, (size_t)ncols * intervals * 4));
@@ -641,7 +608,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(ctx->ev_fit, st));
     } else
-    if (!fuse_hist && !sliced) TRY(launch_hist((const uint16_t *)d_nat));    // next to the block-ordering pass (ribbon order: padding skipped by geometry)
+    if (!sliced) TRY(launch_hist((const uint16_t *)d_nat));    // next to the block-ordering pass (ribbon order: padding skipped by geometry)
     TRY(ensure(ctx, ctx->col_zeros, (size_t)ncols * 4));
     TRY(ensure(ctx, ctx->col_zeros64, (size_t)ncols * 8));
     TRY(ensure(ctx, ctx->col_off, (size_t)ncols * 8));
@@ -650,7 +617,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         // slices of block rows (dim 0): the codes are in natural order, so a slice's codes are ONE contiguous range for the histogram, and the
         // block-ordering pass takes the slice's block rows.  A slice starts when every wavefront of the sweep has published its lines.
         const int NS = std::min(slices_req, G.g0.num);
-        const int segb = choose_segb(G, 2, tune_int("SZ_HIP_PERM_TILE_KB", 32) * 1024);
+        const int segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
         const int nseg = (G.g2.num + segb - 1) / segb;
         TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * nseg * 4));
         TRY(ensure(ctx, ctx->zpos, (size_t)ncols * nseg * SZH_ZCAP * 4));
@@ -688,8 +655,8 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
                 if (h_hi > h_lo) hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), hist_lds, ctx->stream2, (const uint16_t *)d_nat, h_hi, intervals, rshift, use_lds, d_hist, h_lo);
                 if (!segenc)
                 hipLaunchKernelGGL((k_permute<0>), dim3((unsigned)((b0_hi - b0_done) * G.g1.num), std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + 16, ctx->stream3, G,
-                                   (const uint16_t *)d_nat, d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, d_hist, 0u,
-                                   (int)tile_el, b0_done * G.g1.num, 0);
+                                   (const uint16_t *)d_nat, d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p,
+                                   b0_done * G.g1.num);
                 HIPCHK(hipGetLastError());
                 b0_done = b0_hi;
             }
@@ -707,27 +674,13 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     auto permute_all = [&]() -> int {
     HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, st));
     {
-        const int segb = choose_segb(G, 2, tune_int("SZ_HIP_PERM_TILE_KB", 32) * 1024);
+        const int segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
         const int nseg = (G.g2.num + segb - 1) / segb;
         TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * nseg * 4));
         TRY(ensure(ctx, ctx->zpos, (size_t)ncols * nseg * SZH_ZCAP * 4));
-        // the histogram is taken inside the block-ordering pass when its bins fit behind the tile in LDS (SZ_HIP_FUSE_HIST=0: the
-        // separate pass, which is also what large alphabets get)
         const size_t tb = tile_bytes(G, segb, 2), tile_el = (tb + 1) / 2;
-        if (fuse_hist) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
-        // development (timing only): an EXTRA launch in front of the real one that stops early -- 8: after the prologue; 4: after the gather; 5: gather
-        // without its loads; 6: gather without its LDS stores.  It leaves nothing behind that the real launch does not overwrite.
-        if (const int pdbg = tune_int("SZ_HIP_PERM_DBG", 0)) {
-            hipLaunchKernelGGL((k_permute<0>), dim3(ncols, std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + 16, st, G, (const uint16_t *)d_nat,
-                               d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, d_hist, 0u, (int)tile_el, 0, (pdbg & 8) ? 8 : (pdbg | 4));
-        }
-        hipLaunchKernelGGL((k_permute<0>), dim3(ncols, std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + (fuse_hist ? (size_t)intervals * 4 : 0) + 16, st, G, (const uint16_t *)d_nat,
-                           d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p,
-                           d_hist, fuse_hist ? intervals : 0u, (int)tile_el, 0, 0);
-        if (fuse_hist) {
-            HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipEventRecord(ctx->ev_fit, st));
-        }
+        hipLaunchKernelGGL((k_permute<0>), dim3(ncols, std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + 16, st, G, (const uint16_t *)d_nat,
+                           d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, 0);
         perm_segb = segb; perm_nseg = nseg;
         HIPCHK(hipGetLastError());
     }
@@ -981,11 +934,11 @@ int huff_decode_device(szhip_ctx *ctx, u64 *sm, const unsigned char *d_bits, uns
         const size_t lds_pass = SZH_HDEC_LDS + SZH_LUT_SIZE * 4 + lds_tab, lds_write = SZH_HDEC_LDS + SZH_LUT_SIZE * 16 + lds_tab;
         const unsigned gsub = (unsigned)((nsub + 255) / 256);
         hipLaunchKernelGGL(k_hdec_init, dim3(gsub), dim3(256), 0, st, a);
-        const bool optimistic = !ctx->hdec_sync_rounds && tune_int("SZ_HIP_HDEC_OPTIMISTIC", 1) != 0;
+        const bool optimistic = !ctx->hdec_sync_rounds;
         // rounds without a host round trip: round 0 (warm-up guesses), then repair rounds that only touch the sub-sequences whose start
         // moved (a workgroup without one returns at once: ~10 us per idle round).  Smooth fields settle in round 1; wide code books
         // (codes longer than the look-up window resynchronise slowly) sometimes need a third
-        const int64_t opt_rounds = std::max(2, tune_int("SZ_HIP_HDEC_ROUNDS", 3));
+        constexpr int64_t opt_rounds = 3;
         int64_t iter = 0;
         for (;;) {
             a.warmup = iter == 0;                                  // the first round finds its own starts (k_hdec_pass)
@@ -1003,7 +956,6 @@ int huff_decode_device(szhip_ctx *ctx, u64 *sm, const unsigned char *d_bits, uns
             unsigned changed = 0;
             HIPCHK(hipMemcpyAsync(&changed, sm + SM_CHANGED, 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            if (tune_int("SZ_HIP_HDEC_TRACE", 0)) fprintf(stderr, "[szhip] Huffman decode round %lld: %u of %lld sub-sequence starts moved\n", (long long)iter, changed, (long long)nsub);
             if (!changed) break;
             if (++iter > nsub + 2) FAIL(SZHIP_ERR_INTERNAL, "Huffman decode did not converge");
         }
@@ -1204,13 +1156,13 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     // ---- header (szd_float.c:3491-3587)
     double h0 = now_ms();
     dec_header<T> H;
-    H.defer = tune_int("SZ_HIP_DEC_DEFER", 1) != 0;
+    H.defer = true;
     struct Finisher {     // the deferred part of the header (the coefficient sections) on its own thread; no return path may leave it running on H
         std::thread th; int rc = 0;
         void join() { if (th.joinable()) th.join(); }
         ~Finisher() { join(); }
     } finisher;
-    for (size_t want = std::min<size_t>(stream_len, (size_t)std::max(4, tune_int("SZ_HIP_DEC_HEADER_KB", 256)) << 10);;) {
+    for (size_t want = std::min<size_t>(stream_len, (size_t)256 << 10);;) {
         if (stream_on_device && want > avail) {
             TRY(ensure_pinned(ctx, want));
             HIPCHK(hipMemcpyAsync(ctx->pinned, stream_in, want, hipMemcpyDeviceToHost, st));
@@ -1266,7 +1218,7 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     T *d_out = (T *)out;
     if (!out_on_device) { TRY(ensure(ctx, ctx->out, (size_t)n * sizeof(T))); d_out = (T *)ctx->out.p; }
     T *d_sweep = d_out;                        // what the inverse sweep works on: the output array, or (mode 2) a ribbon-order value array
-    // (the inverse sweep fed slice by slice while it runs, round 5's SZ_HIP_DEC_FEED, measured slower -- 2.34 against 2.12 - 2.21 ms, profiles/r05_tried_fed_inverse_sweep.txt -- and
+    // (the inverse sweep fed slice by slice while it runs, tried in round 5, measured slower -- 2.34 against 2.12 - 2.21 ms, profiles/r05_tried_fed_inverse_sweep.txt -- and
     //  removed in round 6)
     // (round 6) where the inverse beam runs (codes and values in natural order): the zero codes per block column are counted first (k_col_zeros), and behind the checks below
     // ONE pass turns the block-ordered codes into natural order and drops the unpredictable values into the array (k_col_unpack, szh_segenc.h) -- k_permute<1> + k_unpred<1> before
@@ -1292,12 +1244,12 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     } else
     {
         HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, st));     // (k_permute<1> adds its segments' counts; k_col_zeros stores a column's)
-        const int segb = choose_segb(G, 2, tune_int("SZ_HIP_PERM_TILE_KB", 32) * 1024);
+        const int segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
         const int nseg = (G.g2.num + segb - 1) / segb;
         TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * nseg * 4));
         TRY(ensure(ctx, ctx->zpos, (size_t)ncols * nseg * SZH_ZCAP * 4));
         hipLaunchKernelGGL((k_permute<1>), dim3(ncols, std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", nseg)))), dim3(256), tile_bytes(G, segb, 2), st, G, (const uint16_t *)d_blk, d_nat,
-                           (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, (unsigned *)nullptr, 0u, 0, 0);
+                           (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, 0);
         perm_segb = segb; perm_nseg = nseg;
         HIPCHK(hipGetLastError());
     }
@@ -1381,11 +1333,9 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
         a.G = G; a.data = nullptr; a.out = d_out; a.codes = d_nat; a.blk_lor = (const uint8_t *)ctx->blk_lor.p; a.coef = (const T *)ctx->coef.p; a.coef_stride = nb;
         a.eb = eb; a.recip = 1 / eb; a.mean = mean; a.cap = (int)intervals; a.radius = (int)intervals / 2; a.use_mean = use_mean;
         a.faceI = (szh_u64 *)ctx->faceI.p; a.faceJ = (szh_u64 *)ctx->faceJ.p; a.epoch = ++ctx->epoch;
-        a.nI = nI; a.nJ = nJ; a.order = (const unsigned *)ctx->order.p; a.no_reg = reg_count == 0 && tune_int("SZ_HIP_NO_REG_HINT", 1);
+        a.nI = nI; a.nJ = nJ; a.order = (const unsigned *)ctx->order.p; a.no_reg = reg_count == 0;
         a.ticket = (unsigned *)(sm + SM_TICKET); a.err = (unsigned *)(sm + SM_ERR); a.ticket_mode = ctx->ticket_atomic ? 0 : tune_int("SZ_HIP_TICKET_MODE", 2);
-        a.progress = (szh_u64 *)ctx->progress.p; a.backoff = tune_int("SZ_HIP_BACKOFF", 4); a.wide = tune_int("SZ_HIP_WIDE", 1) && (double)TS::TPI * nJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9 && (double)TS::TPJ * 9.0 * (double)G.g2.count * szh_gran<T>::NW * 8.0 < 4.0e9;
-        a.trace = tune_int("SZ_HIP_TRACE", 0) ? (szh_u64 *)ctx->trace.p : nullptr;
-        a.dbg = tune_int("SZ_HIP_DBG", 0); a.trace_tile = tune_int("SZ_HIP_TRACE_TILE", 1);
+        a.progress = (szh_u64 *)ctx->progress.p; a.backoff = SZH_FILL_BACKOFF; a.wide = pencil_wide<T>(G, nJ);
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         if (dec_beam) {
             TRY((launch_beam<T, true>(ctx, G, a, st, reg_count))); S.quant_kernel = 2;

@@ -703,11 +703,10 @@ void szhost_coeff_chain_one_p(int is_double, void *coef, const unsigned char *in
                               size_t *progress)
 {
     const int variant = (is_double || use_mean) ? 1 : 0;          /* 1: |diff| * (1 / prec), 0: |diff| / prec (sz_float.c:7133 against :6795, sz_double.c) */
-    const char *sw = getenv("SZ_HIP_CHAIN_FAST");
     int owned = 0;
     size_t steps = 0;
     for (size_t b = 0; b < nblocks; b++) steps += indicator[b] == 0;      /* the chain's length: the regression blocks */
-    const chain_tab *tab = (sw && sw[0] == '0') ? NULL : chain_tab_get(is_double, variant, out->prec[e], steps, &owned);
+    const chain_tab *tab = chain_tab_get(is_double, variant, out->prec[e], steps, &owned);
     if (!tab) { szhost_coeff_chain_one_ref(is_double, coef, indicator, nblocks, use_mean, e, out, progress); return; }
     if (is_double) { CHAIN_FAST(double, uint64_t, fabs, CHAIN_LEAN_F64, ) }
     else { CHAIN_FAST(float, uint32_t, fabsf, CHAIN_LEAN_F32, ) }

@@ -48,8 +48,6 @@ struct SimBackend {
     static void nap() {}
     template <class E, int N> static void ld16(const E *p, E (&v)[N]) { memcpy(v, p, 16); }
     template <class E, int N> static void st16(E *p, const E (&v)[N]) { memcpy(p, v, 16); }
-    static szh_u64 clock() { return 0; }
-    static szh_u64 where() { return 0; }
 };
 
 template <class T, bool DEC>

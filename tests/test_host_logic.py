@@ -400,3 +400,24 @@ def test_chain_table_cache_full_and_short_chains(L, monkeypatch):
             assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and a[2] == b[2], (minsteps, k)
             for e in range(4):
                 assert np.array_equal(a[1][e], b[1][e]), (minsteps, k, e)
+
+
+def test_environment_switches_match_the_integration_table():
+    """The `SZ_HIP_*` names in the product sources are exactly the switches of INTEGRATION.md's table, and every switch the table
+    marks `test` is set somewhere in tests/ or bench.py (a test-only switch that nothing sets selects a path that nothing runs)."""
+    used = set()
+    for d in (os.path.join(ROOT, "sz_amd", "csrc"), os.path.join(ROOT, "include")):
+        for dirpath, dirnames, files in os.walk(d):
+            dirnames[:] = [x for x in dirnames if x != "variants"]          # (other builds of the library, not sources)
+            for f in files:
+                if f.endswith((".c", ".cpp", ".h", ".hip", ".inc")):
+                    used |= set(re.findall(r"SZ_HIP_[A-Z0-9_]+", open(os.path.join(dirpath, f), errors="replace").read()))
+    rows = re.findall(r"^\| `(SZ_HIP_[A-Z0-9_]+)` \|.*\| (user|test) \|$", open(os.path.join(ROOT, "INTEGRATION.md")).read(), flags=re.M)
+    table = dict(rows)
+    assert len(table) == len(rows), "a switch is listed twice"
+    assert used == set(table), f"read but not listed: {sorted(used - set(table))}; listed but not read: {sorted(set(table) - used)}"
+    setters = open(os.path.join(ROOT, "bench.py")).read()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "tests")):
+        setters += "".join(open(os.path.join(dirpath, f)).read() for f in files if f.endswith(".py"))
+    unset = sorted(n for n, who in table.items() if who == "test" and not re.search(r"\b" + n + r"\b", setters))
+    assert not unset, f"test-only switches that no test sets: {unset}"

@@ -12,7 +12,6 @@ SRC = r'''#include <hip/hip_runtime.h>
 #include "%s/sz_amd/csrc/szhip_kernels.h"
 #define BOX(T, D, V) template __global__ void k_omp_box<T, D, V>(szh_omp_geom, const T*, T*, T, T, int, uint16_t*, unsigned*, u64*, T*, const T*, const u64*);
 BOX(float, false, true) BOX(float, true, true) BOX(double, false, true) BOX(double, true, true) BOX(float, false, false)
-template __global__ void k_omp_gather<float>(szh_omp_geom, const float*, const uint16_t*, const unsigned*, const u64*, float*);
 ''' % ROOT
 FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt".split()
 
