@@ -1,4 +1,4 @@
-// szh_segenc.h -- the Huffman packing of the SZ 2.1 type array STRAIGHT FROM NATURAL ORDER (round 6).
+// szh_segenc.h -- the Huffman packing of the SZ 2.1 type array STRAIGHT FROM NATURAL ORDER.
 //
 // Reference: the quantisation codes are stored block by block (sz_float.c:7064, :7359), coded as one bit string (Huffman.c:205-308,
 // encode_withTree), and the unpredictable values follow in the same order (sz_float.c:7288).
@@ -13,16 +13,21 @@
 //   k_col_bits    (larger alphabets, after k_hist_u16) the same two numbers by a pass over the column's rows
 //   k_col_scan    both exclusive scans, and the word of the stream at every column boundary cleared: the two workgroups that share it OR
 //                 their bits in; every other word is written whole by exactly one workgroup -- the stream buffer needs no memset
-//   k_col_encode  the column in SEGMENTS of `segb` blocks: a segment's rows into LDS (natural order, coalesced; the next segment's rows are
-//                 on their way meanwhile), then read in block order -- a thread takes NR consecutive runs (a run = one row of one block,
-//                 s2 codes side by side in LDS) --, packed as k_encode32 packs (lengths summed, one scan per round, 64-bit accumulator,
-//                 words ORed into an LDS window, the window out in whole 4-byte words; a partial last word stays for the next round);
-//                 the unpredictable values of its zero codes go to their places in the list on the way.
+//   k_col_encode  the column in SEGMENTS of `segb` blocks (all of one size but for rounding: no short one at the end): a segment's rows into
+//                 LDS (natural order, coalesced; the next segment's rows are on their way meanwhile), then read in block order -- a thread
+//                 takes nr <= NR consecutive runs (a run = one row of one block, s2 codes side by side in LDS), nr such that the segment's
+//                 runs spread evenly over its rounds --, packed as k_encode32 packs: lengths summed, one 32-bit scan and one barrier per
+//                 round, then the codes read from LDS a SECOND time (nothing but two sums lives across the scan: 75 registers), 64-bit
+//                 accumulator, words ORed into an LDS window, the window out in whole 4-byte words; a partial last word stays for the
+//                 next round; the unpredictable values of its zero codes go to their places in the list on the way.
+//                 (Until the rounds were reworked: NR = 4 fixed, segments of 28 + 28 + 28 + 1 blocks at 512^3 -- a fourth round with 36 of
+//                 1024 runs that cost as much as a full one --, 56 registers of table entries across the scan, 173 in all: two wavefronts
+//                 per SIMD, which waited more than half their cycles.  0.371 -> 0.206 ms; profiles/r07_packing_rounds.txt.)
 // No block-ordered copy, no k_permute, no k_unpred, no memset of the stream.
 #pragma once
 
 namespace szh_se {
-constexpr int NR = 4;            // runs per thread and round
+constexpr int NR = 4;            // runs per thread and round: at most (the host picks k_col_encode's `nrmax` <= NR from the geometry)
 constexpr int INNER = 7;         // codes of a run in the fast form (block widths: 6 or 7 for every extent >= 42, and most below)
 constexpr int PF = 8;            // 16-byte pieces of the next segment's rows a thread keeps on their way
 
@@ -76,7 +81,7 @@ inline size_t seg_pieces_per_thread(const szh_geom3 &G, int segb, int VW)
     size_t p2 = 1; while (p2 < nvec) p2 <<= 1;
     return (rows * p2 + 255) / 256;
 }
-inline size_t seg_window_words(const szh_geom3 &G, unsigned maxlen) { return (size_t)256 * NR * (size_t)G.g2.early * maxlen / 32 + 8; }      // (a round: 256 NR runs of at most g2.early codes)
+inline size_t seg_window_words(const szh_geom3 &G, unsigned maxlen, int nrmax = NR) { return (size_t)256 * nrmax * (size_t)G.g2.early * maxlen / 32 + 8; }      // (a round: 256 nrmax runs of at most g2.early codes)
 }
 
 #ifdef SZH_HIPSIM
@@ -277,23 +282,26 @@ __global__ __launch_bounds__(1024) void k_col_zscan(const unsigned *__restrict__
 // dynamic LDS: [(nsym + 1) x u64 table][a segment's rows][16 bytes: a run of the null symbol][window]
 // table entry of symbol s: low word = code length (bit 16 set for symbol 0: the zero codes are counted in the same sum), high word = the code; entry nsym (the null
 // symbol: places of a thread's share that hold no code) = 0
+// A ROUND is 256 threads x nr consecutive runs each; nr <= nrmax (the window is sized for 256 nrmax runs) is chosen per segment and column so that the segment's runs
+// spread evenly over its rounds -- for the usual column one round per segment, every lane busy.  Nothing but the thread's two sums lives across the scan: the packing
+// pass reads the codes and their table entries from LDS a second time (56 registers of table entries carried across the scan held the kernel at two wavefronts per SIMD).
 // WIDE: every block is 6 or 7 codes wide along the contiguous dimension (at least two blocks along it, none wider than 7: every extent >= 42, and most below): a run
-// is read as four 4-byte words from the word boundary at or below it, the thread keeps its codes' table entries in registers between the two passes
+// is read as four 4-byte words from the word boundary at or below it
 // segs: the nseg segments' geometry (the same for every column: worked out once, on the host -- make_seg's divisions were a third of this kernel's scalar work)
 template <class T, bool WIDE>
-__global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t *__restrict__ codes, const u64 *__restrict__ table, unsigned nsym, const szh_se::seg_t *__restrict__ segs, int nseg, int vw,
+__global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t *__restrict__ codes, const u64 *__restrict__ table, unsigned nsym, const szh_se::seg_t *__restrict__ segs, int nseg, int vw, int nrmax,
                                                     size_t tile_bytes, unsigned win_words, const u64 *__restrict__ col_bitoff, const u64 *__restrict__ col_zoff, u64 bit0,
                                                     unsigned *out32, const T *__restrict__ data, T *__restrict__ unpred)
 {
     using namespace szh_se;
     SZH_DYN_SMEM(smem);
-    __shared__ u64 sh[8];
-    __shared__ unsigned rowbase[128];                                // element offset of every row of the column (rows <= 121; the array: < 2^32 elements)
+    __shared__ u64 sh[2][4];                                         // the wavefronts' sums of a round (rounds alternate between the two sets: one barrier per scan)
+    __shared__ unsigned rowbase[128];                                // element offset of every row of the column (rows <= 121; the array: < 2^32 elements -- the host checks)
     u64 *ltab = reinterpret_cast<u64 *>(smem);
     uint16_t *tile = reinterpret_cast<uint16_t *>(smem + ((size_t)nsym + 1) * 8);
     uint16_t *nullrun = reinterpret_cast<uint16_t *>(smem + ((size_t)nsym + 1) * 8 + tile_bytes);
     unsigned *win = reinterpret_cast<unsigned *>(smem + ((size_t)nsym + 1) * 8 + tile_bytes + 16);
-    const int tid = (int)threadIdx.x;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const col_t c = make_col(G, (int)blockIdx.x);
     for (unsigned i = tid; i < nsym; i += 256) ltab[i] = table[i];
     if (tid == 0) ltab[nsym] = 0;
@@ -345,52 +353,59 @@ __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t 
     seg_t s = segs[0]; s.nruns = s.nblk * c.rows;
     fetch(s);
     const u64 col_bit = bit0 + col_bitoff[blockIdx.x];
+    const u64 col_word = col_bit >> 5;                               // the column's first word: shared with the column before when the column begins inside it
+    const bool col_lead = (col_bit & 31u) != 0u;
     u64 bits_done = 0, zeros_done = col_zoff[blockIdx.x];
     const int null_at = (int)(nullrun - tile);
+    int par = 0;
     for (int segi = 0; segi < nseg; ++segi) {
         // (the last segment's readers of the tile are behind a barrier of its last round: the one in front of the window's way out, or the one that stands in for it)
         place(s);
         __syncthreads();
         seg_t sn = s;
         if (segi + 1 < nseg) { sn = segs[segi + 1]; sn.nruns = sn.nblk * c.rows; fetch(sn); }
-        const int nrounds = (s.nruns + 256 * NR - 1) / (256 * NR);
+        // rounds of the segment: as few as the window allows, the runs spread evenly over them
+        const int nrounds = (s.nruns + 256 * nrmax - 1) / (256 * nrmax);
+        const int nr = (s.nruns + 256 * nrounds - 1) / (256 * nrounds);
         const int edge_k = s.nE * s.E;
-        for (int rd = 0; rd < nrounds; ++rd) {
-            const int q0 = (rd * 256 + tid) * NR;
+        // the four words from the word boundary at or below code `at` of the tile, shifted so that the run's first code is the low half of the first
+        auto run_words = [&](int at, unsigned (&wv)[4]) {
+            const unsigned *w = reinterpret_cast<const unsigned *>(tile + (at & ~1));
+            const unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];             // (a run at the end of the last row reads into the null run and the window's first words)
+            const unsigned sft = (unsigned)(at & 1) << 4;
+            wv[0] = (unsigned)((((u64)w1 << 32) | w0) >> sft); wv[1] = (unsigned)((((u64)w2 << 32) | w1) >> sft);
+            wv[2] = (unsigned)((((u64)w3 << 32) | w2) >> sft); wv[3] = w3 >> sft;
+        };
+        for (int rd = 0; rd < nrounds; ++rd, par ^= 1) {
+            const int q0 = (rd * 256 + tid) * nr;
             // where the thread's first run lies: block `bl` of the segment, row `row` of it
             const int bl0 = (int)div_by((unsigned)q0, (unsigned)c.rows, m_rows), row0 = q0 - bl0 * c.rows;
             // pass 1: the lengths of the thread's codes (low half of `sum1`), its zero codes (high half)
             unsigned sum1 = 0;
-            unsigned elen[WIDE ? NR * INNER : 1], ecode[WIDE ? NR * INNER : 1];
-            bool need7[NR];                                             // (wavefront-uniform) some lane's j-th run is INNER codes wide
+            int jn = 0;                                                 // (wavefront-uniform) runs up to the last one some lane has
+            unsigned need7 = 0;                                         // (wavefront-uniform) bit j: some lane's j-th run is INNER codes wide
             if (WIDE) {
                 int bl = bl0, row = row0;
-#pragma unroll
-                for (int j = 0; j < NR; ++j) {
+                for (int j = 0; j < nr; ++j) {
                     const bool on = q0 + j < s.nruns;
+                    if (!any_lane(on)) break;                            // (every lane comes by here; a thread's runs follow each other: nobody has a later one either)
+                    jn = j + 1;
                     const int s2 = bl < s.nE ? s.E : s.L, koff = bl < s.nE ? bl * s.E : edge_k + (bl - s.nE) * s.L;
-                    const int at = on ? row * s.pitch + s.kshift + koff : null_at;
-                    const unsigned *w = reinterpret_cast<const unsigned *>(tile + (at & ~1));
-                    unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];          // (a run at the end of the last row reads into the null run and the window's first words)
-                    if (at & 1) { w0 = (w0 >> 16) | (w1 << 16); w1 = (w1 >> 16) | (w2 << 16); w2 = (w2 >> 16) | (w3 << 16); w3 >>= 16; }
-                    const unsigned wv[4] = {w0, w1, w2, w3};
+                    unsigned wv[4];
+                    run_words(on ? row * s.pitch + s.kshift + koff : null_at, wv);
+                    const bool n7 = any_lane(on && s2 == INNER);         // (blocks are INNER - 1 or INNER wide here: most runs have no seventh code)
+                    if (n7) need7 |= 1u << j;
 #pragma unroll
                     for (int kk = 0; kk < INNER; ++kk) {
                         unsigned cd = (kk & 1) ? wv[kk >> 1] >> 16 : wv[kk >> 1] & 0xffffu;
-                        if (kk == INNER - 1) {                                         // (blocks are INNER - 1 or INNER wide here: most runs have no such code)
-                            cd = (on && s2 == INNER) ? cd : nsym;
-                            need7[j] = any_lane(on && s2 == INNER);                  // (every lane comes by here)
-                            if (!need7[j]) { elen[j * INNER + kk] = 0u; ecode[j * INNER + kk] = 0u; continue; }
-                        }
-                        const u64 en = ltab[cd];
-                        elen[j * INNER + kk] = (unsigned)en; ecode[j * INNER + kk] = (unsigned)(en >> 32);
-                        sum1 += (unsigned)en;
+                        if (kk == INNER - 1) { if (!n7) continue; cd = (on && s2 == INNER) ? cd : nsym; }
+                        sum1 += (unsigned)ltab[cd];
                     }
                     if (++row == c.rows) { row = 0; ++bl; }
                 }
             } else {
                 int bl = bl0, row = row0;
-                for (int j = 0; j < NR; ++j) {
+                for (int j = 0; j < nr; ++j) {
                     if (q0 + j >= s.nruns) break;
                     const int s2 = bl < s.nE ? s.E : s.L, koff = bl < s.nE ? bl * s.E : edge_k + (bl - s.nE) * s.L;
                     const uint16_t *p = tile + row * s.pitch + s.kshift + koff;
@@ -399,13 +414,22 @@ __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t 
                 }
             }
             const unsigned bsum = sum1 & 0xffffu, zsum = sum1 >> 16;
-            u64 tot2;
-            const u64 ex2 = block_excl_scan_256((u64)bsum | ((u64)zsum << 32), sh, &tot2);     // (its barriers also separate the last round's reads of the window from this round's writes)
-            const unsigned tot = (unsigned)tot2, ex = (unsigned)ex2;
+            // the round's scan: bit counts as 32-bit values (a round: at most 256 * 4 runs of 11 codes of 32 bits); the zero codes take the same steps only in a
+            // wavefront that has some.  One barrier: it also separates the last round's reads of the window from this round's writes
+            unsigned ib = bsum, iz = zsum;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(ib, o, 64); if (lane >= o) ib += t; }
+            if (any_lane(zsum != 0u)) for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(iz, o, 64); if (lane >= o) iz += t; }
+            if (lane == 63) sh[par][wid] = (u64)ib | ((u64)iz << 32);
+            __syncthreads();
+            u64 base2 = 0, tot2 = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) { const u64 t = sh[par][w]; if (w < wid) base2 += t; tot2 += t; }
+            const unsigned tot = (unsigned)tot2, ex = (unsigned)base2 + ib - bsum;
             const u64 gbit = col_bit + bits_done;
             const unsigned lead = (unsigned)(gbit & 31u);
             const unsigned nwords = (lead + tot + 31u) >> 5;           // words the round touches (word 0 holds `lead` bits of what came before: the last round's partial word stayed there)
-            if (bsum) {
+            {
+                // pass 2: the codes once more, their bits into the window
                 const unsigned bitpos = lead + ex;
                 unsigned wpos = bitpos >> 5, nb = bitpos & 31u;
                 u64 acc = 0;
@@ -416,14 +440,27 @@ __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t 
                     if (nb >= 32u) { atomicOr(&win[wpos], (unsigned)(acc >> (nb - 32u))); ++wpos; nb -= 32u; }
                 };
                 if (WIDE) {
-#pragma unroll
-                    for (int e = 0; e < NR * INNER; ++e) {
-                        if (e % INNER == INNER - 1 && !need7[e / INNER]) continue;      // (nobody's run is that wide)
-                        put(elen[e], ecode[e]);
-                    }
-                } else {
+                    // (every lane of a wavefront with bits walks the same runs: a lane without a run reads the null run, whose codes have no bits)
                     int bl = bl0, row = row0;
-                    for (int j = 0; j < NR; ++j) {
+                    if (any_lane(bsum != 0u))
+                    for (int j = 0; j < jn; ++j) {
+                        const bool on = q0 + j < s.nruns;
+                        const int s2 = bl < s.nE ? s.E : s.L, koff = bl < s.nE ? bl * s.E : edge_k + (bl - s.nE) * s.L;
+                        unsigned wv[4];
+                        run_words(on ? row * s.pitch + s.kshift + koff : null_at, wv);
+                        const bool n7 = (need7 >> j) & 1u;
+#pragma unroll
+                        for (int kk = 0; kk < INNER; ++kk) {
+                            unsigned cd = (kk & 1) ? wv[kk >> 1] >> 16 : wv[kk >> 1] & 0xffffu;
+                            if (kk == INNER - 1) { if (!n7) continue; cd = (on && s2 == INNER) ? cd : nsym; }
+                            const u64 en = ltab[cd];
+                            put((unsigned)en, (unsigned)(en >> 32));
+                        }
+                        if (++row == c.rows) { row = 0; ++bl; }
+                    }
+                } else if (bsum) {
+                    int bl = bl0, row = row0;
+                    for (int j = 0; j < nr; ++j) {
                         if (q0 + j >= s.nruns) break;
                         const int s2 = bl < s.nE ? s.E : s.L, koff = bl < s.nE ? bl * s.E : edge_k + (bl - s.nE) * s.L;
                         const uint16_t *p = tile + row * s.pitch + s.kshift + koff;
@@ -431,13 +468,13 @@ __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t 
                         if (++row == c.rows) { row = 0; ++bl; }
                     }
                 }
-                if (nb) atomicOr(&win[wpos], (unsigned)(acc << (32u - nb)));   // the last, partial word
+                if (bsum && nb) atomicOr(&win[wpos], (unsigned)(acc << (32u - nb)));   // the last, partial word
             }
             if (zsum) {
                 // the unpredictable values of the thread's zero codes: the originals, at their places in the list (sz_float.c:7288) -- few threads get here
-                u64 zat = zeros_done + (ex2 >> 32);
+                u64 zat = zeros_done + (unsigned)(base2 >> 32) + iz - zsum;
                 int bl = bl0, row = row0;
-                for (int j = 0; j < NR; ++j) {
+                for (int j = 0; j < nr; ++j) {
                     if (q0 + j >= s.nruns) break;
                     const int s2 = bl < s.nE ? s.E : s.L, koff = bl < s.nE ? bl * s.E : edge_k + (bl - s.nE) * s.L;
                     const uint16_t *p = tile + row * s.pitch + s.kshift + koff;
@@ -460,7 +497,8 @@ __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t 
                 for (unsigned w = tid; w < nout; w += 256) {
                     const unsigned x = __builtin_bswap32(win[w]);
                     win[w] = w == 0 ? keep : 0u;                           // (the window is clear again behind the words that left; the kept word is the next round's first)
-                    const bool shared = (w == 0 && bits_done == 0 && lead != 0u) || (w == nwords - 1 && last_round && partial);
+                    // (shared or not is a matter of WHERE the word lies, not of how far the column has come: a first round may end inside the leading word)
+                    const bool shared = (col_lead && w0 + w == col_word) || (w == nwords - 1 && last_round && partial);
                     if (shared) { if (x) atomicOr(&out32[w0 + w], x); }
                     else out32[w0 + w] = x;
                 }

@@ -386,26 +386,34 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     const int segenc_sw = tune_int("SZ_HIP_SEGENC", 1);
     bool segenc = !two_d && G.ndim == 3 && segenc_sw != 0 && (!feed || segenc_sw == 2);
     // segments of `se_segb` blocks of a block column: their rows, the code table and the bit window (sized here for the longest code words the kernel takes, 32 bits)
-    // share the workgroup's LDS
+    // share the workgroup's LDS.  A tile of 14 KB: k_col_encode needs 75 registers (six wavefronts per SIMD), so the LDS a workgroup takes decides how many columns a CU
+    // works on at once -- 512^3, segments of 29 / 22 / 17 / 15 / 11 blocks: 0.251 / 0.220 / 0.206 / 0.224 / 0.253 ms (profiles/r07_packing_rounds.txt)
     const int se_vw = (G.g2.count % 8) == 0 ? 8 : ((G.g2.count % 4) == 0 ? 4 : 1);
-    int se_segb = 0, se_nseg = 0; size_t se_tile = 0;
+    int se_segb = 0, se_nseg = 0, se_nrmax = szh_se::NR; size_t se_tile = 0;
     if (segenc) {
-        bool ok = intervals < 65536;
+        bool ok = intervals < 65536 && (double)n < 4.0e9;            // (k_col_encode keeps a row's element offset in 32 bits)
+        // every block holds at least 32 codes, so a column's first round (all runs of its first segment, or 256 threads' worth) holds at least 32 code words and
+        // never ends inside the column's leading partial word; k_col_encode tells a word shared with the column before by its position all the same.  (3-D arrays of a
+        // 2 x 2 cross-section are the only ones this sends to the older passes: a dimension of 1 never comes here.)
+        if ((int64_t)G.g0.late * G.g1.late * G.g2.late < 32) ok = false;
         const size_t fixed = ((size_t)intervals + 1) * 8 + 16 + szh_se::seg_window_words(G, 32) * 4 + 64;
-        const size_t lds_cap = (size_t)63 * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 24)) * 1024;
+        const size_t lds_cap = (size_t)63 * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 14)) * 1024;
         if (ok && fixed + szh_se::seg_tile_bytes(G, 1, se_vw) > lds_cap) ok = false;
         if (ok) {
             const size_t budget = std::min(lds_cap - fixed, std::max(want, szh_se::seg_tile_bytes(G, 1, se_vw)));
             int sb = 1;
             while (sb < G.g2.num && szh_se::seg_tile_bytes(G, sb + 1, se_vw) <= budget && szh_se::seg_pieces_per_thread(G, sb + 1, se_vw) <= (size_t)szh_se::PF) ++sb;
-            // a round of k_col_encode is 256 threads x NR runs: segments of just under a whole number of rounds of the usual block column's runs (the last one takes the rest)
-            const int rows_typ = (2 * G.g0.split > G.g0.num ? G.g0.early : G.g0.late) * (2 * G.g1.split > G.g1.num ? G.g1.early : G.g1.late);
-            const int per_round = std::max(1, 256 * szh_se::NR / std::max(1, rows_typ));
-            if (sb >= per_round) sb = sb / per_round * per_round;
+            // segments of equal size, as few as the tile allows: no short segment at the end that pays a whole round's barriers, scan and tile load for a handful of runs
+            sb = (G.g2.num + (G.g2.num + sb - 1) / sb - 1) / ((G.g2.num + sb - 1) / sb);
             if (const int f = tune_int("SZ_HIP_SEG_SEGB", 0)) sb = std::max(1, std::min(f, sb));
             se_segb = sb;
             se_nseg = (G.g2.num + se_segb - 1) / se_segb;
             se_tile = szh_se::seg_tile_bytes(G, se_segb, se_vw);
+            // a round of k_col_encode is 256 threads x up to `se_nrmax` runs (the window is sized for that many): the usual block column's segment in as few rounds as
+            // NR allows, its runs spread evenly over them; a column of more rows takes more rounds
+            const int rows_typ = (2 * G.g0.split > G.g0.num ? G.g0.early : G.g0.late) * (2 * G.g1.split > G.g1.num ? G.g1.early : G.g1.late);
+            const int runs_typ = std::max(1, sb * rows_typ), rounds_typ = (runs_typ + 256 * szh_se::NR - 1) / (256 * szh_se::NR);
+            se_nrmax = std::max(1, std::min(szh_se::NR, (runs_typ + 256 * rounds_typ - 1) / (256 * rounds_typ)));
             if ((double)G.g0.num * G.g1.num >= 2.0e9) ok = false;
         }
         segenc = ok;
@@ -761,7 +769,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         TRY(permute_all());
     }
     if (segenc) {
-        se_lds = ((size_t)intervals + 1) * 8 + se_tile + 16 + szh_se::seg_window_words(G, std::max(1u, enc_maxlen)) * 4;
+        se_lds = ((size_t)intervals + 1) * 8 + se_tile + 16 + szh_se::seg_window_words(G, std::max(1u, enc_maxlen), se_nrmax) * 4;
         // the segments' geometry, the same for every column (k_col_encode reads it instead of working it out)
         se_segs.resize((size_t)se_nseg);
         for (int q = 0; q < se_nseg; ++q) se_segs[(size_t)q] = szh_se::make_seg(G, 1, q, se_segb, se_vw);
@@ -814,12 +822,12 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     }
     if (segenc) {
         TRY(ensure(ctx, ctx->unpred, unpred_bytes + 64));
-        const unsigned se_win = (unsigned)szh_se::seg_window_words(G, std::max(1u, enc_maxlen));
+        const unsigned se_win = (unsigned)szh_se::seg_window_words(G, std::max(1u, enc_maxlen), se_nrmax);
         if (G.g2.num >= 2 && G.g2.early <= szh_se::INNER && G.g2.late >= szh_se::INNER - 1)
-            hipLaunchKernelGGL((k_col_encode<T, true>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_tile, se_win,
+            hipLaunchKernelGGL((k_col_encode<T, true>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
                                (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p);
         else
-            hipLaunchKernelGGL((k_col_encode<T, false>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_tile, se_win,
+            hipLaunchKernelGGL((k_col_encode<T, false>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
                                (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p);
         HIPCHK(hipGetLastError());
         if (total_unpred > 0) HIPCHK(hipMemcpyAsync(d_stream + hdr_len, ctx->unpred.p, unpred_bytes, hipMemcpyDeviceToDevice, st));
