@@ -68,6 +68,7 @@ typedef struct szhip_stats {
     int chain_overlapped;   /* 1: the regression-coefficient chain ran next to the wavefront kernel */
     int quant_kernel;       /* which mapping of the wavefront kernel ran: 0 = k_pencil (8x8 pencils), 2 = k_beam (szh_beam.h) */
     int packing;            /* (round 6) 1: the Huffman packing read the sweep's natural-order codes segment by segment (szh_segenc.h); 0: block-ordered copy first */
+    int book_on_device;     /* 1: the Huffman code book of this stream was built on the device (SZ_HIP_DEV_BOOK=1, szh_book.h); 0: on the host */
 } szhip_stats;
 
 int  szhip_create(szhip_ctx **ctx, int device);
@@ -219,6 +220,27 @@ int szhip_sz14_pwr_locate(int dtype, const unsigned char *stream, size_t stream_
 int szhip_decompress_sz14_pwr(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len,
                               size_t body_off, size_t r0, size_t r1, size_t r2, const unsigned char *signs_host, void *out,
                               int out_on_device, szhip_stats *stats);
+
+/*
+ * The Huffman code book of a code histogram, built on the device (k_huff_book, sz_amd/csrc/szh_book.h) -- what the reference's constructor and tree
+ * serialiser do on the host (Huffman.c:76-185 build, :122-157 code words, :443-585 convert_HuffTree_to_bytes), bit for bit: same heap order among equal counts,
+ * same node numbering, same node-index width.  szhip_compress uses the kernel when SZ_HIP_DEV_BOOK=1 is set; this entry runs it alone.
+ * `hist`: `intervals` counts (1 .. 65536), a device or a host pointer.  Host outputs: `out_tree` (capacity out_tree_cap; record->tree_bytes are valid),
+ * `out_code64` / `out_len8`: `intervals` right-aligned code words and their lengths (0 for a symbol that does not occur).
+ * record->status != 0: the kernel declined and wrote nothing -- the three arrays then come back filled with the byte 0xA5 the entry put into the device
+ * buffers before the launch.  1: more distinct symbols than the kernel's heap holds (1024); 2: a code word beyond 32 bits; 3: an empty histogram;
+ * 4: out_tree_cap too small.  The return value is SZHIP_OK whenever the kernel ran.
+ */
+typedef struct szhip_book_record {
+    uint32_t n_nodes;       /* nodes of the tree: 2 * distinct symbols - 1 */
+    uint32_t tree_bytes;    /* serialised size */
+    uint32_t max_len;       /* longest code word, bits */
+    uint32_t status;
+    uint64_t total_bits;    /* sum of count x code length */
+    uint64_t total_unpred;  /* hist[0] */
+} szhip_book_record;
+int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsigned char *out_tree, size_t out_tree_cap,
+                    uint64_t *out_code64, uint8_t *out_len8, szhip_book_record *record);
 
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)

@@ -47,10 +47,16 @@ class szhip_stats(ctypes.Structure):  # include/szhip.h
                 ("ms_entropy", ctypes.c_double), ("ms_host", ctypes.c_double),
                 ("n_elements", ctypes.c_uint64), ("n_blocks", ctypes.c_uint64), ("n_reg_blocks", ctypes.c_uint64),
                 ("n_unpred", ctypes.c_uint64), ("intervals", ctypes.c_uint), ("use_mean", ctypes.c_int),
-                ("out_bytes", ctypes.c_uint64), ("quant_kernel_launches", ctypes.c_uint64), ("vmin", ctypes.c_double), ("vmax", ctypes.c_double), ("chain_overlapped", ctypes.c_int), ("quant_kernel", ctypes.c_int), ("packing", ctypes.c_int)]
+                ("out_bytes", ctypes.c_uint64), ("quant_kernel_launches", ctypes.c_uint64), ("vmin", ctypes.c_double), ("vmax", ctypes.c_double), ("chain_overlapped", ctypes.c_int), ("quant_kernel", ctypes.c_int), ("packing", ctypes.c_int),
+                ("book_on_device", ctypes.c_int)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class szhip_book_record(ctypes.Structure):  # include/szhip.h
+    _fields_ = [("n_nodes", ctypes.c_uint32), ("tree_bytes", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("status", ctypes.c_uint32),
+                ("total_bits", ctypes.c_uint64), ("total_unpred", ctypes.c_uint64)]
 
 
 class szhost_meta(ctypes.Structure):  # sz_amd/csrc/szhost.h
@@ -138,6 +144,10 @@ def _bind(L):
         L.szhip_decompress_omp.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
                                            ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_stats)]
         L.szhip_decompress_omp.restype = ctypes.c_int
+    if hasattr(L, "szhip_huff_book"):
+        L.szhip_huff_book.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.POINTER(szhip_book_record)]
+        L.szhip_huff_book.restype = ctypes.c_int
     L.szhost_write_meta.argtypes = [ctypes.POINTER(szhost_meta), ctypes.c_ubyte, ctypes.c_char_p]
     L.szhost_write_meta.restype = sz
     L.free.argtypes = [ctypes.c_void_p]
@@ -237,6 +247,20 @@ def make_meta(dtype, err_mode=ABS, abs_bound=0.0, rel_ratio=0.0, vmin=0.0, vmax=
     flags = 0x80 | 0x40 | (0x04 if protect_value_range else 0)
     n = lib().szhost_write_meta(ctypes.byref(m), flags, buf)
     return buf.raw[:n]
+
+
+BOOK_CAP = 1024                      # distinct symbols k_huff_book's heap holds (SZH_BOOK_CAP, sz_amd/csrc/szh_book.h)
+
+
+def szhip_huff_book_tree_cap():
+    """Bytes of the largest tree szhip_huff_book serialises (two-byte node indices)."""
+    return 1 + 9 * (2 * BOOK_CAP - 1)
+
+
+def parse_book_record(raw):
+    """The 32 bytes of a szhip_book_record as a dict (the layout the library copies from the device)."""
+    rec = szhip_book_record.from_buffer_copy(bytes(raw)[:ctypes.sizeof(szhip_book_record)])
+    return {k: getattr(rec, k) for k, _ in rec._fields_}
 
 
 class HipPool:
@@ -360,6 +384,22 @@ class HipContext:
         if rc:
             self._err(rc, "szhip_decompress_omp")
         return st
+
+    def huff_book(self, hist, on_device=False, intervals=None, tree_cap=None):
+        """The device's code book of a histogram (szhip_huff_book; k_huff_book alone).  hist: a numpy uint32 array, or a device pointer with `intervals`.
+        Returns (record, tree bytes, code words uint64[intervals], lengths uint8[intervals]); the arrays hold the fill byte 0xA5 when record.status != 0."""
+        if on_device:
+            ptr, k = hist, int(intervals)
+        else:
+            h = np.ascontiguousarray(hist, dtype=np.uint32)
+            ptr, k = h.ctypes.data, h.size
+        cap = szhip_huff_book_tree_cap() if tree_cap is None else tree_cap
+        tree = np.zeros(max(cap, 1), dtype=np.uint8); code = np.zeros(k, dtype=np.uint64); ln = np.zeros(k, dtype=np.uint8)
+        rec = szhip_book_record()
+        rc = lib().szhip_huff_book(self._h, ptr, k, tree.ctypes.data, cap, code.ctypes.data, ln.ctypes.data, ctypes.byref(rec))
+        if rc:
+            self._err(rc, "szhip_huff_book")
+        return rec, (tree[:rec.tree_bytes].tobytes() if rec.status == 0 else tree.tobytes()), code, ln
 
     def debug_fetch(self, which, count, dtype):
         """Copy an internal workspace of the last call to host (tests only; see szhip_debug_fetch)."""

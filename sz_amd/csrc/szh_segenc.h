@@ -231,9 +231,10 @@ __global__ __launch_bounds__(256) void k_col_bounds(const u64 *__restrict__ col_
 // both scans and the boundary words in ONE launch of one workgroup (up to 2^13 columns, eight per thread in registers -- sixteen spilled under the 1024-thread register bound --: six launches of the general scan less)
 #define SZH_COL_SCAN_PER 8
 __global__ __launch_bounds__(1024) void k_col_scan(const u64 *__restrict__ col_bits, const u64 *__restrict__ col_zeros, int nent, u64 *__restrict__ col_bitoff, u64 *__restrict__ col_zoff,
-                                                   u64 *total_bits, u64 *total_zeros, u64 bit0, unsigned *out32)
+                                                   u64 *total_bits, u64 *total_zeros, u64 bit0, unsigned *out32, const u64 *__restrict__ plan = nullptr)
 {
     __shared__ u64 shb[16], shz[16];
+    if (plan) { if (plan[SZH_PLAN_STATUS] != 0) return; bit0 = plan[SZH_PLAN_BIT0]; }      // (szh_book.h: the payload's start is the device's; a declined book: nothing to do)
     const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int lo = tid * SZH_COL_SCAN_PER;
     u64 vb[SZH_COL_SCAN_PER], vz[SZH_COL_SCAN_PER];
@@ -291,9 +292,10 @@ __global__ __launch_bounds__(1024) void k_col_zscan(const unsigned *__restrict__
 template <class T, bool WIDE>
 __global__ __launch_bounds__(256) void k_col_encode(szh_geom3 G, const uint16_t *__restrict__ codes, const u64 *__restrict__ table, unsigned nsym, const szh_se::seg_t *__restrict__ segs, int nseg, int vw, int nrmax,
                                                     size_t tile_bytes, unsigned win_words, const u64 *__restrict__ col_bitoff, const u64 *__restrict__ col_zoff, u64 bit0,
-                                                    unsigned *out32, const T *__restrict__ data, T *__restrict__ unpred)
+                                                    unsigned *out32, const T *__restrict__ data, T *__restrict__ unpred, const u64 *__restrict__ plan = nullptr)
 {
     using namespace szh_se;
+    if (plan) { if (plan[SZH_PLAN_STATUS] != 0) return; bit0 = plan[SZH_PLAN_BIT0]; }      // (szh_book.h, as in k_col_scan)
     SZH_DYN_SMEM(smem);
     __shared__ u64 sh[2][4];                                         // the wavefronts' sums of a round (rounds alternate between the two sets: one barrier per scan)
     __shared__ unsigned rowbase[128];                                // element offset of every row of the column (rows <= 121; the array: < 2^32 elements -- the host checks)

@@ -145,7 +145,7 @@ struct szhip_ctx {
     // workspaces (grow-only)
     DevBuf lor_bits, reg_flags, reg_rank, coef_compact, in, out, codes_nat, codes_blk, coef, blk_lor, faceI, faceJ, rb_down, rb_right, rb_vals, pt_flags, feed_word, progress, order, small, hist, col_zeros, col_zeros64,
         seg_bits, seg_zeros, seg_bitoff, seg_zoff, seg_hist, seg_tab, col_off, partial, samples, unpred, stream_buf, chunk_bits, chunk_off, code_tab, len_tab, dec_tab,
-        starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe;
+        starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe, book_tree, book_rec, book_stage;
     void *pinned = nullptr; size_t pinned_cap = 0;
     void *pinned2 = nullptr; size_t pinned2_cap = 0;   // target of the second stream's copies (indicator bits, regression-block count)
     // bulk copies between the caller's pageable arrays and the device: SZH_STAGE_T host threads, two pinned buffers + events each
@@ -162,6 +162,10 @@ struct szhip_ctx {
     // the coefficient chain beside the running sweep (M-field): a sweep that gave up waiting for the coefficients (seen 5 - 6 times in 480 rounds with
     // several arrays in flight) is answered by ONE repetition with the chain finished before the sweep starts; the context keeps that order
     bool coef_late = false, no_chain_overlap = false;
+    // the code book built on the device (SZ_HIP_DEV_BOOK=1, szh_book.h): a call whose book the kernel declined (more distinct symbols than its heap holds, a code
+    // word beyond 32 bits, a stream that outgrows the buffers sized before the call) is repeated once with the host's book
+    bool book_declined = false, no_dev_book = false;
+    unsigned long long *book_pin = nullptr;      // pinned: the book's record and the plan behind it, copied asynchronously, read after the call's final synchronisation
     std::vector<int> chain_codes; std::vector<unsigned char> chain_unpred;   // the chains' outputs, kept across calls (fresh memory page-faults under the chain: ~1 ms for the M-field's 10 MB)
     unsigned char *sec_pin[4] = {nullptr, nullptr, nullptr, nullptr}; size_t sec_pin_cap[4] = {0, 0, 0, 0};   // the coefficient sections of the stream header as the chain threads build them: pinned, they go to the device from where they are
     szhip_chain_pool *chain_pool = nullptr;      // the coefficient chains' persistent threads (created with the first array that has regression blocks)
@@ -183,8 +187,14 @@ namespace {
 template <class F>
 static int with_ticket_fallback(szhip_ctx *ctx, F &&run)
 {
-    ctx->wave_timeout = false; ctx->hdec_unconverged = false; ctx->coef_late = false;
+    ctx->wave_timeout = false; ctx->hdec_unconverged = false; ctx->coef_late = false; ctx->book_declined = false;
     int rc = run();
+    if (rc == SZHIP_ERR_INTERNAL && ctx->book_declined && !ctx->no_dev_book) {            // (compression with SZ_HIP_DEV_BOOK=1 only)
+        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
+        ctx->no_dev_book = true; ctx->wave_timeout = false;
+        rc = run();
+        ctx->no_dev_book = false;
+    }
     if (rc == SZHIP_OK && !ctx->no_chain_overlap && tune_int("SZ_HIP_TEST_CHAIN_FALLBACK", 0)) { ctx->coef_late = true; rc = SZHIP_ERR_INTERNAL; }   // tests: exercise the repetition
     if (rc == SZHIP_ERR_INTERNAL && ctx->coef_late && !ctx->no_chain_overlap) {           // (compression of arrays with regression blocks only)
         if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
@@ -255,13 +265,14 @@ void szhip_destroy(szhip_ctx *ctx)
                       &ctx->order, &ctx->small, &ctx->hist, &ctx->col_zeros, &ctx->col_zeros64, &ctx->seg_bits, &ctx->seg_zeros, &ctx->seg_bitoff, &ctx->seg_zoff, &ctx->seg_hist, &ctx->seg_tab, &ctx->col_off, &ctx->partial,
                       &ctx->samples, &ctx->unpred, &ctx->stream_buf, &ctx->chunk_bits, &ctx->chunk_off, &ctx->code_tab,
                       &ctx->len_tab, &ctx->dec_tab, &ctx->starts, &ctx->ends, &ctx->counts, &ctx->offs, &ctx->dirty, &ctx->zcnt, &ctx->zpos,
-                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe};
+                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe, &ctx->book_tree, &ctx->book_rec, &ctx->book_stage};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->pinned2) hipHostFree(ctx->pinned2);
     if (ctx->pinned3) hipHostFree(ctx->pinned3);
     if (ctx->coh) hipHostFree(ctx->coh);
     if (ctx->hdec_res) hipHostFree(ctx->hdec_res);
+    if (ctx->book_pin) hipHostFree(ctx->book_pin);
     for (int w = 0; w < SZH_STAGE_T; ++w) for (int k = 0; k < 2; ++k) { if (ctx->stage_buf[w][k]) hipHostFree(ctx->stage_buf[w][k]); if (ctx->stage_ev[w][k]) hipEventDestroy(ctx->stage_ev[w][k]); }
     for (int i = 0; i < 6; ++i) if (ctx->ev[i]) hipEventDestroy(ctx->ev[i]);
     if (ctx->ev_in) hipEventDestroy(ctx->ev_in);
@@ -549,6 +560,40 @@ int szhip_decompress(szhip_ctx *ctx, int dtype, const unsigned char *stream, int
     return with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
                ? decompress_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats)
                : decompress_impl<double>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats); });
+}
+
+int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsigned char *out_tree, size_t out_tree_cap,
+                    uint64_t *out_code64, uint8_t *out_len8, szhip_book_record *record)
+{
+    if (!ctx || !hist || !out_tree || !out_code64 || !out_len8 || !record || intervals == 0 || intervals > 65536) return SZHIP_ERR_ARG;
+    static_assert(sizeof(szhip_book_record) == sizeof(szh_book_rec), "the public record mirrors the kernel's");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    bool on_device = false;
+#ifndef SZH_SYNC_LAUNCH
+    { hipPointerAttribute_t pa; if (hipPointerGetAttributes(&pa, hist) == hipSuccess) on_device = pa.type == hipMemoryTypeDevice; else (void)hipGetLastError(); }
+#endif
+    const size_t tree_cap = std::min<size_t>(std::max<size_t>(out_tree_cap, 1), 1 + (size_t)9 * (2 * SZH_BOOK_CAP - 1));
+    TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8)); TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
+    TRY(ensure(ctx, ctx->book_tree, tree_cap)); TRY(ensure(ctx, ctx->book_rec, 32 + SZH_PLAN_COUNT * 8));
+    const unsigned *d_hist = (const unsigned *)hist;
+    if (!on_device) {
+        TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
+        HIPCHK(hipMemcpyAsync(ctx->hist.p, hist, (size_t)intervals * 4, hipMemcpyHostToDevice, st));
+        d_hist = (const unsigned *)ctx->hist.p;
+    }
+    HIPCHK(hipMemsetAsync(ctx->code_tab.p, 0xA5, (size_t)intervals * 8, st));
+    HIPCHK(hipMemsetAsync(ctx->len_tab.p, 0xA5, (size_t)intervals, st));
+    HIPCHK(hipMemsetAsync(ctx->book_tree.p, 0xA5, tree_cap, st));
+    hipLaunchKernelGGL(k_huff_book, dim3(1), dim3(256), 0, st, d_hist, intervals, SZH_BOOK_TAB_RAW, (unsigned char *)ctx->book_tree.p, (unsigned)std::min<size_t>(out_tree_cap, tree_cap),
+                       (u64 *)ctx->code_tab.p, (uint8_t *)ctx->len_tab.p, (szh_book_rec *)ctx->book_rec.p, (u64 *)nullptr, (u64)0, 0u, (u64)0, (u64)0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_code64, ctx->code_tab.p, (size_t)intervals * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_len8, ctx->len_tab.p, (size_t)intervals, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_tree, ctx->book_tree.p, std::min<size_t>(out_tree_cap, tree_cap), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(record, ctx->book_rec.p, sizeof(*record), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SZHIP_OK;
 }
 
 int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes)

@@ -1700,5 +1700,6 @@ __global__ void k_probe_touch(unsigned long long *p) { *p = 1; }
 #include "szh_omp.h"
 #include "szh_ompcol.h"
 #include "szh_beam.h"
+#include "szh_book.h"
 #include "szh_segenc.h"
 #include "szh_fittile.h"

@@ -1,4 +1,8 @@
 // szhip_sz21.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace): the SZ 2.1 path (sz_float.c:7126-7560 / szd_float.c:3491-5860 and the double twins): compress_impl, the device Huffman decode, parse_header, decompress_impl.
+// the device code book's verdict as the host reads it behind the call's final synchronisation (szh_book.h): the kernel's own status, the plan's (the stream
+// outgrew the buffers), or the tests' switch -- any of them sends the call round again with the host's book
+static bool book_declines(unsigned rec_status, unsigned long long plan_status, int test_switch) { return rec_status != 0 || plan_status != 0 || test_switch != 0; }
+
 template <class T>
 int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in,
                   const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device,
@@ -422,6 +426,11 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     int sh_rshift = 0;
     bool seghist = segenc && intervals <= SZH_COL_HBINS && tune_int("SZ_HIP_SEGHIST", 1) != 0;
     if (seghist) { const size_t one = (size_t)intervals * 4; while (sh_rshift < 6 && (one << (sh_rshift + 1)) <= 16 * 1024) ++sh_rshift; }
+    // (SZ_HIP_DEV_BOOK=1, off by default) the code book on the device (szh_book.h): a Lorenzo-only array that takes the packing passes above, their two scans in
+    // one launch -- nothing of its entropy stage waits for the host; a book the kernel declines sends the call round again with the host's (with_ticket_fallback)
+    const size_t bk_front = meta_len + 8 + 4 + sizeof(T), bk_mid = 1 + sizeof(T);
+    const bool dev_book = segenc && reg_count == 0 && !ctx->no_dev_book && tune_int("SZ_HIP_DEV_BOOK", 0) != 0 && ncols <= 1024 * SZH_COL_SCAN_PER &&
+                          tune_int("SZ_HIP_SEG_SCAN1", 1) != 0 && bk_front + bk_mid <= 3072;
     const size_t nat_elems = (size_t)n;
     TRY(ensure(ctx, ctx->codes_nat, nat_elems * 2 + 64));
     TRY(ensure(ctx, ctx->codes_blk, (size_t)n * 2 + 64));
@@ -613,8 +622,10 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         hipLaunchKernelGGL(k_col_hist, dim3((unsigned)ncols), dim3(256), ((size_t)intervals * 4) << sh_rshift, st, G, (const uint16_t *)d_nat, intervals, sh_rshift, se_vw, (unsigned *)ctx->seg_hist.p);
         hipLaunchKernelGGL(k_hist_reduce, dim3((unsigned)std::min<int64_t>(64, ncols)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, intervals, (int64_t)ncols, d_hist);
         HIPCHK(hipGetLastError());
+        if (!dev_book) {
         HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(ctx->ev_fit, st));
+        }
     } else
     if (!sliced) TRY(launch_hist((const uint16_t *)d_nat));    // next to the block-ordering pass (ribbon order: padding skipped by geometry)
     TRY(ensure(ctx, ctx->col_zeros, (size_t)ncols * 4));
@@ -698,6 +709,109 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     return SZHIP_OK;
     };
     if (!sliced && !segenc) TRY(permute_all());
+
+    if (dev_book) {
+        if (!seghist) HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));           // (the histogram of the larger alphabets is the second stream's)
+        if (!ctx->book_pin) HIPCHK(hipHostMalloc((void **)&ctx->book_pin, 4096, hipHostMallocDefault));
+        unsigned char *const blob = (unsigned char *)ctx->book_pin + 256;       // the header's fixed front, then the mean byte and the mean
+        {
+            unsigned char *q = blob;
+            memcpy(q, meta, meta_len); q += meta_len;
+            szhost_put_u64be(q, (uint64_t)n); q += 8;
+            szhost_put_u32be(q, (uint32_t)G.block_size); q += 4;
+            if (is_double) szhost_put_f64be(q, (double)eb); else szhost_put_f32be(q, (float)eb);
+            q += sizeof(T);
+            *q++ = (unsigned char)use_mean;
+            memcpy(q, &mean, sizeof(T));
+        }
+        const size_t plan_fixed = bk_front + 12 + bk_mid + ind_bytes + 8;       // the header without the tree
+        const size_t tree_cap = 1 + (size_t)9 * (2 * SZH_BOOK_CAP - 1);
+        // the buffers are sized before the stream's length is known: room for a stream as large as the array and for a quarter of its values unpredictable (a
+        // stream beyond that is declined on the device)
+        const size_t unpred_cap = std::min((size_t)n * sizeof(T), (size_t)n * sizeof(T) / 4 + 65536);
+        const bool in_place = out_on_device == 2 && *out && *out_size >= plan_fixed + tree_cap + 64 && ((uintptr_t)*out & 15) == 0 && tune_int("SZ_HIP_OUT_IN_PLACE", 1);
+        const size_t stream_cap = in_place ? *out_size : plan_fixed + tree_cap + (size_t)n * sizeof(T) + 65536;
+        if (!in_place) TRY(ensure(ctx, ctx->stream_buf, stream_cap));
+        unsigned char *d_stream = in_place ? (unsigned char *)*out : (unsigned char *)ctx->stream_buf.p;
+        TRY(ensure(ctx, ctx->book_stage, bk_front + bk_mid)); TRY(ensure(ctx, ctx->book_tree, tree_cap)); TRY(ensure(ctx, ctx->book_rec, 32 + SZH_PLAN_COUNT * 8));
+        TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8)); TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
+        TRY(ensure(ctx, ctx->unpred, unpred_cap + 64));
+        const int64_t se_nent = (int64_t)ncols;
+        TRY(ensure(ctx, ctx->seg_bits, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zeros, (size_t)se_nent * 8));
+        TRY(ensure(ctx, ctx->seg_bitoff, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zoff, (size_t)se_nent * 8));
+        szh_book_rec *const d_rec = (szh_book_rec *)ctx->book_rec.p;
+        u64 *const d_plan = (u64 *)((char *)ctx->book_rec.p + 32);
+        HIPCHK(hipMemcpyAsync(ctx->book_stage.p, blob, bk_front + bk_mid, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_huff_book, dim3(1), dim3(256), 0, st, (const unsigned *)d_hist, intervals, SZH_BOOK_TAB_SEG, (unsigned char *)ctx->book_tree.p, (unsigned)tree_cap,
+                           (u64 *)ctx->code_tab.p, (uint8_t *)ctx->len_tab.p, d_rec, d_plan, (u64)plan_fixed, (unsigned)sizeof(T), (u64)stream_cap, (u64)unpred_cap);
+        HIPCHK(hipGetLastError());
+        // the packing passes as below, the window sized for the longest code words they take (32 bits)
+        const unsigned se_win = (unsigned)szh_se::seg_window_words(G, 32u, se_nrmax);
+        const size_t se_lds = ((size_t)intervals + 1) * 8 + se_tile + 16 + (size_t)se_win * 4;
+        std::vector<szh_se::seg_t> se_segs((size_t)se_nseg);                    // (alive until the synchronisation below: it is copied to the device asynchronously)
+        for (int q = 0; q < se_nseg; ++q) se_segs[(size_t)q] = szh_se::make_seg(G, 1, q, se_segb, se_vw);
+        TRY(ensure(ctx, ctx->seg_tab, se_segs.size() * sizeof(szh_se::seg_t)));
+        HIPCHK(hipMemcpyAsync(ctx->seg_tab.p, se_segs.data(), se_segs.size() * sizeof(szh_se::seg_t), hipMemcpyHostToDevice, st));
+        const size_t lb = intervals <= 16384 ? (size_t)intervals : 16;
+        if (seghist) hipLaunchKernelGGL(k_col_bits_h, dim3((unsigned)((se_nent + 255) / 256)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, (const uint8_t *)ctx->len_tab.p, intervals, se_nent, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
+        else
+        hipLaunchKernelGGL(k_col_bits, dim3((unsigned)se_nent), dim3(256), lb, st, G, (const uint16_t *)d_nat, (const uint8_t *)ctx->len_tab.p, intervals, se_vw, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
+        hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(1024), 0, st, (const u64 *)ctx->seg_bits.p, (const u64 *)ctx->seg_zeros.p, (int)se_nent, (u64 *)ctx->seg_bitoff.p, (u64 *)ctx->seg_zoff.p,
+                           sm + SM_TOTAL_BITS, sm + SM_TOTAL_UNPRED, (u64)0, (unsigned *)d_stream, (const u64 *)d_plan);
+        // (behind the scan: the word it clears at the payload's start may begin with the header's last bytes)
+        hipLaunchKernelGGL(k_book_tail, dim3((unsigned)std::min<size_t>(64, (plan_fixed + tree_cap + 255) / 256)), dim3(256), 0, st, d_stream, (const unsigned char *)ctx->book_stage.p, (unsigned)bk_front,
+                           (unsigned)bk_mid, intervals, (const unsigned char *)ctx->lor_bits.p, ind_bytes, (const unsigned char *)ctx->book_tree.p, (const szh_book_rec *)d_rec, (const u64 *)d_plan);
+        if (G.g2.num >= 2 && G.g2.early <= szh_se::INNER && G.g2.late >= szh_se::INNER - 1)
+            hipLaunchKernelGGL((k_col_encode<T, true>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
+                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)0, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p, (const u64 *)d_plan);
+        else
+            hipLaunchKernelGGL((k_col_encode<T, false>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
+                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)0, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p, (const u64 *)d_plan);
+        hipLaunchKernelGGL((k_book_unpred<T>), dim3((unsigned)std::min<size_t>(256, (unpred_cap / sizeof(T) + 255) / 256)), dim3(256), 0, st, d_stream, (const T *)ctx->unpred.p, (const szh_book_rec *)d_rec, (const u64 *)d_plan);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        TP("encode launched");
+        u64 h_small[SM_COUNT];
+        HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ctx->book_pin, ctx->book_rec.p, 32 + SZH_PLAN_COUNT * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                                      // the call's one wait behind the sweep
+        TP("final sync");
+        szh_book_rec rec; memcpy(&rec, ctx->book_pin, sizeof(rec));
+        const u64 *const plan = (const u64 *)ctx->book_pin + 4;
+        if (tp_on) { for (int i = 0; i < tp_k; ++i) fprintf(stderr, "%s %.2f | ", tp_n[i], tp_t[i]); fprintf(stderr, "\n"); }
+        if ((unsigned)h_small[SM_ERR] == 2) { ctx->coef_late = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: the regression coefficients did not arrive"); }
+        if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
+        if (book_declines(rec.status, plan[SZH_PLAN_STATUS], tune_int("SZ_HIP_TEST_BOOK_FALLBACK", 0))) {
+            // (no message on stderr: the caller's wrapper repeats the call with the host's book)
+            ctx->book_declined = true;
+            snprintf(ctx->err, sizeof(ctx->err), "device code book declined (status %u)", rec.status ? rec.status : (unsigned)plan[SZH_PLAN_STATUS]);
+            return SZHIP_ERR_INTERNAL;
+        }
+        const u64 total_bits = rec.total_bits, total_unpred = rec.total_unpred;
+        const size_t total_len = (size_t)plan[SZH_PLAN_TOTAL_LEN];
+        if ((total_bits > 0 && h_small[SM_TOTAL_BITS] != total_bits) || h_small[SM_TOTAL_UNPRED] != total_unpred)
+            FAIL(SZHIP_ERR_INTERNAL, "entropy stage mismatch (bits %llu vs %llu, unpredictable %llu vs %llu)", (unsigned long long)h_small[SM_TOTAL_BITS],
+                 (unsigned long long)total_bits, (unsigned long long)h_small[SM_TOTAL_UNPRED], (unsigned long long)total_unpred);
+        if (out_on_device == 2) {
+            if (!*out || *out_size < total_len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, total_len);
+            if (!in_place) { HIPCHK(hipMemcpyAsync(*out, d_stream, total_len, hipMemcpyDeviceToDevice, st)); HIPCHK(hipStreamSynchronize(st)); }
+        } else if (out_on_device) *out = d_stream;
+        else {
+            unsigned char *h = (unsigned char *)malloc(total_len ? total_len : 1);
+            if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
+            const int rc_copy = staged_copy(ctx, h, d_stream, total_len, false);
+            if (rc_copy != SZHIP_OK) { free(h); return rc_copy; }
+            *out = h;
+        }
+        *out_size = total_len;
+        float ms = 0;
+        hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
+        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
+        hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
+        S.n_unpred = total_unpred; S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = total_len; S.packing = 1; S.book_on_device = 1;
+        if (stats) *stats = S;
+        return SZHIP_OK;
+    }
 
     // ---- Huffman code book (host: heap order decides the codes), built as soon as the histogram has arrived.  This is the only host
     //      round trip of the entropy stage: the number of unpredictable values is the histogram's bin 0, so the header can be written
