@@ -188,31 +188,24 @@ template <class F>
 static int with_ticket_fallback(szhip_ctx *ctx, F &&run)
 {
     ctx->wave_timeout = false; ctx->hdec_unconverged = false; ctx->coef_late = false; ctx->book_declined = false;
+    auto again = [&]() {       // drain the context's streams, then run the call again
+        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
+        return run();
+    };
     int rc = run();
     if (rc == SZHIP_ERR_INTERNAL && ctx->book_declined && !ctx->no_dev_book) {            // (compression with SZ_HIP_DEV_BOOK=1 only)
-        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
-        ctx->no_dev_book = true; ctx->wave_timeout = false;
-        rc = run();
-        ctx->no_dev_book = false;
+        ctx->no_dev_book = true; ctx->wave_timeout = false; rc = again(); ctx->no_dev_book = false;
     }
     if (rc == SZHIP_OK && !ctx->no_chain_overlap && tune_int("SZ_HIP_TEST_CHAIN_FALLBACK", 0)) { ctx->coef_late = true; rc = SZHIP_ERR_INTERNAL; }   // tests: exercise the repetition
     if (rc == SZHIP_ERR_INTERNAL && ctx->coef_late && !ctx->no_chain_overlap) {           // (compression of arrays with regression blocks only)
-        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
-        ctx->no_chain_overlap = true; ctx->wave_timeout = false;
-        rc = run();
+        ctx->no_chain_overlap = true; ctx->wave_timeout = false; rc = again();
     }
     if (rc == SZHIP_ERR_INTERNAL && ctx->hdec_unconverged && !ctx->hdec_sync_rounds) {      // (decompression only)
-        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
-        ctx->hdec_sync_rounds = true;
-        ctx->wave_timeout = false;
-        rc = run();
-        ctx->hdec_sync_rounds = false;
+        ctx->hdec_sync_rounds = true; ctx->wave_timeout = false; rc = again(); ctx->hdec_sync_rounds = false;
     }
     if (rc == SZHIP_OK && !ctx->ticket_atomic && tune_int("SZ_HIP_TEST_TICKET_FALLBACK", 0)) { ctx->wave_timeout = true; rc = SZHIP_ERR_INTERNAL; }   // tests: exercise the repetition
     if (rc == SZHIP_ERR_INTERNAL && ctx->wave_timeout && !ctx->ticket_atomic) {
-        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
-        ctx->ticket_atomic = true;
-        rc = run();
+        ctx->ticket_atomic = true; rc = again();
     }
     return rc;
 }

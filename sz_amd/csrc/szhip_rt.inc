@@ -24,7 +24,6 @@
         FAIL(code, __VA_ARGS__);                                                                       \
     } while (0)
 
-
 int ensure(szhip_ctx *ctx, DevBuf &b, size_t bytes, bool zero_new = false)
 {
     if (bytes == 0) bytes = 16;
@@ -37,49 +36,30 @@ int ensure(szhip_ctx *ctx, DevBuf &b, size_t bytes, bool zero_new = false)
     return SZHIP_OK;
 }
 
-int ensure_pinned(szhip_ctx *ctx, size_t bytes)
-{
-    if (ctx->pinned_cap >= bytes) return SZHIP_OK;
-    if (ctx->pinned) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipHostFree(ctx->pinned)); ctx->pinned = nullptr; ctx->pinned_cap = 0; }
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(hipHostMalloc(&ctx->pinned, cap, hipHostMallocDefault));
-    ctx->pinned_cap = cap;
-    return SZHIP_OK;
-}
-
-int ensure_pinned2(szhip_ctx *ctx, size_t bytes)
-{
-    if (ctx->pinned2_cap >= bytes) return SZHIP_OK;
-    if (ctx->pinned2) { HIPCHK(hipStreamSynchronize(ctx->stream2)); HIPCHK(hipHostFree(ctx->pinned2)); ctx->pinned2 = nullptr; ctx->pinned2_cap = 0; }
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(hipHostMalloc(&ctx->pinned2, cap, hipHostMallocDefault));
-    ctx->pinned2_cap = cap;
-    return SZHIP_OK;
-}
-
-int ensure_pinned3(szhip_ctx *ctx, size_t bytes)
-{
-    if (ctx->pinned3_cap >= bytes) return SZHIP_OK;
-    if (ctx->pinned3) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipHostFree(ctx->pinned3)); ctx->pinned3 = nullptr; ctx->pinned3_cap = 0; }
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(hipHostMalloc(&ctx->pinned3, cap, hipHostMallocDefault));
-    ctx->pinned3_cap = cap;
-    return SZHIP_OK;
-}
-
-int ensure_coherent(szhip_ctx *ctx, size_t bytes)
-{
-    if (ctx->coh_cap >= bytes) return SZHIP_OK;
-    if (ctx->coh) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipHostFree(ctx->coh)); ctx->coh = nullptr; ctx->coh_cap = 0; }
-    size_t cap = bytes + bytes / 4 + 4096;
-    HIPCHK(hipHostMalloc(&ctx->coh, cap, hipHostMallocCoherent | hipHostMallocMapped));
-    memset(ctx->coh, 0, cap);                          // (epoch-tagged words live here: none may look current by accident)
-    ctx->coh_cap = cap;
-    return SZHIP_OK;
-}
-
 #define TRY(x) do { int rc_ = (x); if (rc_ != SZHIP_OK) return rc_; } while (0)
 
+// the context's grow-only pinned host buffers: a buffer that must grow is released once the stream whose copies use it has drained
+int ensure_host(szhip_ctx *ctx, void *&p, size_t &have, size_t bytes, hipStream_t user, unsigned flags = hipHostMallocDefault)
+{
+    if (have >= bytes) return SZHIP_OK;
+    if (p) { HIPCHK(hipStreamSynchronize(user)); HIPCHK(hipHostFree(p)); p = nullptr; have = 0; }
+    size_t cap = bytes + bytes / 4 + 4096;
+    HIPCHK(hipHostMalloc(&p, cap, flags));
+    have = cap;
+    return SZHIP_OK;
+}
+int ensure_pinned(szhip_ctx *ctx, size_t bytes) { return ensure_host(ctx, ctx->pinned, ctx->pinned_cap, bytes, ctx->stream); }
+int ensure_pinned2(szhip_ctx *ctx, size_t bytes) { return ensure_host(ctx, ctx->pinned2, ctx->pinned2_cap, bytes, ctx->stream2); }
+int ensure_pinned3(szhip_ctx *ctx, size_t bytes) { return ensure_host(ctx, ctx->pinned3, ctx->pinned3_cap, bytes, ctx->stream); }
+int ensure_coherent(szhip_ctx *ctx, size_t bytes)
+{
+    const size_t had = ctx->coh_cap;
+    TRY(ensure_host(ctx, ctx->coh, ctx->coh_cap, bytes, ctx->stream, hipHostMallocCoherent | hipHostMallocMapped));
+    if (ctx->coh_cap != had) memset(ctx->coh, 0, ctx->coh_cap);      // (epoch-tagged words live here: none may look current by accident)
+    return SZHIP_OK;
+}
+
+// layout of the "small" device scratch (u64 slots)
 enum { SM_MINMAX = 0, SM_WITHIN = 2, SM_MEANCNT = 3, SM_TOTAL_UNPRED = 4, SM_TOTAL_BITS = 5, SM_TICKET = 6, SM_ERR = 7,
        SM_CHANGED = 8, SM_MEANSUM = 9, SM_TOTAL_SYM = 10, SM_NREG = 11, SM_SCRATCH = 12, SM_COUNT = 16 };
 
@@ -261,8 +241,6 @@ int scan_u64(szhip_ctx *ctx, const u64 *in, int64_t n, u64 *out, u64 *total_dev,
     HIPCHK(hipGetLastError());
     return SZHIP_OK;
 }
-
-// layout of the "small" device scratch (u64 slots)
 
 constexpr size_t SZH_PERM_TILE_BYTES = 32 * 1024;   // the tile budget of k_permute (choose_segb)
 int choose_segb(const szh_geom3 &G, size_t elem, size_t budget)

@@ -1,210 +1,331 @@
-// szhip_sz21.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace): the SZ 2.1 path (sz_float.c:7126-7560 / szd_float.c:3491-5860 and the double twins): compress_impl, the device Huffman decode, parse_header, decompress_impl.
+// szhip_sz21.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace): the SZ 2.1 path (sz_float.c:7126-7560 / szd_float.c:3491-5860 and the double twins): sz21_plan + sz21_call (a compress call's plan, its shared state and one member function per phase), compress_impl (the list of phases), the device Huffman decode, parse_header, decompress_impl.
 // the device code book's verdict as the host reads it behind the call's final synchronisation (szh_book.h): the kernel's own status, the plan's (the stream
 // outgrew the buffers), or the tests' switch -- any of them sends the call round again with the host's book
 static bool book_declines(unsigned rec_status, unsigned long long plan_status, int test_switch) { return rec_status != 0 || plan_status != 0 || test_switch != 0; }
 
+// how often a histogram of `intervals` bins is replicated in LDS (k_hist_u16, k_col_hist): 2^shift copies within `cap_bins` bins, 64 copies at the most
+static int hist_rshift(unsigned intervals, size_t cap_bins) { int r = 0; while (r < 6 && ((size_t)intervals << (r + 1)) <= cap_bins) ++r; return r; }
+
+// Which sweep a compress call takes and how its codes are packed: a pure function of the geometry, the alphabet, the regression-block count, the switches and the
+// context's flags, made once the chains' overlap is settled; `revise` is its one later change.
+struct sz21_plan {
+    bool use_beam = false;       // the beam sweep (else k_pencil)
+    bool segenc = false;         // the packing passes read the sweep's natural-order codes, segment by segment (szh_segenc.h); else block order first, then k_encode / k_encode32
+    bool seghist = false;        // small alphabets: a histogram per block column (k_col_hist), from which the columns' bit counts follow without another pass over the codes
+    bool dev_book = false;       // the code book on the device (szh_book.h)
+    bool sliced = false;         // histogram and block ordering slice by slice beside the running sweep
+    int slices_req = 1;
+    int se_vw = 1, se_segb = 0, se_nseg = 0, se_nrmax = szh_se::NR; size_t se_tile = 0;      // segments of `se_segb` blocks of a block column
+    int sh_rshift = 0;
+    // the code book is built and its longest code word known: k_col_encode takes code words of up to 32 bits -- beyond that the block-ordered copy after all
+    // (the caller runs permute_all) and the passes that read it
+    bool revise(unsigned enc_maxlen) { if (!segenc || enc_maxlen <= 32) return false; segenc = false; seghist = false; return true; }
+};
 template <class T>
-int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in,
-                  const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device,
-                  unsigned char **out, size_t *out_size, szhip_stats *stats)
+sz21_plan sz21_make_plan(const szhip_ctx *ctx, const szh_geom3 &G, unsigned intervals, size_t reg_count, bool beam_ok, bool overlap, bool feed, size_t meta_len)
 {
-    const int is_double = sizeof(T) == 8;
-    const bool two_d = r0 == 0;                                // r0 == 0: a 2-D array r1 x r2 (sz_float.c:5516)
-    const szh_geom3 G = two_d ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2);
-    const int ncoef = two_d ? 3 : 4;
-    const int64_t n = G.n, nb = G.nblocks;
-    const T eb = (T)eb_in;
-    const double t_begin = now_ms();
-    double host_ms = 0;
-    const int tp_on = tune_int("SZ_HIP_TIMING", 0); double tp_t[32]; const char *tp_n[32]; int tp_k = 0;
-    auto TP = [&](const char *nm) { if (tp_on && tp_k < 32) { tp_t[tp_k] = now_ms() - t_begin; tp_n[tp_k++] = nm; } };
-    hipStream_t st = ctx->stream;
-    szhip_stats S; memset(&S, 0, sizeof(S));
-    S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)nb;
-
-    const T *d_in = (const T *)data;
-    if (!data_on_device) {
-        TRY(ensure(ctx, ctx->in, (size_t)n * sizeof(T)));
-        TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-        d_in = (const T *)ctx->in.p;
+    sz21_plan P;
+    const int64_t n = G.n;
+    // Which sweep: the beam takes everything it covers (0.69 ms at 512^3 float; k_pencil's 4.4 / 7.4 ms become 1.2 / 2.3 at 512^3 M-field / the f64 slab), unless the
+    // chains run beside k_pencil (`overlap`); SZ_HIP_BEAM=0 switches it off
+    P.use_beam = !overlap && beam_ok;
+    // (round 6) the packing passes read the sweep's natural-order codes themselves, segment by segment (szh_segenc.h): no block-ordered copy, no k_permute /
+    // k_unpred, no cleared stream buffer.  Every 3-D array; whether the code book fits its kernels is known once the tree is built (revise).  SZ_HIP_SEGENC=0: as in round 5.
+    // Not for a sweep that is fed while the host's coefficient chains run (the 512^3 M-field): that sweep takes 1.8 ms, the older passes' slices hide beside it, and one
+    // call measured 3.04 ms with them against 3.18 with these (SZ_HIP_SEGENC=2 takes them there too).
+    const int segenc_sw = tune_int("SZ_HIP_SEGENC", 1);
+    P.segenc = G.ndim == 3 && segenc_sw != 0 && (!feed || segenc_sw == 2);
+    // the segments' rows, the code table and the bit window (sized here for the longest code words the kernel takes, 32 bits) share the workgroup's LDS.  A tile of
+    // 14 KB: k_col_encode needs 75 registers (six wavefronts per SIMD), so the LDS a workgroup takes decides how many columns a CU works on at once -- 512^3,
+    // segments of 29 / 22 / 17 / 15 / 11 blocks: 0.251 / 0.220 / 0.206 / 0.224 / 0.253 ms (profiles/r07_packing_rounds.txt)
+    P.se_vw = (G.g2.count % 8) == 0 ? 8 : ((G.g2.count % 4) == 0 ? 4 : 1);
+    if (P.segenc) {
+        bool ok = intervals < 65536 && (double)n < 4.0e9;            // (k_col_encode keeps a row's element offset in 32 bits)
+        // every block holds at least 32 codes, so a column's first round (all runs of its first segment, or 256 threads' worth) holds at least 32 code words and
+        // never ends inside the column's leading partial word; k_col_encode tells a word shared with the column before by its position all the same.  (3-D arrays of a
+        // 2 x 2 cross-section are the only ones this sends to the older passes: a dimension of 1 never comes here.)
+        if ((int64_t)G.g0.late * G.g1.late * G.g2.late < 32) ok = false;
+        const size_t fixed = ((size_t)intervals + 1) * 8 + 16 + szh_se::seg_window_words(G, 32) * 4 + 64;
+        const size_t lds_cap = (size_t)63 * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 14)) * 1024;
+        if (ok && fixed + szh_se::seg_tile_bytes(G, 1, P.se_vw) > lds_cap) ok = false;
+        if (ok) {
+            const size_t budget = std::min(lds_cap - fixed, std::max(want, szh_se::seg_tile_bytes(G, 1, P.se_vw)));
+            int sb = 1;
+            while (sb < G.g2.num && szh_se::seg_tile_bytes(G, sb + 1, P.se_vw) <= budget && szh_se::seg_pieces_per_thread(G, sb + 1, P.se_vw) <= (size_t)szh_se::PF) ++sb;
+            // segments of equal size, as few as the tile allows: no short segment at the end that pays a whole round's barriers, scan and tile load for a handful of runs
+            sb = (G.g2.num + (G.g2.num + sb - 1) / sb - 1) / ((G.g2.num + sb - 1) / sb);
+            if (const int f = tune_int("SZ_HIP_SEG_SEGB", 0)) sb = std::max(1, std::min(f, sb));
+            P.se_segb = sb;
+            P.se_nseg = (G.g2.num + sb - 1) / sb;
+            P.se_tile = szh_se::seg_tile_bytes(G, sb, P.se_vw);
+            // a round of k_col_encode is 256 threads x up to `se_nrmax` runs (the window is sized for that many): the usual block column's segment in as few rounds as
+            // NR allows, its runs spread evenly over them; a column of more rows takes more rounds
+            const int rows_typ = (2 * G.g0.split > G.g0.num ? G.g0.early : G.g0.late) * (2 * G.g1.split > G.g1.num ? G.g1.early : G.g1.late);
+            const int runs_typ = std::max(1, sb * rows_typ), rounds_typ = (runs_typ + 256 * szh_se::NR - 1) / (256 * szh_se::NR);
+            P.se_nrmax = std::max(1, std::min(szh_se::NR, (runs_typ + 256 * rounds_typ - 1) / (256 * rounds_typ)));
+            if ((double)G.g0.num * G.g1.num >= 2.0e9) ok = false;
+        }
+        P.segenc = ok;
     }
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
-    static const u64 minmax_init[2] = {~0ull, 0ull};          // ordered encodings: the fit pass reduces the array's range into these
-    HIPCHK(hipMemcpyAsync(sm + SM_MINMAX, minmax_init, 16, hipMemcpyHostToDevice, st));
-    const bool range_from_data = (prm->flags & SZHIP_RANGE_FROM_DATA) != 0;
-    TRY(ensure(ctx, ctx->coef, (size_t)nb * 4 * sizeof(T)));
-    TRY(ensure(ctx, ctx->blk_lor, (size_t)nb));
-    T *d_coef = (T *)ctx->coef.p;
-    uint8_t *d_lor = (uint8_t *)ctx->blk_lor.p;
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-    TP("ev0");
+    P.seghist = P.segenc && intervals <= SZH_COL_HBINS && tune_int("SZ_HIP_SEGHIST", 1) != 0;
+    if (P.seghist) P.sh_rshift = hist_rshift(intervals, 4096);                 // (16 KB of LDS)
+    // (SZ_HIP_DEV_BOOK=1, off by default) the code book on the device (szh_book.h): a Lorenzo-only array that takes the packing passes above, their two scans in
+    // one launch -- nothing of its entropy stage waits for the host; a book the kernel declines sends the call round again with the host's (with_ticket_fallback)
+    P.dev_book = P.segenc && reg_count == 0 && !ctx->no_dev_book && tune_int("SZ_HIP_DEV_BOOK", 0) != 0 && G.g0.num * G.g1.num <= 1024 * SZH_COL_SCAN_PER &&
+                 tune_int("SZ_HIP_SEG_SCAN1", 1) != 0 && meta_len + 8 + 4 + sizeof(T) + 1 + sizeof(T) <= 3072;
+    // The entropy stage's passes over the code array (histogram, block ordering) start on finished block rows while the beam sweep is still running: every wavefront
+    // publishes how many of its lines have their codes in memory (szh_beam.h, `tile_done`: a word per wavefront, written every 32 lines after write-through code stores
+    // and a vmcnt(0) -- a system-scope RELEASE per word cost ~35 us each and took the sweep from 1.05 to 1.58 ms); a slice = the block rows whose lines every wavefront
+    // has passed.  Measured at 512^3, one call: S-field 2.12 ms unsliced, 1.94 - 1.96 with 3 - 6 slices; M-field 3.94 -> 3.82 (profiles/r05_beam_slices.txt); more slices
+    // cost more than they hide (the slices' kernels take 2 - 4 x their lone time beside the sweep).  SZ_HIP_SLICES=1: everything after the sweep.  A lane of a pool
+    // (several arrays in flight) takes two slices (SZ_HIP_SLICES_POOL).  Not with the per-column histogram, which runs behind the sweep.
+    P.slices_req = tune_int("SZ_HIP_SLICES", ctx->gate ? tune_int("SZ_HIP_SLICES_POOL", 2) : 4);
+    P.sliced = P.use_beam && P.slices_req > 1 && !P.seghist;
+    return P;
+}
 
-    const int ncols = G.g0.num * G.g1.num;
-
-    unsigned intervals = prm->quantization_intervals;
-    const unsigned max_radius = prm->max_quant_intervals / 2;
-    HIPCHK(hipEventRecord(ctx->ev_in, st));                    // input staged, scratch cleared: the second stream's fit pass may start
-    HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
-
-    // ---- regression fit + predictor selection on the second stream, overlapped with the interval optimiser below.  The pass
-    //      needs only the bound -- except for the mean shortcut of the selection, which the optimiser may switch on; it is run
-    //      WITHOUT it here and repeated in the (rare) use_mean case.
-    const T noise = (T)((double)eb * (two_d ? 0.81 : 1.22));   // sz_float.c:7056 / :5672
-    // (round 6) SZ_HIP_FIT_TILE=1: from LDS tiles wherever that form applies (szh_fittile.h: blocks of up to 7, rows on 16-byte boundaries).  Alone it is the faster pass
-    // (512^3 float: 0.20 against 0.235 ms), inside a call it is not: the pre-quantisation phase ends with the interval optimiser's sampling pass, which shares the
-    // memory system with this one (0.345 against 0.335 ms; the float64 slab 0.81 against 0.76).  Off by default; else one thread per block straight from memory
-    const bool fit_tile = !two_d && szh_ft::applies<T>(G, d_in) && tune_int("SZ_HIP_FIT_TILE", 0) != 0;
-    const int ft_nseg = (G.g2.num + szh_ft::shape<T>::SEGB - 1) / szh_ft::shape<T>::SEGB;
-    auto launch_fit = [&](hipStream_t s_, int um, T mn) -> int {
+// One compress call of the SZ 2.1 path: what its phases share.  compress_impl (below) is the list of the phases; each returns the usual status.
+// LIFETIMES.  Host threads work on this object while a call runs: the chain threads and the pool's jobs (run_chains) read and write cf, sec_len, section_failed,
+// all_reg_keep, chain_done, chain_avail, chain_t0/1, and call make_section.  The destructor's BODY joins them (as join_sections() does where the header is assembled), so
+// every member is still alive then, whichever way the call returns (it also disarms the pool, a no-op on the early returns that never armed it); the members go after
+// it, in reverse order of declaration: fed_guard is lowered after the join.
+// se_segs, tab_code and tab_len are copied to the device asynchronously and live until the final synchronisation.  The object is neither copied nor moved.
+template <class T>
+struct sz21_call {
+    static constexpr int is_double = sizeof(T) == 8;
+    static constexpr int64_t LINE = 128 / (int64_t)sizeof(T);         // values per 128-byte cache line
+    // ---- arguments, geometry
+    szhip_ctx *const ctx; const szhip_params *const prm; const unsigned char *meta; const size_t meta_len; const int out_on_device; unsigned char **const out; size_t *const out_size;
+    const double eb_in; const T eb; const hipStream_t st;
+    const bool two_d;                                          // r0 == 0: a 2-D array r1 x r2 (sz_float.c:5516)
+    const szh_geom3 G; const int ncoef, ncols; const int64_t n, nb;
+    // ---- statistics and the SZ_HIP_TIMING trace
+    const double t_begin = now_ms(); double host_ms = 0;
+    const int tp_on = tune_int("SZ_HIP_TIMING", 0); double tp_t[32]; const char *tp_n[32]; int tp_k = 0;
+    szhip_stats S;
+    // ---- device arrays, the pinned words the fit pass fills
+    const T *d_in = nullptr; u64 *sm = nullptr; T *d_coef = nullptr; uint8_t *d_lor = nullptr; uint16_t *d_nat = nullptr, *d_blk = nullptr; unsigned *d_hist = nullptr, *h_hist = nullptr;
+    T noise = 0; bool fit_tile = false; int ft_nseg = 0;
+    size_t ind_bytes = 0; unsigned char *ind_bits = nullptr; u64 *nreg_h = nullptr, *minmax_h = nullptr;
+    // ---- decisions
+    unsigned intervals = 0; int use_mean = 0; T mean = 0; size_t reg_count = 0;
+    std::vector<unsigned char> meta_own;                       // the parameter bytes as they go into the stream
+    sz21_plan P;
+    unsigned *tile_done = nullptr; size_t beam_words = 0;      // sliced: the words the beam's wavefronts publish
+    int perm_segb = 1, perm_nseg = 1; size_t perm_lds = 0;     // k_permute's tile (prepare_permute)
+    // ---- the code book and the stream's layout (host book)
+    std::vector<szh_se::seg_t> se_segs; std::vector<u64> tab_code; std::vector<uint8_t> tab_len;
+    unsigned enc_maxlen = 0; bool enc32 = false; size_t lds_e32 = 0;
+    unsigned char *hdr = nullptr; size_t pre_len = 0, sections_total = 0, hdr_len = 0, unpred_bytes = 0, total_len = 0; u64 total_bits = 0, total_unpred = 0;
+    u64 h_small[SM_COUNT];                                     // the device's small words, read after the final synchronisation
+    bool synced = false;                                       // the call's final synchronisation is behind us (the device book checks before it delivers)
+    // ---- the coefficient chains: everything the host threads touch (see LIFETIMES)
+    szhost_coeffs cf;
+    size_t sec_len[4] = {0, 0, 0, 0};           // the coefficient sections (built by the chain threads in the context's PINNED buffers: they go to the device from where they are, beside
+                                                // the encoder -- assembling 3.4 MB of them into the header cost 0.2 ms of host copies and 0.1 ms of transfer in front of the encoder at the 512^3 M-field)
+    std::vector<std::thread> section_threads;
+    std::atomic<int> section_failed{0};
+    std::vector<unsigned char> all_reg_keep;   // "every block is a regression block" for the chain over the compacted coefficients
+    std::vector<uint32_t> blk_of_rank;
+    size_t chain_done[4] = {0, 0, 0, 0};       // regression blocks finished per coefficient (written by the chain threads)
+    size_t chain_avail = 0;                    // regression blocks whose coefficients have arrived on the host (read by the chain threads)
+    double chain_t0[4] = {0, 0, 0, 0}, chain_t1[4] = {0, 0, 0, 0};   // (SZ_HIP_TIMING: when each chain thread started / finished its chain)
+    bool overlap = false, feed = false, two_pieces = false;
+    fed_call_guard fed_guard;                   // (lowered when this call returns, whichever way)
+    T *hcoef = nullptr;   // pinned: an asynchronous copy to or from pageable memory makes the runtime pin and unpin the pages around it, which was seen to stall later calls for ~20 ms
+    bool pool_busy = false;                     // a job of this call is on the context's chain workers
+    bool cf_own = false;                        // cf's output arrays belong to the context
+    sz21_call(szhip_ctx *c, size_t r0, size_t r1, size_t r2, double eb_, const szhip_params *p, const unsigned char *m, size_t ml, int ood, unsigned char **o, size_t *os)
+        : ctx(c), prm(p), meta(m), meta_len(ml), out_on_device(ood), out(o), out_size(os), eb_in(eb_), eb((T)eb_), st(c->stream), two_d(r0 == 0),
+          G(r0 == 0 ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2)), ncoef(r0 == 0 ? 3 : 4), ncols(G.g0.num * G.g1.num), n(G.n), nb(G.nblocks)
+    {
+        memset(&S, 0, sizeof(S)); memset(&cf, 0, sizeof(cf));
+        S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)nb;
+    }
+    // no return may leave the section threads (or the pool's workers) running on this object, or the pool armed
+    ~sz21_call() {
+        join_sections();
+        if (ctx->chain_pool) ctx->chain_pool->disarm();
+        if (cf_own) for (int e = 0; e < 4; ++e) { cf.codes[e] = nullptr; cf.unpred[e] = nullptr; }
+        szhost_coeffs_free(&cf);
+    }
+    void join_sections() {
+        for (auto &x : section_threads) if (x.joinable()) x.join();
+        if (pool_busy && ctx->chain_pool) { ctx->chain_pool->wait_all(); pool_busy = false; }
+    }
+    void TP(const char *nm) { if (tp_on && tp_k < 32) { tp_t[tp_k] = now_ms() - t_begin; tp_n[tp_k++] = nm; } }
+    void print_trace() const { if (tp_on) { for (int i = 0; i < tp_k; ++i) fprintf(stderr, "%s %.2f | ", tp_n[i], tp_t[i]); fprintf(stderr, "\n"); } }
+    // the indicator bits are in scan order (dim 0 outermost), most significant bit first; a set bit = a Lorenzo block
+    bool is_lorenzo(int64_t bb) const { return (ind_bits[bb >> 3] >> (7 - (bb & 7))) & 1; }
+    size_t count_lorenzo(int64_t bb, int64_t b_end) const {
+        size_t ones = 0;
+        for (; bb < b_end && (bb & 7); ++bb) ones += is_lorenzo(bb);
+        for (; bb + 64 <= b_end; bb += 64) { uint64_t w8; memcpy(&w8, ind_bits + (bb >> 3), 8); ones += (size_t)__builtin_popcountll(w8); }
+        for (; bb < b_end; ++bb) ones += is_lorenzo(bb);
+        return ones;
+    }
+    // how far the slowest chain is: regression blocks that every coefficient's chain has finished
+    size_t chains_done() const {
+        size_t p = reg_count;
+        for (int e = 0; e < ncoef; ++e) { const size_t d = __atomic_load_n(&chain_done[e], __ATOMIC_ACQUIRE); if (d < p) p = d; }
+        return p;
+    }
+    int launch_fit(hipStream_t s_, int um, T mn) {
         if (fit_tile) hipLaunchKernelGGL((k_fit_tile<T>), dim3((unsigned)((int64_t)ncols * ft_nseg)), dim3(64), 0, s_, G, d_in, d_coef, d_lor, noise, um, mn, sm + SM_MINMAX, ft_nseg);
         else hipLaunchKernelGGL((k_fit_select<T>), dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s_, G, d_in, d_coef, d_lor, noise, um, mn, sm + SM_MINMAX);
         HIPCHK(hipGetLastError());
         return SZHIP_OK;
-    };
-    TRY(launch_fit(ctx->stream2, 0, (T)0));
-    // the stream's indicator bit array and the regression-block count come from the device (no per-block host loop); they follow the
-    // speculative pass on the second stream, so that they are on the host by the time the interval decision is made
-    const size_t ind_bytes = ((size_t)nb + 7) / 8;
-    TRY(ensure(ctx, ctx->lor_bits, ind_bytes + 8));
-    TRY(ensure_pinned2(ctx, ind_bytes + 32));                   // pinned: the copies below must not block this thread
-    unsigned char *const ind_bits = (unsigned char *)ctx->pinned2 + 32;
-    u64 *const nreg_h = (u64 *)ctx->pinned2;
-    u64 *const minmax_h = (u64 *)ctx->pinned2 + 2;
-    hipLaunchKernelGGL(k_pack_lor, dim3((unsigned)((ind_bytes + 255) / 256)), dim3(256), 0, ctx->stream2, (const uint8_t *)d_lor, nb,
-                       (uint8_t *)ctx->lor_bits.p, sm + SM_NREG);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ind_bits, ctx->lor_bits.p, ind_bytes, hipMemcpyDeviceToHost, ctx->stream2));
-    HIPCHK(hipMemcpyAsync(nreg_h, sm + SM_NREG, 8, hipMemcpyDeviceToHost, ctx->stream2));
-    HIPCHK(hipMemcpyAsync(minmax_h, sm + SM_MINMAX, 16, hipMemcpyDeviceToHost, ctx->stream2));
-    HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
-
+    }
+    int launch_pack_lor(hipStream_t s_) {
+        hipLaunchKernelGGL(k_pack_lor, dim3((unsigned)((ind_bytes + 255) / 256)), dim3(256), 0, s_, (const uint8_t *)d_lor, nb, (uint8_t *)ctx->lor_bits.p, sm + SM_NREG);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ind_bits, ctx->lor_bits.p, ind_bytes, hipMemcpyDeviceToHost, s_));
+        HIPCHK(hipMemcpyAsync(nreg_h, sm + SM_NREG, 8, hipMemcpyDeviceToHost, s_));
+        return SZHIP_OK;
+    }
+    // ---- the input staged, the scratch cleared; regression fit + predictor selection on the second stream, overlapped with the interval optimiser.  The pass
+    //      needs only the bound -- except for the mean shortcut of the selection, which the optimiser may switch on; it is run WITHOUT it here and repeated in the
+    //      (rare) use_mean case (join_fit).
+    int stage_and_fit(const void *data, int data_on_device) {
+        d_in = (const T *)data;
+        if (!data_on_device) {
+            TRY(ensure(ctx, ctx->in, (size_t)n * sizeof(T)));
+            TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
+            d_in = (const T *)ctx->in.p;
+        }
+        TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
+        sm = (u64 *)ctx->small.p;
+        HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
+        static const u64 minmax_init[2] = {~0ull, 0ull};          // ordered encodings: the fit pass reduces the array's range into these
+        HIPCHK(hipMemcpyAsync(sm + SM_MINMAX, minmax_init, 16, hipMemcpyHostToDevice, st));
+        TRY(ensure(ctx, ctx->coef, (size_t)nb * 4 * sizeof(T)));
+        TRY(ensure(ctx, ctx->blk_lor, (size_t)nb));
+        d_coef = (T *)ctx->coef.p;
+        d_lor = (uint8_t *)ctx->blk_lor.p;
+        HIPCHK(hipEventRecord(ctx->ev[0], st));
+        TP("ev0");
+        HIPCHK(hipEventRecord(ctx->ev_in, st));                    // input staged, scratch cleared: the second stream's fit pass may start
+        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
+        noise = (T)((double)eb * (two_d ? 0.81 : 1.22));           // sz_float.c:7056 / :5672
+        // (round 6) SZ_HIP_FIT_TILE=1: from LDS tiles wherever that form applies (szh_fittile.h: blocks of up to 7, rows on 16-byte boundaries).  Alone it is the faster pass
+        // (512^3 float: 0.20 against 0.235 ms), inside a call it is not: the pre-quantisation phase ends with the interval optimiser's sampling pass, which shares the
+        // memory system with this one (0.345 against 0.335 ms; the float64 slab 0.81 against 0.76).  Off by default; else one thread per block straight from memory
+        fit_tile = !two_d && szh_ft::applies<T>(G, d_in) && tune_int("SZ_HIP_FIT_TILE", 0) != 0;
+        ft_nseg = (G.g2.num + szh_ft::shape<T>::SEGB - 1) / szh_ft::shape<T>::SEGB;
+        TRY(launch_fit(ctx->stream2, 0, (T)0));
+        // the stream's indicator bit array and the regression-block count come from the device (no per-block host loop); they follow the
+        // speculative pass on the second stream, so that they are on the host by the time the interval decision is made
+        ind_bytes = ((size_t)nb + 7) / 8;
+        TRY(ensure(ctx, ctx->lor_bits, ind_bytes + 8));
+        TRY(ensure_pinned2(ctx, ind_bytes + 32));                   // pinned: the copies below must not block this thread
+        ind_bits = (unsigned char *)ctx->pinned2 + 32;
+        nreg_h = (u64 *)ctx->pinned2;
+        minmax_h = (u64 *)ctx->pinned2 + 2;
+        TRY(launch_pack_lor(ctx->stream2));
+        HIPCHK(hipMemcpyAsync(minmax_h, sm + SM_MINMAX, 16, hipMemcpyDeviceToHost, ctx->stream2));
+        HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
+        return SZHIP_OK;
+    }
     // ---- interval optimiser (round 6 tried two other orders of its passes -- the mean's gather enqueued in front of the fit pass's launches; the sampling pass started before
     //      the mean is known, keeping its sampled values for a small histogram pass --: no faster and slower, profiles/r06_prequant_experiments.txt; removed again)
-    int use_mean = 0; T mean = 0;
-    if (intervals == 0) {
-        const int64_t md = (int64_t)(int)std::sqrt((double)n);
-        // 2-D: a plain stride (sz_float.c:5412-5417): no step-backs
-        const szh_meanwalk w = two_d ? szh_make_meanwalk(n, INT64_MAX / 2, INT64_MAX / 2, md) : szh_make_meanwalk(n, G.d0, G.g2.count, md);
-        int64_t M = 0; // number of strided samples: first m with pos >= n (positions are increasing)
-        {
-            int64_t lo = 0, hi = n / std::max<int64_t>(md - 2, 1) + 2;
-            while (szh_meanwalk_pos(w, hi) < n) hi *= 2;
-            while (lo < hi) { int64_t mid = (lo + hi) / 2; if (szh_meanwalk_pos(w, mid) >= n) hi = mid; else lo = mid + 1; }
-            M = lo;
-        }
-        TRY(ensure(ctx, ctx->samples, (size_t)M * sizeof(T)));
-        TRY(ensure_pinned(ctx, std::max<size_t>((size_t)M * sizeof(T), (size_t)(max_radius + 8192) * 4 + 64)));
-        hipLaunchKernelGGL((k_gather_mean<T>), dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, d_in, w, M, (T *)ctx->samples.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctx->pinned, ctx->samples.p, (size_t)M * sizeof(T), hipMemcpyDeviceToHost, st));
-        TP("mean enqueued");
-        HIPCHK(hipStreamSynchronize(st));
-        TP("mean on host");
-        double h0 = now_ms();
-        const double smean = szhost_seq_mean(is_double, ctx->pinned, (size_t)M);
-        host_ms += now_ms() - h0;
-
-        TRY(ensure(ctx, ctx->hist, (size_t)(max_radius + 8192) * 4 + 64));
-        unsigned *d_rh = (unsigned *)ctx->hist.p, *d_fh = d_rh + max_radius;
-        HIPCHK(hipMemsetAsync(d_rh, 0, (size_t)(max_radius + 8192) * 4, st));
-        const int64_t nrows = szh_sample_row_limit(G, prm->sample_distance);
-        if (!two_d && (G.g0.count <= 1 || G.g1.count <= 1)) {      // a degenerate 3-D array: the reference's walk, literally (k_sample_walk)
-            hipLaunchKernelGGL((k_sample_walk<T, true>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)smean, max_radius, d_rh, d_fh, sm + SM_WITHIN);
+    int choose_intervals() {
+        intervals = prm->quantization_intervals;
+        const unsigned max_radius = prm->max_quant_intervals / 2;
+        if (intervals == 0) {
+            const int64_t md = (int64_t)(int)std::sqrt((double)n);
+            // 2-D: a plain stride (sz_float.c:5412-5417): no step-backs
+            const szh_meanwalk w = two_d ? szh_make_meanwalk(n, INT64_MAX / 2, INT64_MAX / 2, md) : szh_make_meanwalk(n, G.d0, G.g2.count, md);
+            int64_t M = 0, M_hi = n / std::max<int64_t>(md - 2, 1) + 2; // number of strided samples: first m with pos >= n (positions are increasing)
+            while (szh_meanwalk_pos(w, M_hi) < n) M_hi *= 2;
+            while (M < M_hi) { int64_t mid = (M + M_hi) / 2; if (szh_meanwalk_pos(w, mid) >= n) M_hi = mid; else M = mid + 1; }
+            TRY(ensure(ctx, ctx->samples, (size_t)M * sizeof(T)));
+            TRY(ensure_pinned(ctx, std::max<size_t>((size_t)M * sizeof(T), (size_t)(max_radius + 8192) * 4 + 64)));
+            hipLaunchKernelGGL((k_gather_mean<T>), dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, d_in, w, M, (T *)ctx->samples.p);
             HIPCHK(hipGetLastError());
-        } else if (nrows > 0) {
-            int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-            hipLaunchKernelGGL((k_sample<T, true>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb,
-                               (T)smean, max_radius, d_rh, d_fh, sm + SM_WITHIN);
-            HIPCHK(hipGetLastError());
-        }
-        unsigned *h_hist = (unsigned *)ctx->pinned;
-        u64 within = 0;
-        HIPCHK(hipMemcpyAsync(h_hist, d_rh, (size_t)(max_radius + 8192) * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&within, sm + SM_WITHIN, 8, hipMemcpyDeviceToHost, st));
-        TP("sample enqueued");
-        HIPCHK(hipStreamSynchronize(st));
-        TP("sample on host");
-        h0 = now_ms();
-        u64 sample_count = 0;
-        for (unsigned i = 0; i < max_radius; ++i) sample_count += h_hist[i];
-        szhost_decision dec;
-        szhost_decide(is_double, h_hist, max_radius, h_hist + max_radius, sample_count, within, prm->pred_threshold,
-                      (double)eb, smean, &dec);
-        host_ms += now_ms() - h0;
-        intervals = dec.intervals; use_mean = two_d ? 0 : dec.use_mean;   // 2-D: `use_mean = 0`, sz_float.c:5615
-        if (use_mean) {
-            T *d_sum = (T *)(sm + SM_MEANSUM);
-            hipLaunchKernelGGL((k_mean_seq<T>), dim3(1), dim3(64), 0, st, d_in, n, (T)dec.dense_pos, eb, d_sum, sm + SM_MEANCNT);
-            HIPCHK(hipGetLastError());
-            T hsum = 0; u64 hcnt = 0;
-            HIPCHK(hipMemcpyAsync(&hsum, d_sum, sizeof(T), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(&hcnt, sm + SM_MEANCNT, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ctx->pinned, ctx->samples.p, (size_t)M * sizeof(T), hipMemcpyDeviceToHost, st));
+            TP("mean enqueued");
             HIPCHK(hipStreamSynchronize(st));
-            if (hcnt > 0) mean = hsum / (T)hcnt; // `mean = sum / mean_count`, sz_float.c:6668
+            TP("mean on host");
+            double h0 = now_ms();
+            const double smean = szhost_seq_mean(is_double, ctx->pinned, (size_t)M);
+            host_ms += now_ms() - h0;
+            TRY(ensure(ctx, ctx->hist, (size_t)(max_radius + 8192) * 4 + 64));
+            unsigned *d_rh = (unsigned *)ctx->hist.p, *d_fh = d_rh + max_radius;
+            HIPCHK(hipMemsetAsync(d_rh, 0, (size_t)(max_radius + 8192) * 4, st));
+            const int64_t nrows = szh_sample_row_limit(G, prm->sample_distance);
+            if (!two_d && (G.g0.count <= 1 || G.g1.count <= 1)) {      // a degenerate 3-D array: the reference's walk, literally (k_sample_walk)
+                hipLaunchKernelGGL((k_sample_walk<T, true>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)smean, max_radius, d_rh, d_fh, sm + SM_WITHIN);
+                HIPCHK(hipGetLastError());
+            } else if (nrows > 0) {
+                int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
+                hipLaunchKernelGGL((k_sample<T, true>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb, (T)smean, max_radius, d_rh, d_fh, sm + SM_WITHIN);
+                HIPCHK(hipGetLastError());
+            }
+            unsigned *s_hist = (unsigned *)ctx->pinned;
+            u64 within = 0;
+            HIPCHK(hipMemcpyAsync(s_hist, d_rh, (size_t)(max_radius + 8192) * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&within, sm + SM_WITHIN, 8, hipMemcpyDeviceToHost, st));
+            TP("sample enqueued");
+            HIPCHK(hipStreamSynchronize(st));
+            TP("sample on host");
+            h0 = now_ms();
+            u64 sample_count = 0;
+            for (unsigned i = 0; i < max_radius; ++i) sample_count += s_hist[i];
+            szhost_decision dec;
+            szhost_decide(is_double, s_hist, max_radius, s_hist + max_radius, sample_count, within, prm->pred_threshold, (double)eb, smean, &dec);
+            host_ms += now_ms() - h0;
+            intervals = dec.intervals; use_mean = two_d ? 0 : dec.use_mean;   // 2-D: `use_mean = 0`, sz_float.c:5615
+            if (use_mean) {
+                T *d_sum = (T *)(sm + SM_MEANSUM);
+                hipLaunchKernelGGL((k_mean_seq<T>), dim3(1), dim3(64), 0, st, d_in, n, (T)dec.dense_pos, eb, d_sum, sm + SM_MEANCNT);
+                HIPCHK(hipGetLastError());
+                T hsum = 0; u64 hcnt = 0;
+                HIPCHK(hipMemcpyAsync(&hsum, d_sum, sizeof(T), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(&hcnt, sm + SM_MEANCNT, 8, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                if (hcnt > 0) mean = hsum / (T)hcnt; // `mean = sum / mean_count`, sz_float.c:6668
+            }
         }
+        if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
+        S.intervals = intervals; S.use_mean = use_mean;
+        return SZHIP_OK;
     }
-    if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
-    S.intervals = intervals; S.use_mean = use_mean;
-
-    HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));           // join the fit + selection pass
-    if (use_mean) {                                            // the selection depends on the mean after all: repeat the pass
-        TRY(launch_fit(st, use_mean, mean));
-    }
-    if (use_mean) {                                            // (the repeated pass: its indicator bits replace the speculative ones)
-        HIPCHK(hipMemsetAsync(sm + SM_NREG, 0, 8, st));
-        hipLaunchKernelGGL(k_pack_lor, dim3((unsigned)((ind_bytes + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor, nb,
-                           (uint8_t *)ctx->lor_bits.p, sm + SM_NREG);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ind_bits, ctx->lor_bits.p, ind_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(nreg_h, sm + SM_NREG, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else HIPCHK(hipEventSynchronize(ctx->ev_fit));           // usually long done
-    TP("fit joined");
-    const size_t reg_count = (size_t)*nreg_h;
-    S.n_reg_blocks = reg_count;
-    if (reg_count == 0 && ctx->chain_pool) ctx->chain_pool->disarm();
-    // the parameter bytes as they go into the stream: with SZHIP_RANGE_FROM_DATA the range field comes from the fit pass
-    // (computeRangeSize_float + `max = min + valueRangeSize`, sz_float.c:2845-2849, in the data's type)
-    std::vector<unsigned char> meta_own(meta, meta + meta_len);
-    if (range_from_data) {
-        if (meta_len < 4 + 20 + 2 * sizeof(T)) FAIL(SZHIP_ERR_ARG, "parameter bytes too short for a range field");
-        const T lo = (T)ord_dec<T>(minmax_h[0]), hi = (T)ord_dec<T>(minmax_h[1]);
-        const T range = hi - lo, top = lo + range;
-        unsigned char *q = meta_own.data() + 4 + 20;
-        if (is_double) { szhost_put_f64be(q, (double)lo); szhost_put_f64be(q + 8, (double)top); }
-        else { szhost_put_f32be(q, (float)lo); szhost_put_f32be(q + 4, (float)top); }
-        S.vmin = (double)lo; S.vmax = (double)hi;
-        if ((double)range <= eb_in) {          // constant within the bound: the caller's business (a full compression would be thrown away)
-            HIPCHK(hipStreamSynchronize(ctx->stream2)); HIPCHK(hipStreamSynchronize(st));
-            *out = nullptr; *out_size = 0;
-            S.ms_total = now_ms() - t_begin;
-            if (stats) *stats = S;
-            return SZHIP_CONSTANT;
+    // ---- the fit + selection pass joined (repeated if the selection depends on the mean after all); the range field; SZHIP_CONSTANT
+    int join_fit() {
+        HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));
+        if (use_mean) {                                            // (the repeated pass: its indicator bits replace the speculative ones)
+            TRY(launch_fit(st, use_mean, mean));
+            HIPCHK(hipMemsetAsync(sm + SM_NREG, 0, 8, st));
+            TRY(launch_pack_lor(st));
+            HIPCHK(hipStreamSynchronize(st));
+        } else HIPCHK(hipEventSynchronize(ctx->ev_fit));           // usually long done
+        TP("fit joined");
+        reg_count = (size_t)*nreg_h;
+        S.n_reg_blocks = reg_count;
+        if (reg_count == 0 && ctx->chain_pool) ctx->chain_pool->disarm();
+        // the parameter bytes as they go into the stream: with SZHIP_RANGE_FROM_DATA the range field comes from the fit pass
+        // (computeRangeSize_float + `max = min + valueRangeSize`, sz_float.c:2845-2849, in the data's type)
+        meta_own.assign(meta, meta + meta_len);
+        if (prm->flags & SZHIP_RANGE_FROM_DATA) {
+            if (meta_len < 4 + 20 + 2 * sizeof(T)) FAIL(SZHIP_ERR_ARG, "parameter bytes too short for a range field");
+            const T lo = (T)ord_dec<T>(minmax_h[0]), hi = (T)ord_dec<T>(minmax_h[1]);
+            const T range = hi - lo, top = lo + range;
+            unsigned char *q = meta_own.data() + 4 + 20;
+            if (is_double) { szhost_put_f64be(q, (double)lo); szhost_put_f64be(q + 8, (double)top); }
+            else { szhost_put_f32be(q, (float)lo); szhost_put_f32be(q + 4, (float)top); }
+            S.vmin = (double)lo; S.vmax = (double)hi;
+            if ((double)range <= eb_in) {          // constant within the bound: the caller's business (a full compression would be thrown away)
+                HIPCHK(hipStreamSynchronize(ctx->stream2)); HIPCHK(hipStreamSynchronize(st));
+                *out = nullptr; *out_size = 0;
+                S.ms_total = now_ms() - t_begin;
+                return SZHIP_CONSTANT;
+            }
         }
+        meta = meta_own.data();
+        return SZHIP_OK;
     }
-    meta = meta_own.data();
-    // ---- regression coefficient chain (a serial recurrence with reconstruction feedback: host) and its Huffman streams.
-    //      The chains of the four (three) coefficients are independent of each other and each is bound by the latency of its own
-    //      ~45-cycle dependence per block, so they run on one host thread each; a thread goes on to build its coefficient's section
-    //      of the stream header (histogram, tree, payload) while the wavefront kernel is already running on the decoded values.
-    szhost_coeffs cf; memset(&cf, 0, sizeof(cf));
-    size_t sec_len[4] = {0, 0, 0, 0};           // the coefficient sections (built by the chain threads in the context's PINNED buffers: they are copied to the
-                                                // device from where they are, beside the encoder -- assembling 3.4 MB of them into the header cost 0.2 ms of host copies
-                                                // and 0.1 ms of transfer in front of the encoder at the 512^3 M-field)
-    std::vector<std::thread> section_threads;
-    std::atomic<int> section_failed(0);
-    std::vector<unsigned char> all_reg_keep;   // "every block is a regression block" for the chain over the compacted coefficients
-    std::vector<uint32_t> blk_of_rank;
-    size_t chain_done[4] = {0, 0, 0, 0};       // regression blocks finished per coefficient (written by the chain threads)
-    size_t chain_avail = 0;                    // regression blocks whose coefficients have arrived on the host (read by the chain threads: lives as long as they may run)
-    double chain_t0[4] = {0, 0, 0, 0}, chain_t1[4] = {0, 0, 0, 0};   // (SZ_HIP_TIMING: when each chain thread started / finished its chain)
-    bool overlap = false, feed = false;
-    fed_call_guard fed_guard;                   // (lowered when this call returns, whichever way)
-    T *hcoef = nullptr;   // pinned: an asynchronous copy to or from pageable memory makes the runtime pin and unpin the pages around it,
-                          // which was seen to stall later calls for ~20 ms
-    auto make_section = [&](int e) {   // (lives as long as the threads that call it: declared in the function's scope)
+    // a coefficient's section of the stream header (histogram, tree, payload), built by the thread that ran its chain
+    void make_section(int e) {
         std::vector<uint32_t> h32(65536, 0);
         for (size_t i = 0; i < reg_count; ++i) h32[(size_t)cf.codes[e][i]]++;
         szhost_huff *ch = szhost_huff_build(131072, h32.data(), nullptr, 65536);
@@ -226,22 +347,13 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         memcpy(q, cf.unpred[e], cf.unpred_count[e] * sizeof(T)); q += cf.unpred_count[e] * sizeof(T);
         sec_len[e] = (size_t)(q - sec0);
         szhost_huff_free(ch);
-    };
-    bool pool_busy = false;                     // a job of this call is on the context's chain workers
-    struct JoinSections {   // no early return may leave the section threads (or the pool's workers) running on this frame's data
-        std::vector<std::thread> &t; szhost_coeffs &c; szhip_ctx *ctx; bool &busy;
-        bool own = false;           // the output arrays belong to the context
-        ~JoinSections()
-        {
-            for (auto &x : t) if (x.joinable()) x.join();
-            if (busy && ctx->chain_pool) ctx->chain_pool->wait_all();
-            if (ctx->chain_pool) ctx->chain_pool->disarm();
-            if (own) for (int e = 0; e < 4; ++e) { c.codes[e] = nullptr; c.unpred[e] = nullptr; }
-            szhost_coeffs_free(&c);
-        }
-    } join_sections{section_threads, cf, ctx, pool_busy};
-    if (ctx->chain_pool) ctx->chain_pool->arm();       // (the workers wake up now and spin until the coefficients are there -- or are sent back to sleep below)
-    if (reg_count > 0) {
+    }
+    // ---- regression coefficient chain (a serial recurrence with reconstruction feedback: host) and its Huffman streams.
+    //      The chains of the four (three) coefficients are independent of each other and each is bound by the latency of its own
+    //      ~45-cycle dependence per block, so they run on one host thread each; a thread goes on to build its coefficient's section
+    //      of the stream header while the sweep is already running on the decoded values.
+    //      Here: the sections' buffers, the coefficients ranked and gathered, and how the chains overlap with the sweep (`overlap`, `feed`).
+    int prepare_chains() {
         // the sections' buffers, sized for the worst case (a tree of every possible symbol, 64-bit codes, every coefficient verbatim) before any thread writes
         for (int e = 0; e < ncoef; ++e) {
             const size_t bound = sizeof(T) + 12 + (13 * 2 * std::min<size_t>(reg_count, 65536) + 16) + 8 + (8 * reg_count + 16) + 4 + reg_count * sizeof(T) + 64;
@@ -259,8 +371,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         TRY(ensure(ctx, ctx->coef_compact, reg_count * 4 * sizeof(T)));
         hipLaunchKernelGGL(k_reg_flags, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor, nb, (u64 *)ctx->reg_flags.p);
         TRY(scan_u64(ctx, (const u64 *)ctx->reg_flags.p, nb, (u64 *)ctx->reg_rank.p, sm + SM_SCRATCH));
-        hipLaunchKernelGGL((k_move_coef<T, 0>), dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor,
-                           (const u64 *)ctx->reg_rank.p, nb, (int64_t)reg_count, d_coef, (T *)ctx->coef_compact.p);
+        hipLaunchKernelGGL((k_move_coef<T, 0>), dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor, (const u64 *)ctx->reg_rank.p, nb, (int64_t)reg_count, d_coef, (T *)ctx->coef_compact.p);
         HIPCHK(hipGetLastError());
 #ifndef SZH_SYNC_LAUNCH
         // (not in a pool lane: with several contexts at work the hand-off of coefficients to the running kernel failed 5 - 6 times in 480
@@ -280,65 +391,68 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
                G.g0.num >= 2 && reg_count >= (size_t)tune_int("SZ_HIP_FEED_MIN_REG", 65536);
 #ifndef SZH_SYNC_LAUNCH
         feed = feed && (G.d0 % 128) == 0;      // (a plane = whole cache lines of values, flags and codes: a line is never loaded while part of it is still to come)
-#endif
-#ifndef SZH_SYNC_LAUNCH
         if (feed) { TRY(probe_streams(ctx)); feed = ctx->streams_independent == 1; }
 #endif
         if (feed) feed = fed_guard.try_raise();      // (no other lone context's call may join this one half-way: szhip.hip, fed_call_guard)
         TRY(ensure_pinned3(ctx, reg_count * 4 * sizeof(T) + (overlap ? ((size_t)nb + 64) * 4 * sizeof(T) + 256 : 0)));
         hcoef = (T *)ctx->pinned3;
+        return SZHIP_OK;
+    }
+    // ---- the coefficients to the host and the chains started: on threads of this call beside k_pencil (`overlap`), else on the context's pool -- beside the fed
+    //      sweep (`feed`), or finished here and scattered back to the device
+    int run_chains() {
         // (round 5, with the fed sweep) the chains start on the FIRST 32768 coefficients of every array while the rest is still on its way (4.8 MB at the
         // 512^3 M-field: 0.1 ms): chain_avail says how many have arrived, a chain that runs into the mark waits (szhost_coeff_chain_one_pa)
         chain_avail = reg_count;
-        struct AvailAll {      // (no return path may leave a chain waiting for coefficients that never come: destroyed before join_sections waits for the chains)
+        struct AvailAll {      // (no return path may leave a chain waiting for coefficients that never come: released when this phase ends, before anything waits for the chains)
             size_t *p; size_t v;
             ~AvailAll() { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
         } avail_all{&chain_avail, reg_count};
         const size_t first_piece = (size_t)std::max(1, tune_int("SZ_HIP_CHAIN_EARLY_PIECE", 32768));
-        const bool two_pieces = feed && reg_count >= 4 * first_piece;
+        two_pieces = feed && reg_count >= 4 * first_piece;
         if (two_pieces) {
             for (int e = 0; e < 4; ++e)
                 HIPCHK(hipMemcpyAsync(hcoef + (size_t)e * reg_count, (const T *)ctx->coef_compact.p + (size_t)e * reg_count, first_piece * sizeof(T), hipMemcpyDeviceToHost, st));
             HIPCHK(hipEventRecord(ctx->ev_sec, st));
             for (int e = 0; e < 4; ++e)
-                HIPCHK(hipMemcpyAsync(hcoef + (size_t)e * reg_count + first_piece, (const T *)ctx->coef_compact.p + (size_t)e * reg_count + first_piece,
-                                      (reg_count - first_piece) * sizeof(T), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(hcoef + (size_t)e * reg_count + first_piece, (const T *)ctx->coef_compact.p + (size_t)e * reg_count + first_piece, (reg_count - first_piece) * sizeof(T), hipMemcpyDeviceToHost, st));
             chain_avail = 0;
             HIPCHK(hipEventSynchronize(ctx->ev_sec));
             __atomic_store_n(&chain_avail, first_piece, __ATOMIC_RELEASE);
         } else {
-        HIPCHK(hipMemcpyAsync(hcoef, ctx->coef_compact.p, reg_count * 4 * sizeof(T), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpyAsync(hcoef, ctx->coef_compact.p, reg_count * 4 * sizeof(T), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
         }
         TP("coef on host");
         double h0 = now_ms();
         all_reg_keep.assign(reg_count, 0);
         TP("chain begin");
-        const std::vector<unsigned char> &all_reg = all_reg_keep;
+        const unsigned char *const ind = all_reg_keep.data();
         // 2-D planes are carried as {0, a, b, c}: the chain sees components 1..3
         T *const chain_in = hcoef + (two_d ? reg_count : 0);
-        szhost_coeff_chain_begin(is_double, all_reg.data(), reg_count, (double)eb, G.g0.late, G.g1.late, G.g2.late, ncoef, &cf);
-        {   // the chains write into the context's arrays (touched in earlier calls) instead of freshly allocated ones
-            if (ctx->chain_codes.size() < reg_count * 4) ctx->chain_codes.resize(reg_count * 4 + reg_count / 4);
-            if (ctx->chain_unpred.size() < reg_count * 4 * sizeof(T)) ctx->chain_unpred.resize((reg_count * 4 + reg_count / 4) * sizeof(T));
-            for (int e = 0; e < 4; ++e) {
-                free(cf.codes[e]); free(cf.unpred[e]);
-                cf.codes[e] = ctx->chain_codes.data() + (size_t)e * reg_count;
-                cf.unpred[e] = ctx->chain_unpred.data() + (size_t)e * reg_count * sizeof(T);
-            }
-            join_sections.own = true;
+        szhost_coeff_chain_begin(is_double, ind, reg_count, (double)eb, G.g0.late, G.g1.late, G.g2.late, ncoef, &cf);
+        // the chains write into the context's arrays (touched in earlier calls) instead of freshly allocated ones
+        if (ctx->chain_codes.size() < reg_count * 4) ctx->chain_codes.resize(reg_count * 4 + reg_count / 4);
+        if (ctx->chain_unpred.size() < reg_count * 4 * sizeof(T)) ctx->chain_unpred.resize((reg_count * 4 + reg_count / 4) * sizeof(T));
+        for (int e = 0; e < 4; ++e) {
+            free(cf.codes[e]); free(cf.unpred[e]);
+            cf.codes[e] = ctx->chain_codes.data() + (size_t)e * reg_count;
+            cf.unpred[e] = ctx->chain_unpred.data() + (size_t)e * reg_count * sizeof(T);
         }
+        cf_own = true;
         // (threads also for a handful of regression blocks: a section's fixed cost -- a 131 072-state code book -- is ~0.5 ms, and
         //  four of them in line delayed the wavefront kernel of BASELINE configs[3] by 2 ms)
         if (overlap) {
             // The chain runs NEXT TO the wavefront kernel: the threads publish how far they are, the kernel is launched right away and
             // makes a pencil that touches a regression block wait until the blocks it reads are final, and this thread ships the decoded
-            // coefficients as they appear (after the launch, below).  blk_of_rank: scan-order block index of the r-th regression block.
+            // coefficients as they appear (ship_coefs).  blk_of_rank: scan-order block index of the r-th regression block.
             blk_of_rank.resize(reg_count);
-            { size_t r = 0; for (int64_t bb = 0; bb < nb && r < reg_count; ++bb) if (!((ind_bits[bb >> 3] >> (7 - (bb & 7))) & 1)) blk_of_rank[r++] = (uint32_t)bb; if (r != reg_count) FAIL(SZHIP_ERR_INTERNAL, "indicator bits and regression-block count disagree"); }
+            size_t r = 0;
+            for (int64_t bb = 0; bb < nb && r < reg_count; ++bb) if (!is_lorenzo(bb)) blk_of_rank[r++] = (uint32_t)bb;
+            if (r != reg_count) FAIL(SZHIP_ERR_INTERNAL, "indicator bits and regression-block count disagree");
             for (int e = 0; e < 4; ++e) chain_done[e] = 0;
             for (int e = 0; e < ncoef; ++e)
-                section_threads.emplace_back([&, e, chain_in, ind = all_reg_keep.data()] {
+                section_threads.emplace_back([this, e, chain_in, ind] {
                     szhost_coeff_chain_one_p(is_double, chain_in, ind, reg_count, use_mean, e, &cf, &chain_done[e]);
                     make_section(e);
                 });
@@ -347,13 +461,11 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
             pool_busy = true;
             for (int e = 0; e < 4; ++e) chain_done[e] = feed && e >= ncoef ? reg_count : 0;
             const size_t *const avail_ptr = two_pieces ? &chain_avail : nullptr;
-            ctx->chain_pool->submit(ncoef,
-                [&, chain_in, ind = all_reg.data(), avail_ptr](int e) {
+            ctx->chain_pool->submit(ncoef, [this, chain_in, ind, avail_ptr](int e) {
                     chain_t0[e] = now_ms() - t_begin;
                     szhost_coeff_chain_one_pa(is_double, chain_in, ind, reg_count, use_mean, e, &cf, feed ? &chain_done[e] : nullptr, avail_ptr);
                     chain_t1[e] = now_ms() - t_begin;
-                },
-                [&](int e) { make_section(e); });
+                }, [this](int e) { make_section(e); });
             if (two_pieces) {                          // the rest of the coefficients: the chains are at work meanwhile
                 HIPCHK(hipStreamSynchronize(st));
                 __atomic_store_n(&chain_avail, reg_count, __ATOMIC_RELEASE);
@@ -365,105 +477,89 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         if (tp_on) fprintf(stderr, "chain threads: %.2f-%.2f %.2f-%.2f %.2f-%.2f %.2f-%.2f | ", chain_t0[0], chain_t1[0], chain_t0[1], chain_t1[1], chain_t0[2], chain_t1[2], chain_t0[3], chain_t1[3]);
         if (!overlap && !feed) {
             HIPCHK(hipMemcpyAsync(ctx->coef_compact.p, hcoef, reg_count * 4 * sizeof(T), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_move_coef<T, 1>), dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor,
-                               (const u64 *)ctx->reg_rank.p, nb, (int64_t)reg_count, d_coef, (T *)ctx->coef_compact.p);
+            hipLaunchKernelGGL((k_move_coef<T, 1>), dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_lor, (const u64 *)ctx->reg_rank.p, nb, (int64_t)reg_count, d_coef, (T *)ctx->coef_compact.p);
             HIPCHK(hipGetLastError());
         }
+        return SZHIP_OK;
     }
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-    TP("ev1");
-
-    // ---- predict + quantise: the wavefront kernel
-    // (the ribbon mapping writes its codes in its own order, szh_ribbon.h: tiles x steps x 1024 entries, a few per cent more than n)
-    // Which sweep: arrays with regression blocks and doubles take the beam (k_pencil's 4.4 / 7.4 ms become 1.2 / 2.3 at 512^3 M-field / the f64 slab);
-    // a float array whose blocks all chose Lorenzo stays on k_ribbon when that applies -- alone the two sweeps take the same time (1.05 against
-    // 1.03 - 1.13 ms at 512^3), and k_ribbon's finished tile rows feed the entropy stage while it runs (one call 1.95 against 2.08 ms).
-    // SZ_HIP_BEAM=2 sends everything the beam covers to it.
-    // (round 6: the beam, 0.69 ms at 512^3 float against k_ribbon's 1.13, takes everything it covers; SZ_HIP_BEAM=0 switches it off)
-    const bool beam_first = true;
-    const bool use_beam = !overlap && beam_first && beam_applies<T>(G, d_in, reg_count);
-    // (round 6) the packing passes read the sweep's natural-order codes themselves, segment by segment (szh_segenc.h): no block-ordered copy, no k_permute /
-    // k_unpred, no cleared stream buffer.  Every 3-D array whose codes leave the sweep in natural order (beam, pencil); whether the code book fits its kernels
-    // is known once the tree is built -- if not, the block-ordering pass runs then, unsliced, and the older passes follow.  SZ_HIP_SEGENC=0: as in round 5.
-    // Not for a sweep that is fed while the host's coefficient chains run (the 512^3 M-field): that sweep takes 1.8 ms, the older passes' slices hide beside it, and one
-    // call measured 3.04 ms with them against 3.18 with these (SZ_HIP_SEGENC=2 takes them there too).
-    const int segenc_sw = tune_int("SZ_HIP_SEGENC", 1);
-    bool segenc = !two_d && G.ndim == 3 && segenc_sw != 0 && (!feed || segenc_sw == 2);
-    // segments of `se_segb` blocks of a block column: their rows, the code table and the bit window (sized here for the longest code words the kernel takes, 32 bits)
-    // share the workgroup's LDS.  A tile of 14 KB: k_col_encode needs 75 registers (six wavefronts per SIMD), so the LDS a workgroup takes decides how many columns a CU
-    // works on at once -- 512^3, segments of 29 / 22 / 17 / 15 / 11 blocks: 0.251 / 0.220 / 0.206 / 0.224 / 0.253 ms (profiles/r07_packing_rounds.txt)
-    const int se_vw = (G.g2.count % 8) == 0 ? 8 : ((G.g2.count % 4) == 0 ? 4 : 1);
-    int se_segb = 0, se_nseg = 0, se_nrmax = szh_se::NR; size_t se_tile = 0;
-    if (segenc) {
-        bool ok = intervals < 65536 && (double)n < 4.0e9;            // (k_col_encode keeps a row's element offset in 32 bits)
-        // every block holds at least 32 codes, so a column's first round (all runs of its first segment, or 256 threads' worth) holds at least 32 code words and
-        // never ends inside the column's leading partial word; k_col_encode tells a word shared with the column before by its position all the same.  (3-D arrays of a
-        // 2 x 2 cross-section are the only ones this sends to the older passes: a dimension of 1 never comes here.)
-        if ((int64_t)G.g0.late * G.g1.late * G.g2.late < 32) ok = false;
-        const size_t fixed = ((size_t)intervals + 1) * 8 + 16 + szh_se::seg_window_words(G, 32) * 4 + 64;
-        const size_t lds_cap = (size_t)63 * 1024, want = (size_t)std::max(4, tune_int("SZ_HIP_SEG_TILE_KB", 14)) * 1024;
-        if (ok && fixed + szh_se::seg_tile_bytes(G, 1, se_vw) > lds_cap) ok = false;
-        if (ok) {
-            const size_t budget = std::min(lds_cap - fixed, std::max(want, szh_se::seg_tile_bytes(G, 1, se_vw)));
-            int sb = 1;
-            while (sb < G.g2.num && szh_se::seg_tile_bytes(G, sb + 1, se_vw) <= budget && szh_se::seg_pieces_per_thread(G, sb + 1, se_vw) <= (size_t)szh_se::PF) ++sb;
-            // segments of equal size, as few as the tile allows: no short segment at the end that pays a whole round's barriers, scan and tile load for a handful of runs
-            sb = (G.g2.num + (G.g2.num + sb - 1) / sb - 1) / ((G.g2.num + sb - 1) / sb);
-            if (const int f = tune_int("SZ_HIP_SEG_SEGB", 0)) sb = std::max(1, std::min(f, sb));
-            se_segb = sb;
-            se_nseg = (G.g2.num + se_segb - 1) / se_segb;
-            se_tile = szh_se::seg_tile_bytes(G, se_segb, se_vw);
-            // a round of k_col_encode is 256 threads x up to `se_nrmax` runs (the window is sized for that many): the usual block column's segment in as few rounds as
-            // NR allows, its runs spread evenly over them; a column of more rows takes more rounds
-            const int rows_typ = (2 * G.g0.split > G.g0.num ? G.g0.early : G.g0.late) * (2 * G.g1.split > G.g1.num ? G.g1.early : G.g1.late);
-            const int runs_typ = std::max(1, sb * rows_typ), rounds_typ = (runs_typ + 256 * szh_se::NR - 1) / (256 * szh_se::NR);
-            se_nrmax = std::max(1, std::min(szh_se::NR, (runs_typ + 256 * rounds_typ - 1) / (256 * rounds_typ)));
-            if ((double)G.g0.num * G.g1.num >= 2.0e9) ok = false;
+    // the feed of the beam sweep (prepare_chains): slices of block rows; a slice goes out when every chain has passed its last regression block
+    int feed_slices(const szh_qargs<T> &a) {
+        const double h1 = now_ms();
+        const int NF = std::max(2, std::min(G.g0.num, 12));
+        const int64_t per_row = (int64_t)G.g1.num * G.g2.num;
+        size_t r_lo = 0; int b0_lo = 0;
+        for (int sl = 0; sl < NF; ++sl) {
+            const int b0_hi = sl == NF - 1 ? G.g0.num : std::max(b0_lo, (int)((int64_t)G.g0.num * (sl + 1) / NF));
+            if (b0_hi == b0_lo && sl != NF - 1) continue;
+            // regression blocks in block rows below b0_hi
+            size_t r_hi = reg_count;
+            if (b0_hi < G.g0.num) r_hi = r_lo + ((size_t)(b0_hi - b0_lo) * per_row - count_lorenzo(b0_lo * per_row, b0_hi * per_row));
+            unsigned idle = 0;
+            while (chains_done() < r_hi) {
+                szhip_chain_pool::pause();
+                if (++idle > (1u << 28)) FAIL(SZHIP_ERR_INTERNAL, "coefficient chain made no progress");
+            }
+            const int planes_end = b0_hi >= G.g0.num ? G.g0.count : szh_blk_start(G.g0, b0_hi);
+            // (2-D never comes here; the compact arrays are [4][reg_count], the chains decoded them in place)
+            TRY((feed_beam_slice<T>(ctx, G, a, ctx->stream2, hcoef, reg_count, r_lo, r_hi, b0_lo, b0_hi, planes_end, (const u64 *)ctx->reg_rank.p, nb)));
+            r_lo = r_hi; b0_lo = b0_hi;
         }
-        segenc = ok;
+        host_ms += now_ms() - h1;
+        S.chain_overlapped = 2;
+        return SZHIP_OK;
     }
-    // small alphabets: the histogram pass keeps a histogram per block column (k_col_hist), from which the columns' bit counts follow without another pass over the codes
-    int sh_rshift = 0;
-    bool seghist = segenc && intervals <= SZH_COL_HBINS && tune_int("SZ_HIP_SEGHIST", 1) != 0;
-    if (seghist) { const size_t one = (size_t)intervals * 4; while (sh_rshift < 6 && (one << (sh_rshift + 1)) <= 16 * 1024) ++sh_rshift; }
-    // (SZ_HIP_DEV_BOOK=1, off by default) the code book on the device (szh_book.h): a Lorenzo-only array that takes the packing passes above, their two scans in
-    // one launch -- nothing of its entropy stage waits for the host; a book the kernel declines sends the call round again with the host's (with_ticket_fallback)
-    const size_t bk_front = meta_len + 8 + 4 + sizeof(T), bk_mid = 1 + sizeof(T);
-    const bool dev_book = segenc && reg_count == 0 && !ctx->no_dev_book && tune_int("SZ_HIP_DEV_BOOK", 0) != 0 && ncols <= 1024 * SZH_COL_SCAN_PER &&
-                          tune_int("SZ_HIP_SEG_SCAN1", 1) != 0 && bk_front + bk_mid <= 3072;
-    const size_t nat_elems = (size_t)n;
-    TRY(ensure(ctx, ctx->codes_nat, nat_elems * 2 + 64));
-    TRY(ensure(ctx, ctx->codes_blk, (size_t)n * 2 + 64));
-    uint16_t *d_nat = (uint16_t *)ctx->codes_nat.p, *d_blk = (uint16_t *)ctx->codes_blk.p;
-    int nI, nJ, ntiles;
-    using TS = szh_tile_shape<T>;
-    TRY(prepare_pencil(ctx, G, szh_gran<T>::NW, TS::TPI, TS::TPJ, &nI, &nJ, &ntiles));
-    // The entropy stage's two passes over the code array (histogram, block ordering) start on FINISHED TILE ROWS while the sweep is still
-    // running (round 4): the sweep's last tile row ends ~35 % after its first one (the tile rows follow each other down dim 0), and the
-    // sweep keeps the CUs busy with one workgroup each.  k_ribbon publishes every finished tile in host-coherent memory (a.tile_done);
-    // this thread watches the words and launches the passes of slice after slice on two other streams.  SZ_HIP_SLICES=1: everything
-    // after the sweep, as before.
-    // A lane of a pool (several arrays in flight) takes two slices (SZ_HIP_SLICES_POOL; with the passes of the start of round 4 the lanes lost by
-    // slicing -- two lanes at 512^3: 338 GB/s without, 324 with eight slices --, with the lighter passes of its end they gain: 349 -> 356).
-    // Measured (round 4, 512^3 float, one call after the other, same box): 255 GB/s with 1 slice, 276 with 4, 251 - 275 with 8 (the slices'
-    // kernels take 2 - 4 x their lone time beside the sweep and slow it by ~0.1 ms; more slices, more of that).
-    const int slices_req = tune_int("SZ_HIP_SLICES", ctx->gate ? tune_int("SZ_HIP_SLICES_POOL", 2) : 4);
-    // (round 5) the beam sweep: every wavefront publishes how many of its lines have their codes in memory (szh_beam.h, `tile_done`: a word per
-    // wavefront, written every 32 lines after write-through code stores and a vmcnt(0) -- a system-scope RELEASE per word cost ~35 us
-    // each and took the sweep from 1.05 to 1.58 ms); a slice = the block rows whose lines every wavefront has passed.  Measured at 512^3, one call:
-    // S-field 2.12 ms unsliced, 1.94 - 1.96 with 3 - 6 slices; M-field 3.94 -> 3.82 (profiles/r05_beam_slices.txt).
-    const bool sliced = use_beam && slices_req > 1 && !seghist;
-    unsigned *tile_done = nullptr;
-    const szh_bm::grid_t bgrid = szh_bm::make_grid(G);
-    const size_t beam_words = (size_t)bgrid.nKB * bgrid.nJG * szh_bm::WPG;
-    if (sliced) {
-        const size_t tiles = beam_words;
-        TRY(ensure_coherent(ctx, 512 + tiles * 4));
-        tile_done = (unsigned *)((char *)ctx->coh + 512);
-        if (!ctx->stream3) HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
-        if (!ctx->ev_perm) HIPCHK(hipEventCreateWithFlags(&ctx->ev_perm, hipEventDisableTiming));
+    // `overlap`: ship the decoded coefficients while k_pencil runs: DMA only (no kernel that could queue behind the waiting tiles), on the
+    // second stream, in scan order: the values of the newly finished regression blocks go into a block-indexed pinned staging
+    // array, the contiguous block range [first, last] of each coefficient into `dec`, then the progress word (same stream: it
+    // lands after the data).  Blocks between regression blocks are Lorenzo blocks: whatever they receive is never read.
+    int ship_coefs(unsigned epoch, szh_u64 *coh_prog, T *dec, int64_t nbp) {
+        const double h1 = now_ms();
+        const szh_u64 tag = (szh_u64)(epoch & 0xffffffu) << 40;
+        T *const full = (T *)(((uintptr_t)(hcoef + reg_count * 4) + 127) & ~(uintptr_t)127);     // pinned staging, [4][nbp] block-indexed
+        const size_t chunk = std::max<size_t>(2048, reg_count / 32);
+        size_t shipped = 0; int64_t sent = 0;                 // ranks scattered into the staging array; blocks [0, sent) are on the device
+        int idle = 0;
+        while (sent < nb) {
+            const size_t p = chains_done();
+            if (p > shipped && (p - shipped >= chunk || p == reg_count)) {
+                for (int e = 0; e < ncoef; ++e)
+                    for (size_t r = shipped; r < p; ++r) full[(size_t)e * nbp + blk_of_rank[r]] = hcoef[(size_t)e * reg_count + r];
+                shipped = p;
+                // every block below `fin` is final; whole lines of them travel
+                const int64_t fin = p == reg_count ? nb : (int64_t)blk_of_rank[p];
+                const int64_t upto = fin == nb ? nb : fin / LINE * LINE;
+                if (upto > sent) {
+                    for (int e = 0; e < ncoef; ++e)
+                        HIPCHK(hipMemcpyAsync(dec + (size_t)e * nbp + sent, full + (size_t)e * nbp + sent, (size_t)(upto - sent) * sizeof(T), hipMemcpyHostToDevice, ctx->stream2));
+                    HIPCHK(hipStreamSynchronize(ctx->stream2));            // the values are in device memory ...
+                    __atomic_store_n(coh_prog, tag | (szh_u64)upto, __ATOMIC_RELEASE);   // ... before the kernel may look for them
+                    sent = upto;
+                }
+                idle = 0;
+            } else if (++idle > 200000) FAIL(SZHIP_ERR_INTERNAL, "coefficient chain made no progress");
+            else std::this_thread::sleep_for(std::chrono::microseconds(10));
+        }
+        host_ms += now_ms() - h1;
+        S.chain_overlapped = 1;
+        TP("coefficients shipped");
+        return SZHIP_OK;
     }
-    {
+    // ---- predict + quantise: the sweep (beam or k_pencil), and what feeds it while it runs
+    int launch_sweep() {
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
+        TRY(ensure(ctx, ctx->codes_blk, (size_t)n * 2 + 64));
+        d_nat = (uint16_t *)ctx->codes_nat.p; d_blk = (uint16_t *)ctx->codes_blk.p;
+        int nI, nJ, ntiles;
+        using TS = szh_tile_shape<T>;
+        TRY(prepare_pencil(ctx, G, szh_gran<T>::NW, TS::TPI, TS::TPJ, &nI, &nJ, &ntiles));
+        const szh_bm::grid_t bgrid = szh_bm::make_grid(G);
+        beam_words = (size_t)bgrid.nKB * bgrid.nJG * szh_bm::WPG;
+        if (P.sliced) {
+            TRY(ensure_coherent(ctx, 512 + beam_words * 4));
+            tile_done = (unsigned *)((char *)ctx->coh + 512);
+            if (!ctx->stream3) HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
+            if (!ctx->ev_perm) HIPCHK(hipEventCreateWithFlags(&ctx->ev_perm, hipEventDisableTiming));
+        }
         szh_qargs<T> a; memset(&a, 0, sizeof(a));
         a.tile_done = tile_done; a.pub_lines = 32;
         a.G = G; a.data = d_in; a.out = nullptr; a.codes = d_nat; a.blk_lor = d_lor; a.coef = d_coef; a.coef_stride = nb;
@@ -475,7 +571,6 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         a.coef_progress = nullptr;
         szh_u64 *coh_prog = nullptr;
         T *dec = nullptr;                                          // the decoded coefficients as the kernel reads them
-        constexpr int64_t LINE = 128 / (int64_t)sizeof(T);         // values per 128-byte cache line
         const int64_t nbp = (nb + LINE - 1) / LINE * LINE;         // a coefficient's array starts on a line boundary
         if (overlap) {
             // Hand-off between the host's chain and the running kernel (per-XCD L2s are not coherent, and DMA writes do not touch them):
@@ -494,167 +589,92 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
             a.coef = dec; a.coef_stride = nbp;
         }
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (use_beam) {
-            // the feed (see above): slices of block rows; a slice goes out when every chain has passed its last regression block
-            auto feed_slices = [&]() -> int {
-                const double h1 = now_ms();
-                const int NF = std::max(2, std::min(G.g0.num, 12));
-                const int64_t per_row = (int64_t)G.g1.num * G.g2.num;
-                size_t r_lo = 0; int b0_lo = 0;
-                for (int sl = 0; sl < NF; ++sl) {
-                    const int b0_hi = sl == NF - 1 ? G.g0.num : std::max(b0_lo, (int)((int64_t)G.g0.num * (sl + 1) / NF));
-                    if (b0_hi == b0_lo && sl != NF - 1) continue;
-                    // regression blocks in block rows below b0_hi (the indicator bits are in scan order: dim 0 outermost; a zero bit = regression)
-                    size_t r_hi = reg_count;
-                    if (b0_hi < G.g0.num) {
-                        int64_t bb = (int64_t)b0_lo * per_row; const int64_t b_end = (int64_t)b0_hi * per_row;
-                        size_t ones = 0; const int64_t span = b_end - bb;
-                        for (; bb < b_end && (bb & 7); ++bb) ones += (ind_bits[bb >> 3] >> (7 - (bb & 7))) & 1;
-                        for (; bb + 64 <= b_end; bb += 64) { uint64_t w8; memcpy(&w8, ind_bits + (bb >> 3), 8); ones += (size_t)__builtin_popcountll(w8); }
-                        for (; bb < b_end; ++bb) ones += (ind_bits[bb >> 3] >> (7 - (bb & 7))) & 1;
-                        r_hi = r_lo + ((size_t)span - ones);
-                    }
-                    unsigned idle = 0;
-                    for (;;) {
-                        size_t p = reg_count;
-                        for (int e = 0; e < ncoef; ++e) { const size_t d = __atomic_load_n(&chain_done[e], __ATOMIC_ACQUIRE); if (d < p) p = d; }
-                        if (p >= r_hi) break;
-                        szhip_chain_pool::pause();
-                        if (++idle > (1u << 28)) FAIL(SZHIP_ERR_INTERNAL, "coefficient chain made no progress");
-                    }
-                    const int planes_end = b0_hi >= G.g0.num ? G.g0.count : szh_blk_start(G.g0, b0_hi);
-                    // (2-D never comes here; the compact arrays are [4][reg_count], the chains decoded them in place)
-                    TRY((feed_beam_slice<T>(ctx, G, a, ctx->stream2, hcoef, reg_count, r_lo, r_hi, b0_lo, b0_hi, planes_end, (const u64 *)ctx->reg_rank.p, nb)));
-                    r_lo = r_hi; b0_lo = b0_hi;
-                }
-                host_ms += now_ms() - h1;
-                S.chain_overlapped = 2;
-                return SZHIP_OK;
-            };
+        if (P.use_beam) {
 #ifdef SZH_SYNC_LAUNCH
             // (the CPU shim runs a launch to its end before the next one starts: the slices first, then a sweep that finds every plane there)
             if (feed) {
                 TRY(ensure(ctx, ctx->pt_flags, (size_t)G.n + 64)); TRY(ensure(ctx, ctx->rb_vals, (size_t)G.n * sizeof(T) + 64)); TRY(ensure(ctx, ctx->feed_word, 256));
                 HIPCHK(hipMemsetAsync(ctx->pt_flags.p, 0, (size_t)G.n, st));
-                TRY(feed_slices());
+                TRY(feed_slices(a));
                 TRY((launch_beam<T, false>(ctx, G, a, st, reg_count, true)));
             } else
 #endif
             TRY((launch_beam<T, false>(ctx, G, a, st, reg_count, feed)));
             S.quant_kernel = 2;
 #ifndef SZH_SYNC_LAUNCH
-            if (feed) TRY(feed_slices());
+            if (feed) TRY(feed_slices(a));
 #endif
-        }
-        else {
-        const unsigned pgrid = pencil_grid(ctx, a, ntiles);
-        hipLaunchKernelGGL((k_pencil<T, false>), dim3(pgrid), dim3((TS::TPI * TS::TPJ + 2) * 64), 0, st, a);
-        HIPCHK(hipGetLastError());
+        } else {
+            const unsigned pgrid = pencil_grid(ctx, a, ntiles);
+            hipLaunchKernelGGL((k_pencil<T, false>), dim3(pgrid), dim3((TS::TPI * TS::TPJ + 2) * 64), 0, st, a);
+            HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(ctx->ev[3], st));
         TP("pencil launched");
         S.quant_kernel_launches = 1;
-        if (overlap) {
-            // ship the decoded coefficients while the kernel runs: DMA only (no kernel that could queue behind the waiting tiles), on the
-            // second stream, in scan order: the values of the newly finished regression blocks go into a block-indexed pinned staging
-            // array, the contiguous block range [first, last] of each coefficient into d_coef, then the progress word (same stream: it
-            // lands after the data).  Blocks between regression blocks are Lorenzo blocks: whatever they receive is never read.
-            const double h1 = now_ms();
-            const szh_u64 tag = (szh_u64)(a.epoch & 0xffffffu) << 40;
-            T *const full = (T *)(((uintptr_t)(hcoef + reg_count * 4) + 127) & ~(uintptr_t)127);     // pinned staging, [4][nbp] block-indexed
-            const size_t chunk = std::max<size_t>(2048, reg_count / 32);
-            size_t shipped = 0; int64_t sent = 0;                 // ranks scattered into the staging array; blocks [0, sent) are on the device
-            int idle = 0;
-            while (sent < nb) {
-                size_t p = reg_count;
-                for (int e = 0; e < ncoef; ++e) { const size_t d = __atomic_load_n(&chain_done[e], __ATOMIC_ACQUIRE); if (d < p) p = d; }
-                if (p > shipped && (p - shipped >= chunk || p == reg_count)) {
-                    for (int e = 0; e < ncoef; ++e)
-                        for (size_t r = shipped; r < p; ++r) full[(size_t)e * nbp + blk_of_rank[r]] = hcoef[(size_t)e * reg_count + r];
-                    shipped = p;
-                    // every block below `fin` is final; whole lines of them travel
-                    const int64_t fin = p == reg_count ? nb : (int64_t)blk_of_rank[p];
-                    const int64_t upto = fin == nb ? nb : fin / LINE * LINE;
-                    if (upto > sent) {
-                        for (int e = 0; e < ncoef; ++e)
-                            HIPCHK(hipMemcpyAsync(dec + (size_t)e * nbp + sent, full + (size_t)e * nbp + sent, (size_t)(upto - sent) * sizeof(T), hipMemcpyHostToDevice, ctx->stream2));
-                        HIPCHK(hipStreamSynchronize(ctx->stream2));            // the values are in device memory ...
-                        __atomic_store_n(coh_prog, tag | (szh_u64)upto, __ATOMIC_RELEASE);   // ... before the kernel may look for them
-                        sent = upto;
-                    }
-                    idle = 0;
-                } else if (++idle > 200000) FAIL(SZHIP_ERR_INTERNAL, "coefficient chain made no progress");
-                else std::this_thread::sleep_for(std::chrono::microseconds(10));
-            }
-            host_ms += now_ms() - h1;
-            S.chain_overlapped = 1;
-            TP("coefficients shipped");
-        }
+        if (overlap) TRY(ship_coefs(a.epoch, coh_prog, dec, nbp));
+        return SZHIP_OK;
     }
-
-    // ---- histogram, block ordering, unpredictable counts
-    // The histogram (and its copy to the host) runs on the second stream next to the block-ordering pass, so the host builds
-    // the code book while k_permute is still running.
-    TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
-    unsigned *d_hist = (unsigned *)ctx->hist.p;
-    TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
-    unsigned *h_hist = (unsigned *)ctx->pinned;
-    auto launch_hist = [&](const uint16_t *codes) -> int {
+    // the histogram of the whole code array (and its copy to the host) on the second stream, next to the block-ordering pass: the host builds the code book while
+    // k_permute is still running.  (The histogram inside k_permute instead measured equal in kernel time -- 393 against 322 + 69 us -- and lost the overlap.)
+    int launch_hist() {
         HIPCHK(hipEventRecord(ctx->ev_in, st));                    // codes complete
         HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, ctx->stream2));
-        int rshift = 0; int use_lds = intervals <= 16384;
-        if (use_lds) { while ((intervals << (rshift + 1)) <= 16384u && rshift < 6) ++rshift; }
+        const int use_lds = intervals <= 16384, rshift = use_lds ? hist_rshift(intervals, 16384) : 0;
         const size_t lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
-        const int64_t nh = n;
-        int grid = (int)std::min<int64_t>((nh / 8 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), lds, ctx->stream2, codes, nh, intervals, rshift, use_lds, d_hist, (int64_t)0);
+        int grid = (int)std::min<int64_t>((n / 8 + 255) / 256 + 1, 2048);
+        hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), lds, ctx->stream2, (const uint16_t *)d_nat, n, intervals, rshift, use_lds, d_hist, (int64_t)0);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, ctx->stream2));
         HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
         return SZHIP_OK;
-    };
-    // (the histogram inside k_permute instead measured equal in kernel time -- 393 against 322 + 69 us -- and lost the overlap)
-    if (seghist) {
-        // (behind the sweep, on its stream: beside it the pass took from the sweep what it saved behind it -- 512^3: sweep 0.70 -> 0.76 ms with four slices of the older histogram)
-        TRY(ensure(ctx, ctx->seg_hist, (size_t)ncols * intervals * 4));
-        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
-        hipLaunchKernelGGL(k_col_hist, dim3((unsigned)ncols), dim3(256), ((size_t)intervals * 4) << sh_rshift, st, G, (const uint16_t *)d_nat, intervals, sh_rshift, se_vw, (unsigned *)ctx->seg_hist.p);
-        hipLaunchKernelGGL(k_hist_reduce, dim3((unsigned)std::min<int64_t>(64, ncols)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, intervals, (int64_t)ncols, d_hist);
+    }
+    // k_permute's tile: blocks per segment, segments per column, the zero-code lists per segment, the dynamic LDS
+    int prepare_permute() {
+        perm_segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
+        perm_nseg = (G.g2.num + perm_segb - 1) / perm_segb;
+        TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * perm_nseg * 4));
+        TRY(ensure(ctx, ctx->zpos, (size_t)ncols * perm_nseg * SZH_ZCAP * 4));
+        const size_t tile_el = (tile_bytes(G, perm_segb, 2) + 1) / 2;
+        perm_lds = ((tile_el + 1) & ~(size_t)1) * 2 + 16;
+        return SZHIP_OK;
+    }
+    // the block-ordering pass over block columns [col0, col0 + cols) on stream `s_`
+    void launch_permute(hipStream_t s_, int col0, int cols) {
+        hipLaunchKernelGGL((k_permute<0>), dim3((unsigned)cols, std::min(perm_nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), perm_lds, s_, G, (const uint16_t *)d_nat, d_blk,
+                           (unsigned *)ctx->col_zeros.p, perm_segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, col0);
+    }
+    // the columns' zero-code counts -> where each column's unpredictable values start
+    int scan_col_zeros(hipStream_t s_) {
+        hipLaunchKernelGGL(k_u32_to_u64, dim3((ncols + 255) / 256), dim3(256), 0, s_, (const unsigned *)ctx->col_zeros.p, (int64_t)ncols, (u64 *)ctx->col_zeros64.p);
+        return scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, ncols, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED, s_);
+    }
+    // the block-ordering pass over the whole array, on the first stream (arrays whose sweep feeds no slices; with segenc: only if the code book turns out not to fit its kernels)
+    int permute_all() {
+        HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, st));
+        TRY(prepare_permute());
+        launch_permute(st, 0, ncols);
         HIPCHK(hipGetLastError());
-        if (!dev_book) {
-        HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(ctx->ev_fit, st));
-        }
-    } else
-    if (!sliced) TRY(launch_hist((const uint16_t *)d_nat));    // next to the block-ordering pass (ribbon order: padding skipped by geometry)
-    TRY(ensure(ctx, ctx->col_zeros, (size_t)ncols * 4));
-    TRY(ensure(ctx, ctx->col_zeros64, (size_t)ncols * 8));
-    TRY(ensure(ctx, ctx->col_off, (size_t)ncols * 8));
-    int perm_segb = 1, perm_nseg = 1;
-    if (sliced && use_beam) {
-        // slices of block rows (dim 0): the codes are in natural order, so a slice's codes are ONE contiguous range for the histogram, and the
-        // block-ordering pass takes the slice's block rows.  A slice starts when every wavefront of the sweep has published its lines.
-        const int NS = std::min(slices_req, G.g0.num);
-        const int segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
-        const int nseg = (G.g2.num + segb - 1) / segb;
-        TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * nseg * 4));
-        TRY(ensure(ctx, ctx->zpos, (size_t)ncols * nseg * SZH_ZCAP * 4));
-        const size_t tb = tile_bytes(G, segb, 2), tile_el = (tb + 1) / 2;
-        int rshift = 0; const int use_lds = intervals <= 16384;
-        if (use_lds) { while ((intervals << (rshift + 1)) <= 16384u && rshift < 6) ++rshift; }
+        return scan_col_zeros(st);
+    }
+    // slices of block rows (dim 0) beside the running beam sweep: the codes are in natural order, so a slice's codes are ONE contiguous range for the histogram, and the
+    // block-ordering pass takes the slice's block rows.  A slice starts when every wavefront of the sweep has published its lines.
+    int hist_and_order_sliced() {
+        const int NS = std::min(P.slices_req, G.g0.num);
+        TRY(prepare_permute());
+        const int use_lds = intervals <= 16384, rshift = use_lds ? hist_rshift(intervals, 16384) : 0;
         const size_t hist_lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, ctx->stream2));
         HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, ctx->stream3));
         const unsigned tag = (ctx->epoch & 0xfffu) << 20;
         bool sweep_over = false;
         int b0_done = 0;
-        size_t first_late = 0;                                     // wavefronts below this index have been seen past the current slice's rows
         int64_t hist_first = 0;
         for (int sl = 0; sl < NS; ++sl) {
             const int b0_hi = sl == NS - 1 ? G.g0.num : std::max(b0_done, (int)((int64_t)G.g0.num * (sl + 1) / NS));
             const int rows_need = b0_hi >= G.g0.num ? G.g0.count : szh_blk_start(G.g0, b0_hi);
-            first_late = 0;
+            size_t first_late = 0;                                     // wavefronts below this index have been seen past the current slice's rows
             unsigned spins = 0;
             while (!sweep_over && first_late < beam_words) {
                 const unsigned wv = __atomic_load_n(&tile_done[first_late], __ATOMIC_ACQUIRE);
@@ -672,58 +692,150 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
                 hist_first = h_hi;
                 const int grid = (int)std::min<int64_t>(((h_hi - h_lo) / 8 + 255) / 256 + 1, 2048);
                 if (h_hi > h_lo) hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), hist_lds, ctx->stream2, (const uint16_t *)d_nat, h_hi, intervals, rshift, use_lds, d_hist, h_lo);
-                if (!segenc)
-                hipLaunchKernelGGL((k_permute<0>), dim3((unsigned)((b0_hi - b0_done) * G.g1.num), std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + 16, ctx->stream3, G,
-                                   (const uint16_t *)d_nat, d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p,
-                                   b0_done * G.g1.num);
+                if (!P.segenc) launch_permute(ctx->stream3, b0_done * G.g1.num, (b0_hi - b0_done) * G.g1.num);
                 HIPCHK(hipGetLastError());
                 b0_done = b0_hi;
             }
         }
         HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, ctx->stream2));
         HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
-        if (!segenc) {
-        hipLaunchKernelGGL(k_u32_to_u64, dim3((ncols + 255) / 256), dim3(256), 0, ctx->stream3, (const unsigned *)ctx->col_zeros.p, (int64_t)ncols, (u64 *)ctx->col_zeros64.p);
-        TRY(scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, ncols, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED, ctx->stream3));
-        }
+        if (!P.segenc) TRY(scan_col_zeros(ctx->stream3));
         HIPCHK(hipEventRecord(ctx->ev_perm, ctx->stream3));
-        perm_segb = segb; perm_nseg = nseg;
+        return SZHIP_OK;
     }
-    // the block-ordering pass over the whole array, on the first stream (arrays whose sweep feeds no slices; with segenc: only if the code book turns out not to fit its kernels)
-    auto permute_all = [&]() -> int {
-    HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, st));
-    {
-        const int segb = choose_segb(G, 2, SZH_PERM_TILE_BYTES);
-        const int nseg = (G.g2.num + segb - 1) / segb;
-        TRY(ensure(ctx, ctx->zcnt, (size_t)ncols * nseg * 4));
-        TRY(ensure(ctx, ctx->zpos, (size_t)ncols * nseg * SZH_ZCAP * 4));
-        const size_t tb = tile_bytes(G, segb, 2), tile_el = (tb + 1) / 2;
-        hipLaunchKernelGGL((k_permute<0>), dim3(ncols, std::min(nseg, std::max(1, tune_int("SZ_HIP_PERM_Y", 1)))), dim3(256), ((tile_el + 1) & ~(size_t)1) * 2 + 16, st, G, (const uint16_t *)d_nat,
-                           d_blk, (unsigned *)ctx->col_zeros.p, segb, (unsigned *)ctx->zcnt.p, (unsigned *)ctx->zpos.p, 0);
-        perm_segb = segb; perm_nseg = nseg;
+    // ---- histogram, block ordering, unpredictable counts
+    int hist_and_order() {
+        TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
+        d_hist = (unsigned *)ctx->hist.p;
+        TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
+        h_hist = (unsigned *)ctx->pinned;
+        if (P.seghist) {
+            // (behind the sweep, on its stream: beside it the pass took from the sweep what it saved behind it -- 512^3: sweep 0.70 -> 0.76 ms with four slices of the older histogram)
+            TRY(ensure(ctx, ctx->seg_hist, (size_t)ncols * intervals * 4));
+            HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
+            hipLaunchKernelGGL(k_col_hist, dim3((unsigned)ncols), dim3(256), ((size_t)intervals * 4) << P.sh_rshift, st, G, (const uint16_t *)d_nat, intervals, P.sh_rshift, P.se_vw, (unsigned *)ctx->seg_hist.p);
+            hipLaunchKernelGGL(k_hist_reduce, dim3((unsigned)std::min<int64_t>(64, ncols)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, intervals, (int64_t)ncols, d_hist);
+            HIPCHK(hipGetLastError());
+            if (!P.dev_book) {
+                HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipEventRecord(ctx->ev_fit, st));
+            }
+        } else if (!P.sliced) TRY(launch_hist());                  // next to the block-ordering pass
+        TRY(ensure(ctx, ctx->col_zeros, (size_t)ncols * 4));
+        TRY(ensure(ctx, ctx->col_zeros64, (size_t)ncols * 8));
+        TRY(ensure(ctx, ctx->col_off, (size_t)ncols * 8));
+        if (P.sliced) TRY(hist_and_order_sliced());
+        else if (!P.segenc) TRY(permute_all());
+        return SZHIP_OK;
+    }
+    // the stream header's fixed front: the parameter bytes, n, the block size, the bound
+    unsigned char *put_front(unsigned char *q) const {
+        memcpy(q, meta, meta_len); q += meta_len;
+        szhost_put_u64be(q, (uint64_t)n); q += 8;
+        szhost_put_u32be(q, (uint32_t)G.block_size); q += 4;
+        if (is_double) szhost_put_f64be(q, (double)eb); else szhost_put_f32be(q, (float)eb);
+        return q + sizeof(T);
+    }
+    // the segments' geometry, the same for every column (k_col_encode reads it instead of working it out)
+    int upload_segments() {
+        se_segs.resize((size_t)P.se_nseg);
+        for (int q = 0; q < P.se_nseg; ++q) se_segs[(size_t)q] = szh_se::make_seg(G, 1, q, P.se_segb, P.se_vw);
+        TRY(ensure(ctx, ctx->seg_tab, se_segs.size() * sizeof(szh_se::seg_t)));
+        HIPCHK(hipMemcpyAsync(ctx->seg_tab.p, se_segs.data(), se_segs.size() * sizeof(szh_se::seg_t), hipMemcpyHostToDevice, st));
+        return SZHIP_OK;
+    }
+    // The packing passes on natural-order codes (szh_segenc.h): bits and zero codes per block column, their offsets (the scan also clears the words at the column
+    // boundaries), then k_col_encode.  `base_bits`: where the payload starts in `d_stream`; `d_plan`: the device code book's plan, which says so instead (szh_book.h);
+    // `maxlen`: the longest code word, for the bit window.  `between` enqueues what writes the stream in front of the payload: behind the scan, because the first word
+    // it clears may begin with the header's (or the unpredictable values') last bytes.
+    template <class F>
+    int pack_columns(unsigned char *d_stream, u64 base_bits, const u64 *d_plan, unsigned maxlen, F &&between) {
+        const int64_t nent = (int64_t)ncols;
+        TRY(ensure(ctx, ctx->seg_bits, (size_t)nent * 8)); TRY(ensure(ctx, ctx->seg_zeros, (size_t)nent * 8));
+        TRY(ensure(ctx, ctx->seg_bitoff, (size_t)nent * 8)); TRY(ensure(ctx, ctx->seg_zoff, (size_t)nent * 8));
+        u64 *const bits = (u64 *)ctx->seg_bits.p, *const zeros = (u64 *)ctx->seg_zeros.p, *const bitoff = (u64 *)ctx->seg_bitoff.p, *const zoff = (u64 *)ctx->seg_zoff.p;
+        const size_t lb = intervals <= 16384 ? (size_t)intervals : 16;
+        if (P.seghist) hipLaunchKernelGGL(k_col_bits_h, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, (const uint8_t *)ctx->len_tab.p, intervals, nent, bits, zeros);
+        else hipLaunchKernelGGL(k_col_bits, dim3((unsigned)nent), dim3(256), lb, st, G, (const uint16_t *)d_nat, (const uint8_t *)ctx->len_tab.p, intervals, P.se_vw, bits, zeros);
+        if (nent <= 1024 * SZH_COL_SCAN_PER && tune_int("SZ_HIP_SEG_SCAN1", 1))
+            hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(1024), 0, st, (const u64 *)bits, (const u64 *)zeros, (int)nent, bitoff, zoff, sm + SM_TOTAL_BITS, sm + SM_TOTAL_UNPRED, base_bits, (unsigned *)d_stream, d_plan);
+        else {
+            TRY(scan_u64(ctx, (const u64 *)bits, nent, bitoff, sm + SM_TOTAL_BITS));
+            TRY(scan_u64(ctx, (const u64 *)zeros, nent, zoff, sm + SM_TOTAL_UNPRED));
+            hipLaunchKernelGGL(k_col_bounds, dim3((unsigned)((nent + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)bitoff, nent, (const u64 *)(sm + SM_TOTAL_BITS), base_bits, (unsigned *)d_stream);
+        }
         HIPCHK(hipGetLastError());
+        TRY(between());
+        const unsigned win = (unsigned)szh_se::seg_window_words(G, std::max(1u, maxlen), P.se_nrmax);
+        const size_t lds = ((size_t)intervals + 1) * 8 + P.se_tile + 16 + (size_t)win * 4;
+        auto encode = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nent), dim3(256), lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, P.se_nseg, P.se_vw,
+                               P.se_nrmax, P.se_tile, win, (const u64 *)bitoff, (const u64 *)zoff, base_bits, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p, d_plan);
+        };
+        if (G.g2.num >= 2 && G.g2.early <= szh_se::INNER && G.g2.late >= szh_se::INNER - 1) encode(k_col_encode<T, true>);
+        else encode(k_col_encode<T, false>);
+        HIPCHK(hipGetLastError());
+        return SZHIP_OK;
     }
-    hipLaunchKernelGGL(k_u32_to_u64, dim3((ncols + 255) / 256), dim3(256), 0, st, (const unsigned *)ctx->col_zeros.p, (int64_t)ncols,
-                       (u64 *)ctx->col_zeros64.p);
-    TRY(scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, ncols, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED));
-    return SZHIP_OK;
-    };
-    if (!sliced && !segenc) TRY(permute_all());
-
-    if (dev_book) {
-        if (!seghist) HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));           // (the histogram of the larger alphabets is the second stream's)
+    // ---- the end of every call: the sweep's and the packing passes' words read back, checked behind the final synchronisation, the stream delivered, the statistics
+    int enqueue_readback() {
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        TP("encode launched");
+        HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
+        return SZHIP_OK;
+    }
+    // the stream to the caller: into its device buffer (of capacity *out_size), as a pointer into the context's buffer, or as a malloc'd host copy; synchronises
+    // the first stream unless that is behind us and nothing was enqueued since
+    int deliver(unsigned char *d_stream, size_t len, bool in_place) {
+        if (out_on_device == 2) {
+            if (!*out || *out_size < len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, len);
+            if (!in_place) { HIPCHK(hipMemcpyAsync(*out, d_stream, len, hipMemcpyDeviceToDevice, st)); synced = false; }
+            if (!synced) HIPCHK(hipStreamSynchronize(st));
+        } else if (out_on_device) {
+            if (!synced) HIPCHK(hipStreamSynchronize(st));
+            *out = d_stream;
+        } else {
+            unsigned char *h = (unsigned char *)malloc(len ? len : 1);
+            if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
+            const int rc_copy = staged_copy(ctx, h, d_stream, len, false);
+            if (rc_copy != SZHIP_OK) { free(h); return rc_copy; }
+            *out = h;
+        }
+        *out_size = len;
+        synced = true;
+        return SZHIP_OK;
+    }
+    // after the final synchronisation: the wavefront kernel's error flag; the device book's verdict (`declined`, with its status; the caller's wrapper repeats the
+    // call with the host's book, so no message on stderr); the packed bit count and the device's count of zero codes must match what the code book predicted
+    int check_final(bool declined, unsigned book_status, u64 bits, u64 unpred) {
+        if ((unsigned)h_small[SM_ERR] == 2) { ctx->coef_late = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: the regression coefficients did not arrive"); }
+        if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
+        if (declined) {
+            ctx->book_declined = true;
+            snprintf(ctx->err, sizeof(ctx->err), "device code book declined (status %u)", book_status);
+            return SZHIP_ERR_INTERNAL;
+        }
+        if ((bits > 0 && h_small[SM_TOTAL_BITS] != bits) || h_small[SM_TOTAL_UNPRED] != unpred)
+            FAIL(SZHIP_ERR_INTERNAL, "entropy stage mismatch (bits %llu vs %llu, unpredictable %llu vs %llu)", (unsigned long long)h_small[SM_TOTAL_BITS],
+                 (unsigned long long)bits, (unsigned long long)h_small[SM_TOTAL_UNPRED], (unsigned long long)unpred);
+        return SZHIP_OK;
+    }
+    void finish_stats(size_t len, u64 unpred, int packing, int book_on_device) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
+        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
+        hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
+        S.n_unpred = unpred; S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = len; S.packing = packing; S.book_on_device = book_on_device;
+    }
+    // ---- the code book on the device (k_huff_book), the header written by kernels, the packing passes: nothing waits for the host before the call's one
+    //      synchronisation; the checks come before an output is published
+    int encode_with_device_book() {
+        const size_t bk_front = meta_len + 8 + 4 + sizeof(T), bk_mid = 1 + sizeof(T);
+        if (!P.seghist) HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));           // (the histogram of the larger alphabets is the second stream's)
         if (!ctx->book_pin) HIPCHK(hipHostMalloc((void **)&ctx->book_pin, 4096, hipHostMallocDefault));
         unsigned char *const blob = (unsigned char *)ctx->book_pin + 256;       // the header's fixed front, then the mean byte and the mean
-        {
-            unsigned char *q = blob;
-            memcpy(q, meta, meta_len); q += meta_len;
-            szhost_put_u64be(q, (uint64_t)n); q += 8;
-            szhost_put_u32be(q, (uint32_t)G.block_size); q += 4;
-            if (is_double) szhost_put_f64be(q, (double)eb); else szhost_put_f32be(q, (float)eb);
-            q += sizeof(T);
-            *q++ = (unsigned char)use_mean;
-            memcpy(q, &mean, sizeof(T));
-        }
+        unsigned char *const mid = put_front(blob);
+        mid[0] = (unsigned char)use_mean; memcpy(mid + 1, &mean, sizeof(T));
         const size_t plan_fixed = bk_front + 12 + bk_mid + ind_bytes + 8;       // the header without the tree
         const size_t tree_cap = 1 + (size_t)9 * (2 * SZH_BOOK_CAP - 1);
         // the buffers are sized before the stream's length is known: room for a stream as large as the array and for a quarter of its values unpredictable (a
@@ -736,124 +848,67 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         TRY(ensure(ctx, ctx->book_stage, bk_front + bk_mid)); TRY(ensure(ctx, ctx->book_tree, tree_cap)); TRY(ensure(ctx, ctx->book_rec, 32 + SZH_PLAN_COUNT * 8));
         TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8)); TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
         TRY(ensure(ctx, ctx->unpred, unpred_cap + 64));
-        const int64_t se_nent = (int64_t)ncols;
-        TRY(ensure(ctx, ctx->seg_bits, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zeros, (size_t)se_nent * 8));
-        TRY(ensure(ctx, ctx->seg_bitoff, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zoff, (size_t)se_nent * 8));
         szh_book_rec *const d_rec = (szh_book_rec *)ctx->book_rec.p;
         u64 *const d_plan = (u64 *)((char *)ctx->book_rec.p + 32);
         HIPCHK(hipMemcpyAsync(ctx->book_stage.p, blob, bk_front + bk_mid, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_huff_book, dim3(1), dim3(256), 0, st, (const unsigned *)d_hist, intervals, SZH_BOOK_TAB_SEG, (unsigned char *)ctx->book_tree.p, (unsigned)tree_cap,
                            (u64 *)ctx->code_tab.p, (uint8_t *)ctx->len_tab.p, d_rec, d_plan, (u64)plan_fixed, (unsigned)sizeof(T), (u64)stream_cap, (u64)unpred_cap);
         HIPCHK(hipGetLastError());
-        // the packing passes as below, the window sized for the longest code words they take (32 bits)
-        const unsigned se_win = (unsigned)szh_se::seg_window_words(G, 32u, se_nrmax);
-        const size_t se_lds = ((size_t)intervals + 1) * 8 + se_tile + 16 + (size_t)se_win * 4;
-        std::vector<szh_se::seg_t> se_segs((size_t)se_nseg);                    // (alive until the synchronisation below: it is copied to the device asynchronously)
-        for (int q = 0; q < se_nseg; ++q) se_segs[(size_t)q] = szh_se::make_seg(G, 1, q, se_segb, se_vw);
-        TRY(ensure(ctx, ctx->seg_tab, se_segs.size() * sizeof(szh_se::seg_t)));
-        HIPCHK(hipMemcpyAsync(ctx->seg_tab.p, se_segs.data(), se_segs.size() * sizeof(szh_se::seg_t), hipMemcpyHostToDevice, st));
-        const size_t lb = intervals <= 16384 ? (size_t)intervals : 16;
-        if (seghist) hipLaunchKernelGGL(k_col_bits_h, dim3((unsigned)((se_nent + 255) / 256)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, (const uint8_t *)ctx->len_tab.p, intervals, se_nent, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
-        else
-        hipLaunchKernelGGL(k_col_bits, dim3((unsigned)se_nent), dim3(256), lb, st, G, (const uint16_t *)d_nat, (const uint8_t *)ctx->len_tab.p, intervals, se_vw, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
-        hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(1024), 0, st, (const u64 *)ctx->seg_bits.p, (const u64 *)ctx->seg_zeros.p, (int)se_nent, (u64 *)ctx->seg_bitoff.p, (u64 *)ctx->seg_zoff.p,
-                           sm + SM_TOTAL_BITS, sm + SM_TOTAL_UNPRED, (u64)0, (unsigned *)d_stream, (const u64 *)d_plan);
-        // (behind the scan: the word it clears at the payload's start may begin with the header's last bytes)
-        hipLaunchKernelGGL(k_book_tail, dim3((unsigned)std::min<size_t>(64, (plan_fixed + tree_cap + 255) / 256)), dim3(256), 0, st, d_stream, (const unsigned char *)ctx->book_stage.p, (unsigned)bk_front,
-                           (unsigned)bk_mid, intervals, (const unsigned char *)ctx->lor_bits.p, ind_bytes, (const unsigned char *)ctx->book_tree.p, (const szh_book_rec *)d_rec, (const u64 *)d_plan);
-        if (G.g2.num >= 2 && G.g2.early <= szh_se::INNER && G.g2.late >= szh_se::INNER - 1)
-            hipLaunchKernelGGL((k_col_encode<T, true>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
-                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)0, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p, (const u64 *)d_plan);
-        else
-            hipLaunchKernelGGL((k_col_encode<T, false>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
-                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)0, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p, (const u64 *)d_plan);
+        TRY(upload_segments());
+        // the window sized for the longest code words the packing passes take (32 bits)
+        TRY(pack_columns(d_stream, 0, (const u64 *)d_plan, 32u, [&]() -> int {
+            hipLaunchKernelGGL(k_book_tail, dim3((unsigned)std::min<size_t>(64, (plan_fixed + tree_cap + 255) / 256)), dim3(256), 0, st, d_stream, (const unsigned char *)ctx->book_stage.p, (unsigned)bk_front,
+                               (unsigned)bk_mid, intervals, (const unsigned char *)ctx->lor_bits.p, ind_bytes, (const unsigned char *)ctx->book_tree.p, (const szh_book_rec *)d_rec, (const u64 *)d_plan);
+            return SZHIP_OK;
+        }));
         hipLaunchKernelGGL((k_book_unpred<T>), dim3((unsigned)std::min<size_t>(256, (unpred_cap / sizeof(T) + 255) / 256)), dim3(256), 0, st, d_stream, (const T *)ctx->unpred.p, (const szh_book_rec *)d_rec, (const u64 *)d_plan);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ctx->ev[4], st));
-        TP("encode launched");
-        u64 h_small[SM_COUNT];
-        HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
+        TRY(enqueue_readback());
         HIPCHK(hipMemcpyAsync(ctx->book_pin, ctx->book_rec.p, 32 + SZH_PLAN_COUNT * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));                                      // the call's one wait behind the sweep
+        synced = true;
         TP("final sync");
         szh_book_rec rec; memcpy(&rec, ctx->book_pin, sizeof(rec));
         const u64 *const plan = (const u64 *)ctx->book_pin + 4;
-        if (tp_on) { for (int i = 0; i < tp_k; ++i) fprintf(stderr, "%s %.2f | ", tp_n[i], tp_t[i]); fprintf(stderr, "\n"); }
-        if ((unsigned)h_small[SM_ERR] == 2) { ctx->coef_late = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: the regression coefficients did not arrive"); }
-        if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
-        if (book_declines(rec.status, plan[SZH_PLAN_STATUS], tune_int("SZ_HIP_TEST_BOOK_FALLBACK", 0))) {
-            // (no message on stderr: the caller's wrapper repeats the call with the host's book)
-            ctx->book_declined = true;
-            snprintf(ctx->err, sizeof(ctx->err), "device code book declined (status %u)", rec.status ? rec.status : (unsigned)plan[SZH_PLAN_STATUS]);
-            return SZHIP_ERR_INTERNAL;
-        }
-        const u64 total_bits = rec.total_bits, total_unpred = rec.total_unpred;
-        const size_t total_len = (size_t)plan[SZH_PLAN_TOTAL_LEN];
-        if ((total_bits > 0 && h_small[SM_TOTAL_BITS] != total_bits) || h_small[SM_TOTAL_UNPRED] != total_unpred)
-            FAIL(SZHIP_ERR_INTERNAL, "entropy stage mismatch (bits %llu vs %llu, unpredictable %llu vs %llu)", (unsigned long long)h_small[SM_TOTAL_BITS],
-                 (unsigned long long)total_bits, (unsigned long long)h_small[SM_TOTAL_UNPRED], (unsigned long long)total_unpred);
-        if (out_on_device == 2) {
-            if (!*out || *out_size < total_len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, total_len);
-            if (!in_place) { HIPCHK(hipMemcpyAsync(*out, d_stream, total_len, hipMemcpyDeviceToDevice, st)); HIPCHK(hipStreamSynchronize(st)); }
-        } else if (out_on_device) *out = d_stream;
-        else {
-            unsigned char *h = (unsigned char *)malloc(total_len ? total_len : 1);
-            if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
-            const int rc_copy = staged_copy(ctx, h, d_stream, total_len, false);
-            if (rc_copy != SZHIP_OK) { free(h); return rc_copy; }
-            *out = h;
-        }
-        *out_size = total_len;
-        float ms = 0;
-        hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
-        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-        hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
-        S.n_unpred = total_unpred; S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = total_len; S.packing = 1; S.book_on_device = 1;
-        if (stats) *stats = S;
+        print_trace();
+        TRY(check_final(book_declines(rec.status, plan[SZH_PLAN_STATUS], tune_int("SZ_HIP_TEST_BOOK_FALLBACK", 0)), rec.status ? rec.status : (unsigned)plan[SZH_PLAN_STATUS],
+                        rec.total_bits, rec.total_unpred));
+        const size_t len = (size_t)plan[SZH_PLAN_TOTAL_LEN];
+        TRY(deliver(d_stream, len, in_place));
+        finish_stats(len, rec.total_unpred, 1, 1);
         return SZHIP_OK;
     }
-
     // ---- Huffman code book (host: heap order decides the codes), built as soon as the histogram has arrived.  This is the only host
     //      round trip of the entropy stage: the number of unpredictable values is the histogram's bin 0, so the header can be written
     //      and the remaining kernels enqueued while the block-ordering pass is still running; the kernel error flag and the device's
     //      own count of zero codes are checked after the final synchronisation.
-    TP("permute launched");
-    HIPCHK(hipEventSynchronize(ctx->ev_fit));
-    TP("hist on host");
-    double h0 = now_ms();
-    szhost_huff *hf = szhost_huff_build(2 * (int)intervals, h_hist, nullptr, intervals);
-    host_ms += now_ms() - h0;
-    const u64 total_unpred = h_hist[0];
-    S.n_unpred = total_unpred;
-    if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
-
-    // ---- stream header
-    TP("tree built");
-    for (auto &x : section_threads) if (x.joinable()) x.join();
-    if (pool_busy) { ctx->chain_pool->wait_all(); pool_busy = false; }
-    TP("sections joined");
-    if (section_failed) { szhost_huff_free(hf); FAIL(SZHIP_ERR_INTERNAL, "coefficient Huffman build failed"); }
-    size_t sections_total = 0;
-    for (int e = 0; e < ncoef; ++e) sections_total += sec_len[e];
-    h0 = now_ms();
-    const size_t tree_bytes = szhost_huff_tree_size(hf);
-    const size_t pre_len = meta_len + 8 + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes + 1 + sizeof(T) + ind_bytes;     // the header in front of the coefficient sections
-    const size_t hdr_len = pre_len + sections_total + 8;
-    const size_t unpred_bytes = (size_t)total_unpred * sizeof(T);
-    const size_t pay_bytes = (size_t)((hf->total_bits + 7) / 8);
-    const size_t total_len = hdr_len + unpred_bytes + pay_bytes;
-    // assembled in pinned memory (the histogram that lived there has been consumed): with coefficient sections the header is megabytes,
-    // and an asynchronous copy from pageable memory of that size makes the runtime pin and unpin the pages
-    TRY(ensure_pinned(ctx, pre_len + 8 + 64));
-    unsigned char *const hdr = (unsigned char *)ctx->pinned;           // [the header in front of the sections][the eight bytes behind them]
-    memset(hdr, 0, pre_len + 8);
-    {
-        unsigned char *q = hdr;
-        memcpy(q, meta, meta_len); q += meta_len;
-        szhost_put_u64be(q, (uint64_t)n); q += 8;
-        szhost_put_u32be(q, (uint32_t)G.block_size); q += 4;
-        if (is_double) szhost_put_f64be(q, (double)eb); else szhost_put_f32be(q, (float)eb);
-        q += sizeof(T);
+    //      Here: the book, the coefficient sections joined, the header assembled in pinned memory, the plan revised, the code tables on their way to the device.
+    int build_host_book() {
+        TP("permute launched");
+        HIPCHK(hipEventSynchronize(ctx->ev_fit));
+        TP("hist on host");
+        double h0 = now_ms();
+        szhost_huff *hf = szhost_huff_build(2 * (int)intervals, h_hist, nullptr, intervals);
+        host_ms += now_ms() - h0;
+        total_unpred = h_hist[0];
+        if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
+        TP("tree built");
+        join_sections();
+        TP("sections joined");
+        if (section_failed) { szhost_huff_free(hf); FAIL(SZHIP_ERR_INTERNAL, "coefficient Huffman build failed"); }
+        for (int e = 0; e < ncoef; ++e) sections_total += sec_len[e];
+        h0 = now_ms();
+        const size_t tree_bytes = szhost_huff_tree_size(hf);
+        pre_len = meta_len + 8 + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes + 1 + sizeof(T) + ind_bytes;     // the header in front of the coefficient sections
+        hdr_len = pre_len + sections_total + 8;
+        unpred_bytes = (size_t)total_unpred * sizeof(T);
+        total_len = hdr_len + unpred_bytes + (size_t)((hf->total_bits + 7) / 8);
+        // assembled in pinned memory (the histogram that lived there has been consumed): with coefficient sections the header is megabytes,
+        // and an asynchronous copy from pageable memory of that size makes the runtime pin and unpin the pages
+        { const int rc = ensure_pinned(ctx, pre_len + 8 + 64); if (rc != SZHIP_OK) { szhost_huff_free(hf); return rc; } }
+        hdr = (unsigned char *)ctx->pinned;                              // [the header in front of the sections][the eight bytes behind them]
+        memset(hdr, 0, pre_len + 8);
+        unsigned char *q = put_front(hdr);
         szhost_put_u32be(q, intervals); q += 4;
         szhost_put_u32be(q, (uint32_t)tree_bytes); q += 4;
         szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;
@@ -861,160 +916,132 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         *q++ = (unsigned char)use_mean;
         memcpy(q, &mean, sizeof(T)); q += sizeof(T);
         memcpy(q, ind_bits, ind_bytes); q += ind_bytes;
-        const uint64_t tu = total_unpred; memcpy(q, &tu, 8); q += 8;
-    }
-    // device code tables: right-aligned code bits + lengths, one entry per symbol < intervals
-    std::vector<u64> tab_code(intervals); std::vector<uint8_t> tab_len(intervals);
-    for (unsigned s = 0; s < intervals; ++s) { tab_code[s] = hf->code[s]; tab_len[s] = hf->len[s]; }
-    const u64 total_bits = hf->total_bits;
-    szhost_huff_free(hf);
-    // code words of up to 32 bits and a table that fits beside the window in LDS: k_encode32 (32 consecutive codes per thread) packs the
-    // payload, from the table `code << 8 | length`; anything else stays with k_encode
-    unsigned enc_maxlen = 0;
-    for (unsigned s = 0; s < intervals; ++s) enc_maxlen = std::max<unsigned>(enc_maxlen, tab_len[s]);
-    const size_t lds_e32 = (size_t)intervals * 8 + ((size_t)SZH_E32_ROUND * enc_maxlen / 32 + 4) * 4 + 16;
-    const bool enc32 = enc_maxlen >= 1 && enc_maxlen <= 32 && lds_e32 <= 60 * 1024 && tune_int("SZ_HIP_ENC32", 1);
-    // (round 6) the packing passes on natural-order codes: does the code book fit (code words of up to 32 bits)?  If not: the block-ordered copy after all, and the passes that read it
-    size_t se_lds = 0;
-    std::vector<szh_se::seg_t> se_segs;                             // (alive until the call's final synchronisation: it is copied to the device asynchronously)
-    if (segenc && enc_maxlen > 32) {
-        segenc = false; seghist = false;
-        if (sliced) HIPCHK(hipStreamWaitEvent(st, ctx->ev_perm, 0));
-        TRY(permute_all());
-    }
-    if (segenc) {
-        se_lds = ((size_t)intervals + 1) * 8 + se_tile + 16 + szh_se::seg_window_words(G, std::max(1u, enc_maxlen), se_nrmax) * 4;
-        // the segments' geometry, the same for every column (k_col_encode reads it instead of working it out)
-        se_segs.resize((size_t)se_nseg);
-        for (int q = 0; q < se_nseg; ++q) se_segs[(size_t)q] = szh_se::make_seg(G, 1, q, se_segb, se_vw);
-        TRY(ensure(ctx, ctx->seg_tab, se_segs.size() * sizeof(szh_se::seg_t)));
-        HIPCHK(hipMemcpyAsync(ctx->seg_tab.p, se_segs.data(), se_segs.size() * sizeof(szh_se::seg_t), hipMemcpyHostToDevice, st));
-    }
-    if (segenc) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 32) | tab_len[s] | (s == 0 ? 0x10000u : 0u);      // (k_col_encode's table: szh_segenc.h)
-    else if (enc32) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 8) | tab_len[s];
-    host_ms += now_ms() - h0;
-
-    TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
-    TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
-    HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
-    // (a caller's device buffer with room for the stream and the 64 bytes of slack behind it is written in place: no 37 MB copy at the end of the call)
-    const bool in_place = out_on_device == 2 && *out && *out_size >= total_len + 64 && ((uintptr_t)*out & 15) == 0 && tune_int("SZ_HIP_OUT_IN_PLACE", 1);
-    if (!in_place) TRY(ensure(ctx, ctx->stream_buf, total_len + 64));
-    unsigned char *d_stream = in_place ? (unsigned char *)*out : (unsigned char *)ctx->stream_buf.p;
-    const int64_t se_nent = (int64_t)ncols;
-    if (segenc) {
-        // bits and zero codes per segment, their offsets, then the words at the segment boundaries cleared -- in front of the header's copies: the first of
-        // those words may begin with the header's (or the unpredictable values') last bytes
-        TRY(ensure(ctx, ctx->seg_bits, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zeros, (size_t)se_nent * 8));
-        TRY(ensure(ctx, ctx->seg_bitoff, (size_t)se_nent * 8)); TRY(ensure(ctx, ctx->seg_zoff, (size_t)se_nent * 8));
-        const size_t lb = intervals <= 16384 ? (size_t)intervals : 16;
-        if (seghist) hipLaunchKernelGGL(k_col_bits_h, dim3((unsigned)((se_nent + 255) / 256)), dim3(256), 0, st, (const unsigned *)ctx->seg_hist.p, (const uint8_t *)ctx->len_tab.p, intervals, se_nent, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
-        else
-        hipLaunchKernelGGL(k_col_bits, dim3((unsigned)se_nent), dim3(256), lb, st, G, (const uint16_t *)d_nat, (const uint8_t *)ctx->len_tab.p, intervals, se_vw, (u64 *)ctx->seg_bits.p, (u64 *)ctx->seg_zeros.p);
-        if (se_nent <= 1024 * SZH_COL_SCAN_PER && tune_int("SZ_HIP_SEG_SCAN1", 1))
-            hipLaunchKernelGGL(k_col_scan, dim3(1), dim3(1024), 0, st, (const u64 *)ctx->seg_bits.p, (const u64 *)ctx->seg_zeros.p, (int)se_nent, (u64 *)ctx->seg_bitoff.p, (u64 *)ctx->seg_zoff.p,
-                               sm + SM_TOTAL_BITS, sm + SM_TOTAL_UNPRED, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream);
-        else {
-        TRY(scan_u64(ctx, (const u64 *)ctx->seg_bits.p, se_nent, (u64 *)ctx->seg_bitoff.p, sm + SM_TOTAL_BITS));
-        TRY(scan_u64(ctx, (const u64 *)ctx->seg_zeros.p, se_nent, (u64 *)ctx->seg_zoff.p, sm + SM_TOTAL_UNPRED));
-        hipLaunchKernelGGL(k_col_bounds, dim3((unsigned)((se_nent + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)ctx->seg_bitoff.p, se_nent, (const u64 *)(sm + SM_TOTAL_BITS),
-                           (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream);
+        const uint64_t tu = total_unpred; memcpy(q, &tu, 8);
+        // device code tables: right-aligned code bits + lengths, one entry per symbol < intervals
+        tab_code.resize(intervals); tab_len.resize(intervals);
+        for (unsigned s = 0; s < intervals; ++s) { tab_code[s] = hf->code[s]; tab_len[s] = hf->len[s]; }
+        total_bits = hf->total_bits;
+        szhost_huff_free(hf);
+        // code words of up to 32 bits and a table that fits beside the window in LDS: k_encode32 (32 consecutive codes per thread) packs the
+        // payload, from the table `code << 8 | length`; anything else stays with k_encode
+        for (unsigned s = 0; s < intervals; ++s) enc_maxlen = std::max<unsigned>(enc_maxlen, tab_len[s]);
+        lds_e32 = (size_t)intervals * 8 + ((size_t)SZH_E32_ROUND * enc_maxlen / 32 + 4) * 4 + 16;
+        enc32 = enc_maxlen >= 1 && enc_maxlen <= 32 && lds_e32 <= 60 * 1024 && tune_int("SZ_HIP_ENC32", 1);
+        if (P.revise(enc_maxlen)) {                                      // (the code book does not fit the packing passes on natural-order codes)
+            if (P.sliced) HIPCHK(hipStreamWaitEvent(st, ctx->ev_perm, 0));
+            TRY(permute_all());
         }
-        HIPCHK(hipGetLastError());
-    } else
-    HIPCHK(hipMemsetAsync(d_stream, 0, total_len + 64, st));
-    HIPCHK(hipMemcpyAsync(d_stream, hdr, pre_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_stream + pre_len + sections_total, hdr + pre_len, 8, hipMemcpyHostToDevice, st));
-    if (sections_total) {                                      // the coefficient sections: from the chain threads' pinned buffers, beside the encoder (the stream buffer is cleared)
-        const hipStream_t ssec = ctx->stream3 ? ctx->stream3 : ctx->stream2;      // (the third stream has nothing else to do from here on)
-        HIPCHK(hipEventRecord(ctx->ev_feed, st));
-        HIPCHK(hipStreamWaitEvent(ssec, ctx->ev_feed, 0));
-        size_t off = pre_len;
-        for (int e = 0; e < ncoef; ++e) { HIPCHK(hipMemcpyAsync(d_stream + off, ctx->sec_pin[e], sec_len[e], hipMemcpyHostToDevice, ssec)); off += sec_len[e]; }
-        HIPCHK(hipEventRecord(ctx->ev_sec, ssec));
+        if (P.segenc) TRY(upload_segments());
+        if (P.segenc) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 32) | tab_len[s] | (s == 0 ? 0x10000u : 0u);      // (k_col_encode's table: szh_segenc.h)
+        else if (enc32) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 8) | tab_len[s];
+        host_ms += now_ms() - h0;
+        TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
+        TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
+        HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
+        return SZHIP_OK;
     }
-    if (segenc) {
-        TRY(ensure(ctx, ctx->unpred, unpred_bytes + 64));
-        const unsigned se_win = (unsigned)szh_se::seg_window_words(G, std::max(1u, enc_maxlen), se_nrmax);
-        if (G.g2.num >= 2 && G.g2.early <= szh_se::INNER && G.g2.late >= szh_se::INNER - 1)
-            hipLaunchKernelGGL((k_col_encode<T, true>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
-                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p);
-        else
-            hipLaunchKernelGGL((k_col_encode<T, false>), dim3((unsigned)se_nent), dim3(256), se_lds, st, G, (const uint16_t *)d_nat, (const u64 *)ctx->code_tab.p, intervals, (const szh_se::seg_t *)ctx->seg_tab.p, se_nseg, se_vw, se_nrmax, se_tile, se_win,
-                               (const u64 *)ctx->seg_bitoff.p, (const u64 *)ctx->seg_zoff.p, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream, d_in, (T *)ctx->unpred.p);
-        HIPCHK(hipGetLastError());
+    // the header in front of the coefficient sections and the eight bytes behind them; the sections themselves from the chain threads' pinned buffers, beside the encoder
+    int copy_header(unsigned char *d_stream) {
+        HIPCHK(hipMemcpyAsync(d_stream, hdr, pre_len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_stream + pre_len + sections_total, hdr + pre_len, 8, hipMemcpyHostToDevice, st));
+        if (sections_total) {
+            const hipStream_t ssec = ctx->stream3 ? ctx->stream3 : ctx->stream2;      // (the third stream has nothing else to do from here on)
+            HIPCHK(hipEventRecord(ctx->ev_feed, st));
+            HIPCHK(hipStreamWaitEvent(ssec, ctx->ev_feed, 0));
+            size_t off = pre_len;
+            for (int e = 0; e < ncoef; ++e) { HIPCHK(hipMemcpyAsync(d_stream + off, ctx->sec_pin[e], sec_len[e], hipMemcpyHostToDevice, ssec)); off += sec_len[e]; }
+            HIPCHK(hipEventRecord(ctx->ev_sec, ssec));
+        }
+        return SZHIP_OK;
+    }
+    // the older packing passes, on block-ordered codes: k_unpred on the second stream beside k_chunk_bits + k_encode32 / k_encode
+    int pack_block_ordered(unsigned char *d_stream) {
+        const u64 base_bits = (u64)(hdr_len + unpred_bytes) * 8;
+        if (P.sliced) HIPCHK(hipStreamWaitEvent(st, ctx->ev_perm, 0));      // block order and per-column offsets (third stream) from here on
+        if (total_unpred > 0) {
+            // the unpredictable values are gathered on the second stream while the payload is being encoded on the first (both only read
+            // the block-ordered codes); their copy into the stream follows the join below
+            TRY(ensure(ctx, ctx->unpred, unpred_bytes));
+            HIPCHK(hipEventRecord(ctx->ev_in, st));                // block order, per-column offsets ready
+            HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
+            hipLaunchKernelGGL((k_unpred<T, 0>), dim3(ncols), dim3(256), 0, ctx->stream2, G, (const uint16_t *)d_blk, (const unsigned *)ctx->col_zeros.p,
+                               (const u64 *)ctx->col_off.p, d_in, (T *)ctx->unpred.p, (T *)nullptr, (const unsigned *)ctx->zcnt.p, (const unsigned *)ctx->zpos.p, perm_segb, perm_nseg);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
+        }
+        if (total_bits > 0) {
+            const int64_t nchunks = (n + SZH_ENC_CHUNK - 1) / SZH_ENC_CHUNK;
+            TRY(ensure(ctx, ctx->chunk_bits, (size_t)nchunks * 8 + 64));
+            TRY(ensure(ctx, ctx->chunk_off, (size_t)nchunks * 8));
+            hipLaunchKernelGGL(k_chunk_bits, dim3((unsigned)((nchunks + SZH_CB_PER - 1) / SZH_CB_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const uint8_t *)ctx->len_tab.p, intervals, (u64 *)ctx->chunk_bits.p);
+            TRY(scan_u64(ctx, (const u64 *)ctx->chunk_bits.p, nchunks, (u64 *)ctx->chunk_off.p, sm + SM_TOTAL_BITS));
+            if (enc32) {
+                const int64_t nrounds = (n + SZH_E32_ROUND - 1) / SZH_E32_ROUND;
+                hipLaunchKernelGGL(k_encode32, dim3((unsigned)((nrounds + SZH_E32_PER - 1) / SZH_E32_PER)), dim3(256), lds_e32, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
+                                   intervals, (const u64 *)ctx->chunk_off.p, base_bits, (unsigned *)d_stream);
+            } else
+                hipLaunchKernelGGL(k_encode, dim3((unsigned)((nchunks + SZH_ENC_PER - 1) / SZH_ENC_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
+                                   (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)ctx->chunk_off.p, base_bits, (unsigned *)d_stream);
+            HIPCHK(hipGetLastError());
+        }
+        if (total_unpred > 0) HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));
+        return SZHIP_OK;
+    }
+    // ---- the host's book: header, payload and unpredictable values into the stream buffer; the stream is delivered with the final synchronisation and checked
+    //      behind it -- a host copy published by then is released again if a check fails
+    int encode_with_host_book() {
+        TRY(build_host_book());
+        // (a caller's device buffer with room for the stream and the 64 bytes of slack behind it is written in place: no 37 MB copy at the end of the call)
+        const bool in_place = out_on_device == 2 && *out && *out_size >= total_len + 64 && ((uintptr_t)*out & 15) == 0 && tune_int("SZ_HIP_OUT_IN_PLACE", 1);
+        if (!in_place) TRY(ensure(ctx, ctx->stream_buf, total_len + 64));
+        unsigned char *d_stream = in_place ? (unsigned char *)*out : (unsigned char *)ctx->stream_buf.p;
+        if (P.segenc) {
+            TRY(pack_columns(d_stream, (u64)(hdr_len + unpred_bytes) * 8, (const u64 *)nullptr, enc_maxlen, [&]() -> int {
+                TRY(copy_header(d_stream));
+                return ensure(ctx, ctx->unpred, unpred_bytes + 64);
+            }));
+        } else {
+            HIPCHK(hipMemsetAsync(d_stream, 0, total_len + 64, st));
+            TRY(copy_header(d_stream));
+            TRY(pack_block_ordered(d_stream));
+        }
         if (total_unpred > 0) HIPCHK(hipMemcpyAsync(d_stream + hdr_len, ctx->unpred.p, unpred_bytes, hipMemcpyDeviceToDevice, st));
-    } else {
-    if (sliced) HIPCHK(hipStreamWaitEvent(st, ctx->ev_perm, 0));      // block order and per-column offsets (third stream) from here on
-    if (total_unpred > 0) {
-        // the unpredictable values are gathered on the second stream while the payload is being encoded on the first (both only read
-        // the block-ordered codes); their copy into the stream follows the join below
-        TRY(ensure(ctx, ctx->unpred, unpred_bytes));
-        HIPCHK(hipEventRecord(ctx->ev_in, st));                // block order, per-column offsets ready
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
-        hipLaunchKernelGGL((k_unpred<T, 0>), dim3(ncols), dim3(256), 0, ctx->stream2, G, (const uint16_t *)d_blk, (const unsigned *)ctx->col_zeros.p,
-                           (const u64 *)ctx->col_off.p, d_in, (T *)ctx->unpred.p, (T *)nullptr, (const unsigned *)ctx->zcnt.p,
-                           (const unsigned *)ctx->zpos.p, perm_segb, perm_nseg);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
+        if (sections_total) HIPCHK(hipStreamWaitEvent(st, ctx->ev_sec, 0));
+        TRY(enqueue_readback());
+        TRY(deliver(d_stream, total_len, in_place));
+        TP("final sync");
+        print_trace();
+        const int rc = check_final(false, 0, total_bits, total_unpred);
+        if (rc != SZHIP_OK) {                                    // found AFTER the stream was handed to the caller's pointer: a host copy that this call malloc'd is released again
+            if (!out_on_device && *out) { free(*out); *out = nullptr; }
+            *out_size = 0;
+            return rc;
+        }
+        finish_stats(total_len, total_unpred, P.segenc ? 1 : 0, 0);
+        return SZHIP_OK;
     }
-    if (total_bits > 0) {
-        const int64_t nchunks = (n + SZH_ENC_CHUNK - 1) / SZH_ENC_CHUNK;
-        TRY(ensure(ctx, ctx->chunk_bits, (size_t)nchunks * 8 + 64));
-        TRY(ensure(ctx, ctx->chunk_off, (size_t)nchunks * 8));
-        hipLaunchKernelGGL(k_chunk_bits, dim3((unsigned)((nchunks + SZH_CB_PER - 1) / SZH_CB_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const uint8_t *)ctx->len_tab.p,
-                           intervals, (u64 *)ctx->chunk_bits.p);
-        TRY(scan_u64(ctx, (const u64 *)ctx->chunk_bits.p, nchunks, (u64 *)ctx->chunk_off.p, sm + SM_TOTAL_BITS));
-        if (enc32) {
-            const int64_t nrounds = (n + SZH_E32_ROUND - 1) / SZH_E32_ROUND;
-            hipLaunchKernelGGL(k_encode32, dim3((unsigned)((nrounds + SZH_E32_PER - 1) / SZH_E32_PER)), dim3(256), lds_e32, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
-                               intervals, (const u64 *)ctx->chunk_off.p, (u64)(hdr_len + unpred_bytes) * 8, (unsigned *)d_stream);
-        } else
-        hipLaunchKernelGGL(k_encode, dim3((unsigned)((nchunks + SZH_ENC_PER - 1) / SZH_ENC_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
-                           (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)ctx->chunk_off.p, (u64)(hdr_len + unpred_bytes) * 8,
-                           (unsigned *)d_stream);
-        HIPCHK(hipGetLastError());
-    }
-    if (total_unpred > 0) {
-        HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));
-        HIPCHK(hipMemcpyAsync(d_stream + hdr_len, ctx->unpred.p, unpred_bytes, hipMemcpyDeviceToDevice, st));
-    }
-    }
-    if (sections_total) HIPCHK(hipStreamWaitEvent(st, ctx->ev_sec, 0));
-    HIPCHK(hipEventRecord(ctx->ev[4], st));
-    TP("encode launched");
-    u64 h_small[SM_COUNT];                                     // checked after the synchronisation below
-    HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
-    if (out_on_device == 2) { // caller-provided device buffer of capacity *out_size
-        if (!*out || *out_size < total_len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, total_len);
-        if (!in_place) HIPCHK(hipMemcpyAsync(*out, d_stream, total_len, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else if (out_on_device) {
-        HIPCHK(hipStreamSynchronize(st));
-        *out = d_stream;
-    } else {
-        unsigned char *h = (unsigned char *)malloc(total_len ? total_len : 1);
-        if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
-        TRY(staged_copy(ctx, h, d_stream, total_len, false));
-        *out = h;
-    }
-    *out_size = total_len;
-    TP("final sync");
-    if (tp_on) { for (int i = 0; i < tp_k; ++i) fprintf(stderr, "%s %.2f | ", tp_n[i], tp_t[i]); fprintf(stderr, "\n"); }
-    // after the final synchronisation: the wavefront kernel's error flag; the shuffled bit count and the device's count of zero codes
-    // must match what the histogram predicted
-    if ((unsigned)h_small[SM_ERR] == 2) { ctx->coef_late = true; FAIL_PUBLISHED(SZHIP_ERR_INTERNAL, "wavefront kernel: the regression coefficients did not arrive"); }
-    if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL_PUBLISHED(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
-    if ((total_bits > 0 && h_small[SM_TOTAL_BITS] != total_bits) || h_small[SM_TOTAL_UNPRED] != total_unpred)
-        FAIL_PUBLISHED(SZHIP_ERR_INTERNAL, "entropy stage mismatch (bits %llu vs %llu, unpredictable %llu vs %llu)", (unsigned long long)h_small[SM_TOTAL_BITS],
-             (unsigned long long)total_bits, (unsigned long long)h_small[SM_TOTAL_UNPRED], (unsigned long long)total_unpred);
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
-    S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = total_len; S.packing = segenc ? 1 : 0;
-    if (stats) *stats = S;
+};
+
+template <class T>
+int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device,
+                  unsigned char **out, size_t *out_size, szhip_stats *stats)
+{
+    sz21_call<T> c(ctx, r0, r1, r2, eb_in, prm, meta, meta_len, out_on_device, out, out_size);
+    int rc = c.stage_and_fit(data, data_on_device);
+    if (rc == SZHIP_OK) rc = c.choose_intervals();
+    if (rc == SZHIP_OK) rc = c.join_fit();
+    if (rc == SZHIP_CONSTANT && stats) *stats = c.S;
+    if (rc != SZHIP_OK) return rc;
+    if (ctx->chain_pool) ctx->chain_pool->arm();       // (the workers wake up now and spin until the coefficients are there -- or are sent back to sleep when the call ends)
+    if (c.reg_count > 0) { TRY(c.prepare_chains()); TRY(c.run_chains()); }
+    HIPCHK(hipEventRecord(ctx->ev[1], c.st));
+    c.TP("ev1");
+    c.P = sz21_make_plan<T>(ctx, c.G, c.intervals, c.reg_count, beam_applies<T>(c.G, c.d_in, c.reg_count), c.overlap, c.feed, meta_len);
+    TRY(c.launch_sweep());
+    TRY(c.hist_and_order());
+    TRY(c.P.dev_book ? c.encode_with_device_book() : c.encode_with_host_book());
+    if (stats) *stats = c.S;
     return SZHIP_OK;
 }
 
