@@ -66,7 +66,7 @@ typedef struct szhip_stats {
     uint64_t quant_kernel_launches; /* launches of the wavefront kernel (1 per call) */
     double vmin, vmax;      /* the array's range when SZHIP_RANGE_FROM_DATA was set (else 0) */
     int chain_overlapped;   /* 1: the regression-coefficient chain ran next to the wavefront kernel */
-    int quant_kernel;       /* which mapping of the wavefront kernel ran: 0 = k_pencil (8x8 pencils), 2 = k_beam (szh_beam.h) */
+    int quant_kernel;       /* which mapping of the wavefront kernel ran: 0 = k_pencil (8x8 pencils), 2 = k_beam (szh_beam.h); the OpenMP container: 3 = k_omp_col (32 x 32 box faces, 16-byte aligned array), 4 = k_omp_box reading rows 16 bytes at a time, 5 = k_omp_box value by value */
     int packing;            /* (round 6) 1: the Huffman packing read the sweep's natural-order codes segment by segment (szh_segenc.h); 0: block-ordered copy first */
     int book_on_device;     /* 1: the Huffman code book of this stream was built on the device (SZ_HIP_DEV_BOOK=1, szh_book.h); 0: on the host */
 } szhip_stats;
@@ -99,6 +99,17 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
  * What it reads from device memory must be complete when the call is made: synchronise the stream that produces it first -- the null stream's
  * implicit ordering does not reach non-blocking streams, and a device-to-device hipMemcpy may return to the host before the copy has finished
  * (profiles/r06_device_input_ordering.txt: a tool that decoded a stream right behind such a copy read a stream whose end had not arrived).
+ * Alignment: a pointer to VALUES -- `data` of szhip_minmax, of every compress call and of the prepare calls, `out` of every decompress call -- is aligned to its
+ * element (4 bytes for SZHIP_F32, 8 for SZHIP_F64), on the host or on the device; any other address is refused with SZHIP_ERR_ARG before anything is launched or
+ * written.  More is never required: an array that starts at any element of a larger allocation (a chunk of a buffer, a view that skips a row) is taken, and the
+ * library itself picks the kernels that need 16-byte rows only where the address allows them -- same stream, same values.  BYTE pointers -- `stream`, `meta`, a
+ * caller's stream buffer (out_on_device = 2), the output arrays of szhip_huff_book -- take any alignment.  Nothing is written in front of an output or behind
+ * its end (r0*r1*r2 values of a decompress call, the capacity of a caller's stream buffer), and an input array is never written.
+ * A caller's stream buffer (out_on_device = 2 of szhip_compress / szhip_pool_submit) is written IN PLACE exactly when its address is a multiple of 16 and its
+ * capacity is at least the stream's length + 64 (with SZ_HIP_DEV_BOOK=1, where the length is not known before the kernels run: at least the header without the
+ * tree + 18424 + 64 bytes, and a stream that leaves less than 64 bytes of the capacity free goes round again with the host's book); then bytes behind the stream,
+ * up to the capacity, may be zeroed.  Otherwise the stream is built in the context's buffer and copied: then exactly its bytes are written.  A capacity below the
+ * stream's length is SZHIP_ERR_ARG -- found when the length is known, at the end of the call; nothing outside the buffer has been written and the context stays usable.
  */
 /* min / max of n values (device or host pointer) */
 int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double *vmin, double *vmax);

@@ -249,6 +249,15 @@ def make_meta(dtype, err_mode=ABS, abs_bound=0.0, rel_ratio=0.0, vmin=0.0, vmax=
     return buf.raw[:n]
 
 
+def sz14_range(vmin, vmax, dtype):
+    """(value_range, median) as szhip_compress_sz14 takes them: max - min and min + range / 2, both computed in the data's type
+    (include/szhip.h; the reference's range scan, dataCompression.c:102-119)."""
+    T = np.dtype(dtype).type
+    lo, hi = T(vmin), T(vmax)
+    rng = T(hi - lo)
+    return float(rng), float(T(lo + T(rng / T(2))))
+
+
 BOOK_CAP = 1024                      # distinct symbols k_huff_book's heap holds (SZH_BOOK_CAP, sz_amd/csrc/szh_book.h)
 
 
@@ -341,12 +350,15 @@ class HipContext:
             self._err(rc, "szhip_minmax")
         return lo.value, hi.value
 
-    def compress(self, ptr, on_device, shape3, dtype, eb, meta, params=None, out_on_device=False):
-        """Returns (bytes | device pointer int, size, stats)."""
+    def compress(self, ptr, on_device, shape3, dtype, eb, meta, params=None, out_on_device=False, out_ptr=None, out_cap=0):
+        """Returns (bytes | device pointer int, size, stats).  out_ptr / out_cap: the caller's device buffer and its capacity in bytes
+        (out_on_device = 2 of include/szhip.h); the stream is written there and out_ptr comes back."""
         p = params or szhip_params(100, 0.99, 65536, 0)
         out = ctypes.c_void_p()
         n = ctypes.c_size_t(0)
         st = szhip_stats()
+        if out_ptr is not None:
+            out, n, out_on_device = ctypes.c_void_p(out_ptr), ctypes.c_size_t(out_cap), 2
         rc = lib().szhip_compress(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ptr, int(on_device), shape3[0], shape3[1],
                                   shape3[2], eb, ctypes.byref(p), meta, len(meta), int(out_on_device), ctypes.byref(out),
                                   ctypes.byref(n), ctypes.byref(st))
@@ -359,6 +371,34 @@ class HipContext:
         b = ctypes.string_at(out.value, n.value)
         lib().free(out)
         return b, n.value, st
+
+    def compress_sz14(self, ptr, on_device, shape3, dtype, eb, value_range, median, meta, params=None, out_on_device=False, out_ptr=None, out_cap=0):
+        """The SZ 1.4 container (szhip_compress_sz14).  shape3: (r0, r1, r2), r0 == 0 a 2-D array, r0 == r1 == 0 a 1-D array; value_range / median: see
+        sz14_range.  Returns (bytes | device pointer int, size, stats)."""
+        p = params or szhip_params(100, 0.99, 65536, 0)
+        out = ctypes.c_void_p()
+        n = ctypes.c_size_t(0)
+        st = szhip_stats()
+        if out_ptr is not None:
+            out, n, out_on_device = ctypes.c_void_p(out_ptr), ctypes.c_size_t(out_cap), 2
+        rc = lib().szhip_compress_sz14(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ptr, int(on_device), shape3[0], shape3[1], shape3[2], eb,
+                                       value_range, median, ctypes.byref(p), meta, len(meta), int(out_on_device), ctypes.byref(out), ctypes.byref(n),
+                                       ctypes.byref(st))
+        if rc:
+            self._err(rc, "szhip_compress_sz14")
+        if out_on_device:
+            return out.value, n.value, st
+        b = ctypes.string_at(out.value, n.value)
+        lib().free(out)
+        return b, n.value, st
+
+    def decompress_sz14(self, stream_ptr, stream_on_device, stream_len, body_off, shape3, dtype, out_ptr, out_on_device):
+        st = szhip_stats()
+        rc = lib().szhip_decompress_sz14(self._h, 0 if np.dtype(dtype) == np.float32 else 1, stream_ptr, int(stream_on_device), stream_len,
+                                         body_off, shape3[0], shape3[1], shape3[2], out_ptr, int(out_on_device), ctypes.byref(st))
+        if rc:
+            self._err(rc, "szhip_decompress_sz14")
+        return st
 
     def compress_omp(self, ptr, on_device, shape3, dtype, eb, thread_num, meta, params=None, out_on_device=False):
         """The reference's OpenMP container (szhip_compress_omp; sz/src/sz_omp.c:63-358).  Returns (bytes | device pointer int, size, stats)."""

@@ -386,9 +386,19 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
     return SZHIP_OK;
 }
 
+// include/szhip.h, "Device pointers and ordering": a pointer to VALUES (`data`, `out` of a decompress call) is aligned to its element, on the host or on the device;
+// refused here, before anything is launched.  Byte pointers (streams, parameter bytes, a caller's stream buffer) take any alignment.
+static bool values_misaligned(szhip_ctx *ctx, int dtype, const void *p)
+{
+    if (((uintptr_t)p & (dtype == SZHIP_F32 ? 3u : 7u)) == 0) return false;
+    snprintf(ctx->err, sizeof(ctx->err), "pointer %p is not aligned to its %d-byte elements", p, dtype == SZHIP_F32 ? 4 : 8);
+    return true;
+}
+
 int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int on_dev, size_t n, double *vmin, double *vmax)
 {
     if (!ctx || !data || !n || !vmin || !vmax) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     return dtype == SZHIP_F32 ? minmax_impl<float>(ctx, data, on_dev, n, vmin, vmax)
                               : minmax_impl<double>(ctx, data, on_dev, n, vmin, vmax);
@@ -401,6 +411,7 @@ int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_devi
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
     if ((r0 != 0 && r0 < 2) || r1 < 2 || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const compress_call_guard in_flight;
     unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
@@ -418,6 +429,7 @@ int szhip_compress_sz14(szhip_ctx *ctx, int dtype, const void *data, int data_on
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
     if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const compress_call_guard in_flight;
     unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
@@ -433,6 +445,7 @@ int szhip_decompress_sz14(szhip_ctx *ctx, int dtype, const unsigned char *stream
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
     if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const int rc = with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
                ? decompress14_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, 0, r0, r1, r2, out, out_on_device, stats)
@@ -448,6 +461,7 @@ int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
     if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff || thread_num < 1) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const int rc = dtype == SZHIP_F32
                ? compress_omp_impl<float>(ctx, data, data_on_device, r0, r1, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats)
@@ -461,6 +475,7 @@ int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream,
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
     if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const int rc = dtype == SZHIP_F32
                ? decompress_omp_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats)
@@ -474,6 +489,7 @@ int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_d
                       double *min_log_value)
 {
     if (!ctx || !data || !n || !d_log || !positive || !real_precision || !value_range || !median || !min_log_value || !(pwr_ratio > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const int rc = dtype == SZHIP_F32
         ? pwr_prepare_impl<float>(ctx, data, data_on_device, n, vmin, vmax, pwr_ratio, d_log, signs_host, positive, real_precision, value_range, median, min_log_value)
@@ -486,6 +502,7 @@ int szhip_msst_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_
                        unsigned char *signs_host, int *positive, double *near_zero, double *median_log, double *min_log_value)
 {
     if (!ctx || !data || !d_prepared || !positive || !near_zero || !median_log || !min_log_value || n == 0 || !(pwr_ratio > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const int rc = dtype == SZHIP_F32
         ? msst_prepare_impl<float>(ctx, data, data_on_device, n, vmax, pwr_ratio, d_prepared, signs_host, positive, near_zero, median_log, min_log_value)
@@ -501,6 +518,7 @@ int szhip_compress_sz14_pwr(szhip_ctx *ctx, int dtype, const void *data, int dat
     if (!ctx || !data || !params || !meta || !out || !out_size || !pwr || (pwr->signs_blob_size && !pwr->signs_blob)) return SZHIP_ERR_ARG;
     if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     const compress_call_guard in_flight;
     unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
@@ -533,6 +551,7 @@ int szhip_decompress_sz14_pwr(szhip_ctx *ctx, int dtype, const unsigned char *st
 {
     if (!ctx || !stream || !out || body_off >= stream_len || stream_on_device) return SZHIP_ERR_ARG;        // the header is read on the host
     if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     size_t bo, bs; double thr;
     if (szhip_sz14_pwr_locate(dtype, stream, stream_len, body_off, &bo, &bs, &thr) != SZHIP_OK) return SZHIP_ERR_STREAM;
@@ -549,6 +568,7 @@ int szhip_decompress(szhip_ctx *ctx, int dtype, const unsigned char *stream, int
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
     if ((r0 != 0 && r0 < 2) || r1 < 2 || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     return with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
                ? decompress_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats)

@@ -132,6 +132,7 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[3], st));
     S.quant_kernel_launches = 1;
+    S.quant_kernel = omp_col_applies(g, d_in, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);      // (szhip.h: which form the address and the box shape allowed)
 
     // ---- ONE histogram over all boxes -> code book (host); the ranks of the boxes' verbatim values meanwhile.  Small alphabets: a
     // histogram per box on the way (k_omp_hist_box), from which the boxes' payload sizes follow without another pass over the codes
@@ -422,6 +423,7 @@ int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stre
                             (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, (T *)ctx->samples.p, (const T *)ctx->unpred.p, (const u64 *)ctx->col_off.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[3], st));
+    S.quant_kernel = omp_col_applies(g, d_out, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);
     unsigned bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
     if (!out_on_device) TRY(staged_copy(ctx, out, d_out, (size_t)n * sizeof(T), false));
