@@ -14,6 +14,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -176,6 +177,7 @@ namespace {
 // The host side of every path, one file per path (all inside this anonymous namespace, one translation unit: the kernels' templates are
 // instantiated once):
 #include "szhip_rt.inc"      // buffers, streams, staging copies, launchers of the sweep kernels
+#include "szhip_steps.inc"   // the steps of a call that the paths below share
 #include "szhip_sz21.inc"    // SZ 2.1: the hot path (SZ_compress_args / SZ_decompress of float and double arrays)
 #include "szhip_sz14.inc"    // SZ 1.4 container, MSST19
 #include "szhip_pwr.inc"     // point-wise relative bounds
@@ -183,15 +185,24 @@ namespace {
 
 } // namespace
 
+// no work of the context is in flight behind this
+static void drain(szhip_ctx *ctx)
+{
+    if (ctx->stream3) hipStreamSynchronize(ctx->stream3);
+    hipStreamSynchronize(ctx->stream2);
+    hipStreamSynchronize(ctx->stream);
+}
+// (an early exit must not leave work in flight)
+static int drained_on_failure(szhip_ctx *ctx, int rc) { if (rc != SZHIP_OK) drain(ctx); return rc; }
+// (the same for the paths that use the first stream only)
+static int synced_on_failure(szhip_ctx *ctx, int rc) { if (rc != SZHIP_OK) hipStreamSynchronize(ctx->stream); return rc; }
+
 // runs one call; a wavefront-kernel wait that timed out under the index ticket is answered by ONE repetition with the atomic ticket (see szhip_ctx)
 template <class F>
 static int with_ticket_fallback(szhip_ctx *ctx, F &&run)
 {
     ctx->wave_timeout = false; ctx->hdec_unconverged = false; ctx->coef_late = false; ctx->book_declined = false;
-    auto again = [&]() {       // drain the context's streams, then run the call again
-        if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream);
-        return run();
-    };
+    auto again = [&]() { drain(ctx); return run(); };
     int rc = run();
     if (rc == SZHIP_ERR_INTERNAL && ctx->book_declined && !ctx->no_dev_book) {            // (compression with SZ_HIP_DEV_BOOK=1 only)
         ctx->no_dev_book = true; ctx->wave_timeout = false; rc = again(); ctx->no_dev_book = false;
@@ -210,6 +221,25 @@ static int with_ticket_fallback(szhip_ctx *ctx, F &&run)
     return rc;
 }
 
+// a compress call under compress_call_guard: a failed first attempt clears *out and *out_size, so a repetition starts from the caller's values
+template <class F>
+static int guarded_compress(szhip_ctx *ctx, unsigned char **out, size_t *out_size, F &&run)
+{
+    const compress_call_guard in_flight;
+    unsigned char *const out0 = *out; const size_t cap0 = *out_size;
+    return drained_on_failure(ctx, with_ticket_fallback(ctx, [&]() { *out = out0; *out_size = cap0; return run(); }));
+}
+
+// the extents an entry point takes: a 3-D array, or (r0 == 0) a 2-D one ...
+static bool dims_3d_2d(size_t r0, size_t r1, size_t r2)
+{
+    return !((r0 != 0 && r0 < 2) || r1 < 2 || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff);
+}
+// ... or (r0 == 0 and r1 == 0) a 1-D one
+static bool dims_3d_2d_1d(size_t r0, size_t r1, size_t r2)
+{
+    return !((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff);
+}
 
 extern "C" {
 
@@ -387,21 +417,23 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
 }
 
 // include/szhip.h, "Device pointers and ordering": a pointer to VALUES (`data`, `out` of a decompress call) is aligned to its element, on the host or on the device;
-// refused here, before anything is launched.  Byte pointers (streams, parameter bytes, a caller's stream buffer) take any alignment.
-static bool values_misaligned(szhip_ctx *ctx, int dtype, const void *p)
+// refused here, before anything is launched; then the context's device is made current.  Byte pointers (streams, parameter bytes, a caller's stream buffer) take any alignment.
+static int check_alignment_set_device(szhip_ctx *ctx, int dtype, const void *p)
 {
-    if (((uintptr_t)p & (dtype == SZHIP_F32 ? 3u : 7u)) == 0) return false;
-    snprintf(ctx->err, sizeof(ctx->err), "pointer %p is not aligned to its %d-byte elements", p, dtype == SZHIP_F32 ? 4 : 8);
-    return true;
+    if (((uintptr_t)p & (dtype == SZHIP_F32 ? 3u : 7u)) != 0) {
+        snprintf(ctx->err, sizeof(ctx->err), "pointer %p is not aligned to its %d-byte elements", p, dtype == SZHIP_F32 ? 4 : 8);
+        return SZHIP_ERR_ARG;
+    }
+    return hipSetDevice(ctx->device) != hipSuccess ? SZHIP_ERR_NODEVICE : SZHIP_OK;
 }
+// the float or the double instance of a path's host code
+#define BY_DTYPE(dtype, fn, ...) ((dtype) == SZHIP_F32 ? fn<float>(__VA_ARGS__) : fn<double>(__VA_ARGS__))
 
 int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int on_dev, size_t n, double *vmin, double *vmax)
 {
     if (!ctx || !data || !n || !vmin || !vmax) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    return dtype == SZHIP_F32 ? minmax_impl<float>(ctx, data, on_dev, n, vmin, vmax)
-                              : minmax_impl<double>(ctx, data, on_dev, n, vmin, vmax);
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return BY_DTYPE(dtype, minmax_impl, ctx, data, on_dev, n, vmin, vmax);
 }
 
 int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -409,17 +441,11 @@ int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_devi
                    unsigned char **out, size_t *out_size, szhip_stats *stats)
 {
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
-    if ((r0 != 0 && r0 < 2) || r1 < 2 || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (!dims_3d_2d(r0, r1, r2)) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const compress_call_guard in_flight;
-    unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
-    const int rc = with_ticket_fallback(ctx, [&]() { *out = out0; *out_size = cap0; return dtype == SZHIP_F32
-               ? compress_impl<float>(ctx, data, data_on_device, r0, r1, r2, eb, params, meta, meta_len, out_on_device, out, out_size, stats)
-               : compress_impl<double>(ctx, data, data_on_device, r0, r1, r2, eb, params, meta, meta_len, out_on_device, out, out_size, stats); });
-    if (rc != SZHIP_OK) { if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream); } // an early exit must not leave work in flight
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return guarded_compress(ctx, out, out_size, [&]() {
+               return BY_DTYPE(dtype, compress_impl, ctx, data, data_on_device, r0, r1, r2, eb, params, meta, meta_len, out_on_device, out, out_size, stats); });
 }
 
 int szhip_compress_sz14(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -427,31 +453,21 @@ int szhip_compress_sz14(szhip_ctx *ctx, int dtype, const void *data, int data_on
                         int out_on_device, unsigned char **out, size_t *out_size, szhip_stats *stats)
 {
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
-    if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (!dims_3d_2d_1d(r0, r1, r2)) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const compress_call_guard in_flight;
-    unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
-    const int rc = with_ticket_fallback(ctx, [&]() { *out = out0; *out_size = cap0; return dtype == SZHIP_F32
-               ? compress14_impl<float>(ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, nullptr, out_on_device, out, out_size, stats)
-               : compress14_impl<double>(ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, nullptr, out_on_device, out, out_size, stats); });
-    if (rc != SZHIP_OK) { if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream); }
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return guarded_compress(ctx, out, out_size, [&]() {
+               return BY_DTYPE(dtype, compress14_impl, ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, nullptr, out_on_device, out, out_size, stats); });
 }
 
 int szhip_decompress_sz14(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
                           size_t r0, size_t r1, size_t r2, void *out, int out_on_device, szhip_stats *stats)
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
-    if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const int rc = with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
-               ? decompress14_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, 0, r0, r1, r2, out, out_on_device, stats)
-               : decompress14_impl<double>(ctx, stream, stream_on_device, stream_len, body_off, 0, r0, r1, r2, out, out_on_device, stats); });
-    if (rc != SZHIP_OK) { if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream); }
-    return rc;
+    if (!dims_3d_2d_1d(r0, r1, r2)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    return drained_on_failure(ctx, with_ticket_fallback(ctx, [&]() {
+               return BY_DTYPE(dtype, decompress14_impl, ctx, stream, stream_on_device, stream_len, body_off, 0, r0, r1, r2, out, out_on_device, stats); }));
 }
 
 int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb, int thread_num,
@@ -461,13 +477,9 @@ int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_
     if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
     if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff || thread_num < 1) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const int rc = dtype == SZHIP_F32
-               ? compress_omp_impl<float>(ctx, data, data_on_device, r0, r1, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats)
-               : compress_omp_impl<double>(ctx, data, data_on_device, r0, r1, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats);
-    if (rc != SZHIP_OK) hipStreamSynchronize(ctx->stream);
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, compress_omp_impl, ctx, data, data_on_device, r0, r1, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats));
 }
 
 int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -475,13 +487,9 @@ int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream,
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
     if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const int rc = dtype == SZHIP_F32
-               ? decompress_omp_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats)
-               : decompress_omp_impl<double>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats);
-    if (rc != SZHIP_OK) hipStreamSynchronize(ctx->stream);
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats));
 }
 
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,
@@ -489,26 +497,18 @@ int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_d
                       double *min_log_value)
 {
     if (!ctx || !data || !n || !d_log || !positive || !real_precision || !value_range || !median || !min_log_value || !(pwr_ratio > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const int rc = dtype == SZHIP_F32
-        ? pwr_prepare_impl<float>(ctx, data, data_on_device, n, vmin, vmax, pwr_ratio, d_log, signs_host, positive, real_precision, value_range, median, min_log_value)
-        : pwr_prepare_impl<double>(ctx, data, data_on_device, n, vmin, vmax, pwr_ratio, d_log, signs_host, positive, real_precision, value_range, median, min_log_value);
-    if (rc != SZHIP_OK) hipStreamSynchronize(ctx->stream);
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, pwr_prepare_impl, ctx, data, data_on_device, n, vmin, vmax, pwr_ratio, d_log, signs_host, positive, real_precision, value_range, median, min_log_value));
 }
 
 int szhip_msst_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmax, double pwr_ratio, void **d_prepared,
                        unsigned char *signs_host, int *positive, double *near_zero, double *median_log, double *min_log_value)
 {
     if (!ctx || !data || !d_prepared || !positive || !near_zero || !median_log || !min_log_value || n == 0 || !(pwr_ratio > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const int rc = dtype == SZHIP_F32
-        ? msst_prepare_impl<float>(ctx, data, data_on_device, n, vmax, pwr_ratio, d_prepared, signs_host, positive, near_zero, median_log, min_log_value)
-        : msst_prepare_impl<double>(ctx, data, data_on_device, n, vmax, pwr_ratio, d_prepared, signs_host, positive, near_zero, median_log, min_log_value);
-    if (rc != SZHIP_OK) hipStreamSynchronize(ctx->stream);
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, msst_prepare_impl, ctx, data, data_on_device, n, vmax, pwr_ratio, d_prepared, signs_host, positive, near_zero, median_log, min_log_value));
 }
 
 int szhip_compress_sz14_pwr(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -516,17 +516,11 @@ int szhip_compress_sz14_pwr(szhip_ctx *ctx, int dtype, const void *data, int dat
                             const szhip_pwr *pwr, int out_on_device, unsigned char **out, size_t *out_size, szhip_stats *stats)
 {
     if (!ctx || !data || !params || !meta || !out || !out_size || !pwr || (pwr->signs_blob_size && !pwr->signs_blob)) return SZHIP_ERR_ARG;
-    if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    if (!dims_3d_2d_1d(r0, r1, r2)) return SZHIP_ERR_ARG;
     if (!(eb > 0)) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, data)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    const compress_call_guard in_flight;
-    unsigned char *const out0 = *out; const size_t cap0 = *out_size;     // (a failed first attempt clears them: the repetition starts from the caller's values)
-    const int rc = with_ticket_fallback(ctx, [&]() { *out = out0; *out_size = cap0; return dtype == SZHIP_F32
-               ? compress14_impl<float>(ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, pwr, out_on_device, out, out_size, stats)
-               : compress14_impl<double>(ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, pwr, out_on_device, out, out_size, stats); });
-    if (rc != SZHIP_OK) { if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream); }
-    return rc;
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    return guarded_compress(ctx, out, out_size, [&]() {
+               return BY_DTYPE(dtype, compress14_impl, ctx, data, data_on_device, r0, r1, r2, eb, value_range, median, params, meta, meta_len, pwr, out_on_device, out, out_size, stats); });
 }
 
 int szhip_sz14_pwr_locate(int dtype, const unsigned char *stream, size_t stream_len, size_t body_off, size_t *blob_off, size_t *blob_size, double *min_log_value)
@@ -550,29 +544,23 @@ int szhip_decompress_sz14_pwr(szhip_ctx *ctx, int dtype, const unsigned char *st
                               size_t r0, size_t r1, size_t r2, const unsigned char *signs_host, void *out, int out_on_device, szhip_stats *stats)
 {
     if (!ctx || !stream || !out || body_off >= stream_len || stream_on_device) return SZHIP_ERR_ARG;        // the header is read on the host
-    if ((r0 != 0 && r0 < 2) || (r1 < 2 && !(r0 == 0 && r1 == 0)) || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    if (!dims_3d_2d_1d(r0, r1, r2)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, out));
     size_t bo, bs; double thr;
     if (szhip_sz14_pwr_locate(dtype, stream, stream_len, body_off, &bo, &bs, &thr) != SZHIP_OK) return SZHIP_ERR_STREAM;
     const bool msst = (stream[3] & 0x08) != 0;                   // TightDataPointStorageF.c:81
-    const int rc = with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
-               ? decompress14_pwr_impl<float>(ctx, stream, 0, stream_len, body_off, r0, r1, r2, signs_host, thr, msst, out, out_on_device, stats)
-               : decompress14_pwr_impl<double>(ctx, stream, 0, stream_len, body_off, r0, r1, r2, signs_host, thr, msst, out, out_on_device, stats); });
-    if (rc != SZHIP_OK) { if (ctx->stream3) hipStreamSynchronize(ctx->stream3); hipStreamSynchronize(ctx->stream2); hipStreamSynchronize(ctx->stream); }
-    return rc;
+    return drained_on_failure(ctx, with_ticket_fallback(ctx, [&]() {
+               return BY_DTYPE(dtype, decompress14_pwr_impl, ctx, stream, 0, stream_len, body_off, r0, r1, r2, signs_host, thr, msst, out, out_on_device, stats); }));
 }
 
 int szhip_decompress(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
                      size_t r0, size_t r1, size_t r2, void *out, int out_on_device, szhip_stats *stats)
 {
     if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
-    if ((r0 != 0 && r0 < 2) || r1 < 2 || r2 < 2 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
-    if (values_misaligned(ctx, dtype, out)) return SZHIP_ERR_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    return with_ticket_fallback(ctx, [&]() { return dtype == SZHIP_F32
-               ? decompress_impl<float>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats)
-               : decompress_impl<double>(ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats); });
+    if (!dims_3d_2d(r0, r1, r2)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    return with_ticket_fallback(ctx, [&]() {
+               return BY_DTYPE(dtype, decompress_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats); });
 }
 
 int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsigned char *out_tree, size_t out_tree_cap,

@@ -6,7 +6,7 @@
 //   | u32 ucount[nb] | T first[nb] | the boxes' verbatim values, box after box | u64 payload_bytes[nb] | the boxes' Huffman payloads
 // (the tables behind the tree in the host's byte order, as the reference memcpy's them).
 // =====================================================================================================================
-static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, size_t r2, size_t elem, szh_omp_geom *g)
+static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, size_t r2, szh_omp_geom *g)
 {
     if (thread_num < 1) FAIL(SZHIP_ERR_ARG, "thread_num %d", thread_num);
     // sz_omp.c:88-117: the exponent of two is spread over the three dimensions, dim 0 first; the rest of thread_num goes to dim 2
@@ -32,7 +32,6 @@ static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, si
     g->tile8 = (g->c0 % 8 == 0 && g->c1 % 8 == 0) ? 1 : 0;
     g->pitch = g->c1;
     if (g->tile8) while (g->pitch % 16 != 8) ++g->pitch;       // 8 or 24 modulo 32
-    (void)elem;
     return SZHIP_OK;
 }
 
@@ -42,144 +41,103 @@ static bool omp_col_applies(const szh_omp_geom &g, const void *base, size_t row_
     return g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0 && ((uintptr_t)base & 15u) == 0 && row_pitch_bytes % 16 == 0;
 }
 
+// One compress call into the OpenMP container: its state, and one member function per phase (compress_omp_impl is their sequence).
 template <class T>
-int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, int thread_num,
-                      const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device, unsigned char **out, size_t *out_size,
-                      szhip_stats *stats)
-{
-    szh_omp_geom g;
-    TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, sizeof(T), &g));
-    const szh_geom3 G = szh_make_geom3((int)r0, (int)r1, (int)r2);
-    const int64_t n = G.n;
-    const T eb = (T)eb_in;                                     // `float realPrecision` of sz_omp.c:63 (double: :578)
-    if (!(eb > 0)) FAIL(SZHIP_ERR_ARG, "error bound %g", eb_in);
-    const double t_begin = now_ms();
-    double host_ms = 0;
-    hipStream_t st = ctx->stream;
-    szhip_stats S; memset(&S, 0, sizeof(S));
-    S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb;
-    const T *d_in = (const T *)data;
-    if (!data_on_device) {
-        TRY(ensure(ctx, ctx->in, (size_t)n * sizeof(T)));
-        TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-        d_in = (const T *)ctx->in.p;
-    }
-    if ((uintptr_t)d_in & 15u) g.vec = 0;
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-    // ---- interval count (sz_omp.c:73-82: optimize_intervals_float_3D_opt over the whole array when it is not fixed)
-    unsigned intervals = prm->quantization_intervals;
-    if (intervals == 0) {
-        const unsigned max_radius = prm->max_quant_intervals / 2;
-        TRY(ensure(ctx, ctx->hist, (size_t)(max_radius + 8192) * 4 + 64));
-        TRY(ensure_pinned(ctx, (size_t)(max_radius + 8192) * 4 + 64));
-        unsigned *d_rh = (unsigned *)ctx->hist.p, *d_fh = d_rh + max_radius;
-        HIPCHK(hipMemsetAsync(d_rh, 0, (size_t)(max_radius + 8192) * 4, st));
-        const int64_t nrows = szh_sample_row_limit(G, prm->sample_distance);
-        if (G.g0.count <= 1 || G.g1.count <= 1) {                   // a degenerate 3-D array: the reference's walk, literally (k_sample_walk)
-            hipLaunchKernelGGL((k_sample_walk<T, false>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)0, max_radius, d_rh, d_fh, sm + SM_WITHIN);
-            HIPCHK(hipGetLastError());
-        } else if (nrows > 0) {
-            int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-            hipLaunchKernelGGL((k_sample<T, false>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb, (T)0,
-                               max_radius, d_rh, d_fh, sm + SM_WITHIN);
-            HIPCHK(hipGetLastError());
-        }
-        unsigned *h_rh = (unsigned *)ctx->pinned;
-        HIPCHK(hipMemcpyAsync(h_rh, d_rh, (size_t)max_radius * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        double h0 = now_ms();
-        u64 total = 0;
-        for (unsigned i = 0; i < max_radius; ++i) total += h_rh[i];
-        const size_t target = (size_t)((float)total * prm->pred_threshold);
-        size_t sum = 0; unsigned i = 0;
-        for (; i < max_radius; ++i) { sum += h_rh[i]; if (sum > target) break; }
-        if (i >= max_radius) i = max_radius - 1;
-        unsigned p2 = 2 * (i + 1); p2 -= 1; p2 |= p2 >> 1; p2 |= p2 >> 2; p2 |= p2 >> 4; p2 |= p2 >> 8; p2 |= p2 >> 16; p2 += 1;
-        intervals = p2 < 32 ? 32 : p2;
-        host_ms += now_ms() - h0;
-    }
-    if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
-    S.intervals = intervals;
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
+struct omp_call : call_base {
+    // ---- arguments, geometry
+    const szhip_params *const prm; const unsigned char *const meta; const size_t meta_len;
+    const int out_on_device; unsigned char **const out; size_t *const out_size;
+    const T eb;                                                // `float realPrecision` of sz_omp.c:63 (double: :578)
+    szh_omp_geom g; const szh_geom3 G; const size_t row_bytes; const int64_t n = G.n;
+    // ---- device arrays
+    const T *d_in = nullptr; u64 *sm = nullptr; uint16_t *d_codes = nullptr; unsigned char *d_stream = nullptr;
+    unsigned *d_ucount = nullptr, *d_hist_box = nullptr; T *d_first = nullptr; u64 *d_ucount64 = nullptr, *d_uoff = nullptr, *d_box_bytes = nullptr, *d_box_off = nullptr;
+    // ---- decisions
+    unsigned intervals = 0; bool box_hist = false, sweep_counted = true;
+    // ---- the code book and the stream's layout
+    std::vector<u64> tab_code; std::vector<uint8_t> tab_len; unsigned maxlen = 0; u64 total_bits = 0, E = 0;
+    std::vector<unsigned char> hdr;
+    size_t hdr_len = 0, off_ucount = 0, off_first = 0, off_unpred = 0, off_sizes = 0, off_pay = 0, cap_len = 0;
 
+    // ---- the array staged; interval count (sz_omp.c:73-82: optimize_intervals_float_3D_opt over the whole array when it is not fixed)
+    int choose_intervals(const void *data, int data_on_device) {
+        S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb;
+        TRY(stage_input(ctx, data, data_on_device, (size_t)n, &d_in));
+        if ((uintptr_t)d_in & 15u) g.vec = 0;
+        TRY(clear_small(ctx, &sm));
+        HIPCHK(hipEventRecord(ctx->ev[0], st));
+        intervals = prm->quantization_intervals;
+        if (intervals == 0) TRY(sampled_intervals<T>(ctx, G, false, d_in, prm, eb, sm, &intervals, &host_ms));
+        if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
+        S.intervals = intervals;
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        return SZHIP_OK;
+    }
     // ---- the boxes: predict + quantise
-    TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
-    uint16_t *d_codes = (uint16_t *)ctx->codes_nat.p;
-    TRY(ensure(ctx, ctx->zcnt, (size_t)g.nb * 4));
-    TRY(ensure(ctx, ctx->samples, (size_t)g.nb * sizeof(T)));
-    TRY(ensure(ctx, ctx->col_zeros64, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)g.nb * 8 + 8));
-    unsigned *d_ucount = (unsigned *)ctx->zcnt.p; T *d_first = (T *)ctx->samples.p;
-    u64 *d_ucount64 = (u64 *)ctx->col_zeros64.p, *d_uoff = (u64 *)ctx->col_off.p;
-    const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
-    const bool box_hist = intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
-    bool sweep_counted = true;
-    HIPCHK(hipEventRecord(ctx->ev[2], st));
-    if (omp_col_applies(g, d_in, r2 * sizeof(T))) {        // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
-        szh_oc::sweep_args<T> oa;
-        oa.g = g; oa.data = d_in; oa.out = nullptr; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
-        oa.ucount = d_ucount; oa.ucount64 = d_ucount64; oa.first = d_first; oa.uoff = nullptr; oa.vflags = nullptr; oa.fw = 0;
-        // (with a histogram per box coming anyway, the boxes' counts of verbatim values are its bins 0: the sweep leaves the counting out --
-        //  two vector instructions per step of a kernel that is bound by exactly those)
-        if (box_hist) { sweep_counted = false; hipLaunchKernelGGL((k_omp_col<T, 32, 32, false, false>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa); }
-        else hipLaunchKernelGGL((k_omp_col<T, 32, 32, false, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
-    } else if (g.vec) hipLaunchKernelGGL((k_omp_box<T, false, true>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, d_in, (T *)nullptr, eb, (T)(1 / eb),
-                                  (int)intervals, d_codes, d_ucount, d_ucount64, d_first, (const T *)nullptr, (const u64 *)nullptr);
-    else hipLaunchKernelGGL((k_omp_box<T, false, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, d_in, (T *)nullptr, eb, (T)(1 / eb),
-                            (int)intervals, d_codes, d_ucount, d_ucount64, d_first, (const T *)nullptr, (const u64 *)nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[3], st));
-    S.quant_kernel_launches = 1;
-    S.quant_kernel = omp_col_applies(g, d_in, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);      // (szhip.h: which form the address and the box shape allowed)
-
-    // ---- ONE histogram over all boxes -> code book (host); the ranks of the boxes' verbatim values meanwhile.  Small alphabets: a
-    // histogram per box on the way (k_omp_hist_box), from which the boxes' payload sizes follow without another pass over the codes
-    TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
-    unsigned *d_hist = (unsigned *)ctx->hist.p;
-    TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
-    unsigned *h_hist = (unsigned *)ctx->pinned;
-    HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
-    unsigned *d_hist_box = nullptr;
-    if (box_hist) {
-        TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * intervals * 4));
-        d_hist_box = (unsigned *)ctx->chunk_bits.p;
-        // lane-private copies of the bins against same-address atomics -- but no more copies than the box has codes to spread over them
-        // (a box of 4096 codes with 64 copies of 32 bins spent its time clearing and summing 32 KB: 0.40 ms for 32 768 such boxes)
-        int rshift = 0;
-        while ((intervals << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)intervals << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
-        const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
-        hipLaunchKernelGGL(k_omp_hist_box, dim3((unsigned)((g.nb + hist_per_wg - 1) / hist_per_wg)), dim3(256), ((size_t)intervals << rshift) * 4, st, g.bel, (const uint16_t *)d_codes, intervals, rshift,
-                           d_hist_box, d_hist, sweep_counted ? (unsigned *)nullptr : d_ucount, sweep_counted ? (u64 *)nullptr : d_ucount64, g.nb, hist_per_wg);
+    int quantise() {
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
+        d_codes = (uint16_t *)ctx->codes_nat.p;
+        TRY(ensure(ctx, ctx->zcnt, (size_t)g.nb * 4));
+        TRY(ensure(ctx, ctx->samples, (size_t)g.nb * sizeof(T)));
+        TRY(ensure(ctx, ctx->col_zeros64, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)g.nb * 8 + 8));
+        d_ucount = (unsigned *)ctx->zcnt.p; d_first = (T *)ctx->samples.p;
+        d_ucount64 = (u64 *)ctx->col_zeros64.p; d_uoff = (u64 *)ctx->col_off.p;
+        const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
+        box_hist = intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
+        HIPCHK(hipEventRecord(ctx->ev[2], st));
+        if (omp_col_applies(g, d_in, row_bytes)) {             // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
+            szh_oc::sweep_args<T> oa;
+            oa.g = g; oa.data = d_in; oa.out = nullptr; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
+            oa.ucount = d_ucount; oa.ucount64 = d_ucount64; oa.first = d_first; oa.uoff = nullptr; oa.vflags = nullptr; oa.fw = 0;
+            // (with a histogram per box coming anyway, the boxes' counts of verbatim values are its bins 0: the sweep leaves the counting out --
+            //  two vector instructions per step of a kernel that is bound by exactly those)
+            if (box_hist) { sweep_counted = false; hipLaunchKernelGGL((k_omp_col<T, 32, 32, false, false>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa); }
+            else hipLaunchKernelGGL((k_omp_col<T, 32, 32, false, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
+        } else hipLaunchKernelGGL((g.vec ? k_omp_box<T, false, true> : k_omp_box<T, false, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, d_in,
+                                  (T *)nullptr, eb, (T)(1 / eb), (int)intervals, d_codes, d_ucount, d_ucount64, d_first, (const T *)nullptr, (const u64 *)nullptr);
         HIPCHK(hipGetLastError());
-    } else {
-        int rshift = 0; int use_lds = intervals <= 16384;
-        if (use_lds) { while ((intervals << (rshift + 1)) <= 16384u && rshift < 6) ++rshift; }
-        const size_t lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
-        int grid = (int)std::min<int64_t>((n / 8 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), lds, st, (const uint16_t *)d_codes, n, intervals, rshift, use_lds, d_hist, (int64_t)0);
-        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[3], st));
+        S.quant_kernel_launches = 1;
+        S.quant_kernel = omp_col_applies(g, d_in, row_bytes) ? 3 : (g.vec ? 4 : 5);      // (szhip.h: which form the address and the box shape allowed)
+        return SZHIP_OK;
     }
-    HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
-    if (!box_hist) TRY(scan_u64(ctx, (const u64 *)d_ucount64, g.nb, d_uoff, sm + SM_TOTAL_UNPRED));      // (with per-box histograms: in k_omp_layout, below)
-    HIPCHK(hipStreamSynchronize(st));
-    const u64 E = h_hist[0];
-    S.n_unpred = E;
-    double h0 = now_ms();
-    szhost_huff *hf = szhost_huff_build(2 * (int)intervals, h_hist, nullptr, intervals);
-    if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
-    const size_t tree_bytes = szhost_huff_tree_size(hf);
-    const u64 total_bits = hf->total_bits;
-    std::vector<u64> tab_code(intervals); std::vector<uint8_t> tab_len(intervals);
-    for (unsigned s2 = 0; s2 < intervals; ++s2) { tab_code[s2] = hf->code[s2]; tab_len[s2] = hf->len[s2]; }
-    // ---- container: everything up to the payloads has a known size now; the payloads take at most a byte of padding per box
-    const size_t hdr_len = meta_len + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes;
-    const size_t off_ucount = hdr_len, off_first = off_ucount + (size_t)g.nb * 4, off_unpred = off_first + (size_t)g.nb * sizeof(T);
-    const size_t off_sizes = off_unpred + (size_t)E * sizeof(T), off_pay = off_sizes + (size_t)g.nb * 8;
-    const size_t cap_len = off_pay + (size_t)((total_bits + 7) / 8) + (size_t)g.nb;
-    std::vector<unsigned char> hdr(hdr_len, 0);
-    {
+    // ---- ONE histogram over all boxes -> code book (host); the ranks of the boxes' verbatim values meanwhile.  Small alphabets: a
+    // histogram per box on the way (k_omp_hist_box), from which the boxes' payload sizes follow without another pass over the codes.
+    // Then the container: everything up to the payloads has a known size; the payloads take at most a byte of padding per box
+    int hist_and_book() {
+        TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
+        unsigned *d_hist = (unsigned *)ctx->hist.p;
+        TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
+        unsigned *h_hist = (unsigned *)ctx->pinned;
+        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
+        if (box_hist) {
+            TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * intervals * 4));
+            d_hist_box = (unsigned *)ctx->chunk_bits.p;
+            // lane-private copies of the bins against same-address atomics -- but no more copies than the box has codes to spread over them
+            // (a box of 4096 codes with 64 copies of 32 bins spent its time clearing and summing 32 KB: 0.40 ms for 32 768 such boxes)
+            int rshift = 0;
+            while ((intervals << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)intervals << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
+            const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
+            hipLaunchKernelGGL(k_omp_hist_box, dim3((unsigned)((g.nb + hist_per_wg - 1) / hist_per_wg)), dim3(256), ((size_t)intervals << rshift) * 4, st, g.bel, (const uint16_t *)d_codes, intervals, rshift,
+                               d_hist_box, d_hist, sweep_counted ? (unsigned *)nullptr : d_ucount, sweep_counted ? (u64 *)nullptr : d_ucount64, g.nb, hist_per_wg);
+            HIPCHK(hipGetLastError());
+        } else
+            TRY(launch_hist_u16(ctx, st, d_codes, 0, n, intervals, d_hist));
+        HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
+        if (!box_hist) TRY(scan_u64(ctx, (const u64 *)d_ucount64, g.nb, d_uoff, sm + SM_TOTAL_UNPRED));      // (with per-box histograms: in k_omp_layout, below)
+        HIPCHK(hipStreamSynchronize(st));
+        E = h_hist[0];
+        S.n_unpred = E;
+        const double h0 = now_ms();
+        const huff_ptr hf = host_book(h_hist, intervals, tab_code, tab_len, &maxlen);
+        if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
+        const size_t tree_bytes = szhost_huff_tree_size(hf.get());
+        total_bits = hf->total_bits;
+        hdr_len = meta_len + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes;
+        off_ucount = hdr_len; off_first = off_ucount + (size_t)g.nb * 4; off_unpred = off_first + (size_t)g.nb * sizeof(T);
+        off_sizes = off_unpred + (size_t)E * sizeof(T); off_pay = off_sizes + (size_t)g.nb * 8;
+        cap_len = off_pay + (size_t)((total_bits + 7) / 8) + (size_t)g.nb;
+        hdr.assign(hdr_len, 0);
         unsigned char *q = hdr.data();
         memcpy(q, meta, meta_len); q += meta_len;
         szhost_put_u32be(q, (uint32_t)g.nb); q += 4;              // (`thread_num` after the grid has been cut: sz_omp.c:122)
@@ -188,23 +146,25 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
         szhost_put_u32be(q, intervals); q += 4;
         szhost_put_u32be(q, (uint32_t)tree_bytes); q += 4;
         szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;
-        szhost_huff_tree_write(hf, q);
+        szhost_huff_tree_write(hf.get(), q);
+        host_ms += now_ms() - h0;
+        return SZHIP_OK;
     }
-    szhost_huff_free(hf);
-    host_ms += now_ms() - h0;
-    unsigned maxlen = 0;
-    for (unsigned s2 = 0; s2 < intervals; ++s2) maxlen = std::max<unsigned>(maxlen, tab_len[s2]);
-    TRY(ensure(ctx, ctx->stream_buf, cap_len + 64));
-    unsigned char *d_stream = (unsigned char *)ctx->stream_buf.p;
-    HIPCHK(hipMemsetAsync(d_stream, 0, cap_len + 64, st));
-    TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8));
-    u64 *d_box_bytes = (u64 *)ctx->reg_flags.p, *d_box_off = (u64 *)ctx->reg_rank.p;
-    const size_t lds3 = (size_t)intervals * 8 + ((size_t)SZH_OMP_R3 * maxlen / 32 + 4) * 4 + 16;
-    const bool fast = box_hist && maxlen <= 32 && intervals <= 2048 && lds3 <= 60 * 1024;
-    if (fast) {
-        // ---- the usual case (code words of at most 32 bits, a histogram per box): ONE upload -- the header and the packed code table
-        // `code << 8 | len` --, one launch for the boxes' sizes and places (k_omp_layout), one that packs the codes and writes every table
-        // of the stream itself (k_omp_encode_box3).  (Round 4, first form: 8 copies / fills and 8 small launches here, ~0.1 ms of gaps.)
+    // ---- packing: the boxes' payloads and every table of the stream into the stream buffer
+    int pack() {
+        TRY(ensure(ctx, ctx->stream_buf, cap_len + 64));
+        d_stream = (unsigned char *)ctx->stream_buf.p;
+        HIPCHK(hipMemsetAsync(d_stream, 0, cap_len + 64, st));
+        TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8));
+        d_box_bytes = (u64 *)ctx->reg_flags.p; d_box_off = (u64 *)ctx->reg_rank.p;
+        const size_t lds3 = (size_t)intervals * 8 + ((size_t)SZH_OMP_R3 * maxlen / 32 + 4) * 4 + 16;
+        const bool fast = box_hist && maxlen <= 32 && intervals <= 2048 && lds3 <= 60 * 1024;
+        return fast ? pack_fast(lds3) : pack_general();
+    }
+    // the usual case (code words of at most 32 bits, a histogram per box): ONE upload -- the header and the packed code table
+    // `code << 8 | len` --, one launch for the boxes' sizes and places (k_omp_layout), one that packs the codes and writes every table
+    // of the stream itself (k_omp_encode_box3).  (Round 4, first form: 8 copies / fills and 8 small launches here, ~0.1 ms of gaps.)
+    int pack_fast(size_t lds3) {
         const size_t hdr_pad = (hdr_len + 7) / 8 * 8, blob = hdr_pad + (size_t)intervals * 8;
         TRY(ensure_pinned3(ctx, blob));
         unsigned char *hb = (unsigned char *)ctx->pinned3;
@@ -230,209 +190,209 @@ int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
         // (the verbatim values go through an aligned buffer: their table lies at whatever byte offset the tree's size gives it, and byte
         //  stores from the kernel were half of its 0.1 ms for them)
         if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
-    } else {
-        TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
-        TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
-        HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
+        return SZHIP_OK;
+    }
+    // the first form: tables copied one by one; the boxes' payload sizes (from their histograms, or one more pass over the codes), their places, then
+    // ONE pass that packs every box's codes behind a running bit position and drops its verbatim values into the table on the way
+    int pack_general() {
+        TRY(upload_code_tables(ctx, tab_code, tab_len));
         HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_stream + off_ucount, d_ucount, (size_t)g.nb * 4, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(d_stream + off_first, d_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
         if (box_hist) TRY(scan_u64(ctx, (const u64 *)d_ucount64, g.nb, d_uoff, sm + SM_TOTAL_UNPRED));
-        // the boxes' payload sizes (from their histograms, or one more pass over the codes), their places, then ONE pass that packs every
-        // box's codes behind a running bit position and drops its verbatim values into the table on the way
         TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
         if (box_hist) hipLaunchKernelGGL(k_omp_box_bits_h, dim3((unsigned)((g.nb + 3) / 4)), dim3(256), 0, st, g.nb, intervals, (const unsigned *)d_hist_box, (const uint8_t *)ctx->len_tab.p, d_box_bytes);
         else hipLaunchKernelGGL(k_omp_box_bits_c, dim3((unsigned)g.nb), dim3(256), 0, st, g.bel, (const uint16_t *)d_codes, (const uint8_t *)ctx->len_tab.p, d_box_bytes);
         HIPCHK(hipGetLastError());
         TRY(scan_u64(ctx, (const u64 *)d_box_bytes, g.nb, d_box_off, sm + SM_SCRATCH));
         HIPCHK(hipMemcpyAsync(d_stream + off_sizes, d_box_bytes, (size_t)g.nb * 8, hipMemcpyDeviceToDevice, st));
-        if (intervals <= 2048)
-            hipLaunchKernelGGL((k_omp_encode_box<T, true>), dim3((unsigned)g.nb), dim3(256), (size_t)intervals * 9 + 16, st, g, d_in, (const uint16_t *)d_codes, (const u64 *)ctx->code_tab.p,
-                               (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)d_box_off, (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8,
-                               (unsigned *)d_stream, (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR));
-        else
-            hipLaunchKernelGGL((k_omp_encode_box<T, false>), dim3((unsigned)g.nb), dim3(256), 16, st, g, d_in, (const uint16_t *)d_codes, (const u64 *)ctx->code_tab.p,
-                               (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)d_box_off, (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8,
-                               (unsigned *)d_stream, (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR));
+        const bool tab_lds = intervals <= 2048;                  // the code table in LDS when it fits
+        hipLaunchKernelGGL((tab_lds ? k_omp_encode_box<T, true> : k_omp_encode_box<T, false>), dim3((unsigned)g.nb), dim3(256), (tab_lds ? (size_t)intervals * 9 : 0) + 16, st, g, d_in, (const uint16_t *)d_codes,
+                           (const u64 *)ctx->code_tab.p, (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)d_box_off, (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8,
+                           (unsigned *)d_stream, (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR));
         HIPCHK(hipGetLastError());
         if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        return SZHIP_OK;
     }
-    HIPCHK(hipEventRecord(ctx->ev[4], st));
-    u64 h_small[SM_COUNT];
-    HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h_small[SM_TOTAL_UNPRED] != E || (unsigned)h_small[SM_ERR] != 0 ||
-        h_small[SM_SCRATCH] < (total_bits + 7) / 8 || h_small[SM_SCRATCH] > (total_bits + 7) / 8 + (u64)g.nb)
-        FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: entropy stage mismatch");
-    const size_t total_len = off_pay + (size_t)h_small[SM_SCRATCH];
-    if (total_len > cap_len) FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: payloads larger than their bound");
-    if (out_on_device == 2) {
-        if (!*out || *out_size < total_len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, total_len);
-        HIPCHK(hipMemcpyAsync(*out, d_stream, total_len, hipMemcpyDeviceToDevice, st));
+    // ---- the end of the entropy stage; the device's counts against the book's, delivery, the statistics
+    int check_and_deliver() {
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        u64 h_small[SM_COUNT];
+        HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-    } else if (out_on_device) {
-        *out = d_stream;
-    } else {
-        unsigned char *h = (unsigned char *)malloc(total_len ? total_len : 1);
-        if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
-        const int rc_copy = staged_copy(ctx, h, d_stream, total_len, false);
-        if (rc_copy != SZHIP_OK || hipStreamSynchronize(st) != hipSuccess) { free(h); FAIL(rc_copy != SZHIP_OK ? rc_copy : SZHIP_ERR_NODEVICE, "copying the stream to the host failed"); }
-        *out = h;
+        if (h_small[SM_TOTAL_UNPRED] != E || (unsigned)h_small[SM_ERR] != 0 ||
+            h_small[SM_SCRATCH] < (total_bits + 7) / 8 || h_small[SM_SCRATCH] > (total_bits + 7) / 8 + (u64)g.nb)
+            FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: entropy stage mismatch");
+        const size_t total_len = off_pay + (size_t)h_small[SM_SCRATCH];
+        if (total_len > cap_len) FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: payloads larger than their bound");
+        TRY(deliver_stream(ctx, d_stream, total_len, out_on_device, out, out_size, false, true));
+        if (!out_on_device && hipStreamSynchronize(st) != hipSuccess) FAIL_PUBLISHED(SZHIP_ERR_NODEVICE, "copying the stream to the host failed");
+        compress_times(ctx, S, host_ms, t_begin, total_len);
+        return SZHIP_OK;
     }
-    *out_size = total_len;
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
-    S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = total_len;
-    if (stats) *stats = S;
-    return SZHIP_OK;
+};
+
+template <class T>
+int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, int thread_num,
+                      const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device, unsigned char **out, size_t *out_size,
+                      szhip_stats *stats)
+{
+    szh_omp_geom g;
+    TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+    if (!((T)eb_in > 0)) FAIL(SZHIP_ERR_ARG, "error bound %g", eb_in);
+    omp_call<T> c{call_base(ctx), prm, meta, meta_len, out_on_device, out, out_size, (T)eb_in, g, szh_make_geom3((int)r0, (int)r1, (int)r2), r2 * sizeof(T)};
+    TRY(c.choose_intervals(data, data_on_device));
+    TRY(c.quantise());
+    TRY(c.hist_and_book());
+    TRY(c.pack());
+    TRY(c.check_and_deliver());
+    return c.done(stats);
 }
 
-// `body_off`: offset of the thread_num field (4 + MetaDataByteLength: what decompressDataSeries_*_3D_openmp is handed)
+// One decompress call of the OpenMP container.  `body_off`: offset of the thread_num field (4 + MetaDataByteLength: what decompressDataSeries_*_3D_openmp is handed)
 template <class T>
-int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_on_device, size_t stream_len, size_t body_off, size_t r0, size_t r1, size_t r2,
-                        void *out, int out_on_device, szhip_stats *stats)
-{
-    const double t_begin = now_ms();
-    hipStream_t st = ctx->stream;
-    szhip_stats S; memset(&S, 0, sizeof(S));
-    TRY(ensure(ctx, ctx->stream_buf, stream_len + 64));
-    unsigned char *d_stream = (unsigned char *)ctx->stream_buf.p;
-    if (stream_on_device) { if (stream_in != d_stream) HIPCHK(hipMemcpyAsync(d_stream, stream_in, stream_len, hipMemcpyDeviceToDevice, st)); }
-    else TRY(staged_copy(ctx, d_stream, stream_in, stream_len, true));
-    HIPCHK(hipMemsetAsync(d_stream + stream_len, 0, 64, st));
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-    std::vector<unsigned char> hbuf;
-    const unsigned char *hs = stream_in;
-    auto fetch = [&](size_t want) -> int {                    // the first `want` bytes of the stream on the host
-        if (want > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-        if (!stream_on_device) return SZHIP_OK;
-        hbuf.resize(want);
-        HIPCHK(hipMemcpyAsync(hbuf.data(), d_stream, want, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        hs = hbuf.data();
+struct omp_dec : call_base {
+    // ---- arguments
+    const size_t stream_len, body_off, r0, r1, r2; void *const out; const int out_on_device;
+    stream_intake in;
+    // ---- the header and the tables behind it
+    szh_omp_geom g; int64_t n = 0; T eb = 0; unsigned intervals = 0; u64 E = 0;
+    size_t off_first = 0, off_unpred = 0, off_pay = 0;
+    dec_table D;
+    std::vector<u64> uoff, bbytes, boff;
+    // ---- device arrays
+    u64 *sm = nullptr; uint16_t *d_codes = nullptr; T *d_out = nullptr;
+
+    // ---- the stream taken in; the fixed fields, the box grid, the tree, the boxes' counts of verbatim values and payload sizes: on the host
+    int read_header() {
+        TRY(in.open());
+        const size_t fixed = body_off + 4 + sizeof(T) + 12;
+        TRY(in.fetch(fixed));
+        const unsigned char *q = in.hs + body_off;
+        const int thread_num = (int)szhost_get_u32be(q); q += 4;
+        eb = sizeof(T) == 8 ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
+        intervals = szhost_get_u32be(q); q += 4;
+        const size_t tree_bytes = szhost_get_u32be(q); q += 4;
+        const int node_count = (int)szhost_get_u32be(q); q += 4;
+        if (intervals < 4 || intervals > 65536 || !(eb > 0)) FAIL(SZHIP_ERR_STREAM, "bad OpenMP-container header");
+        if (node_count <= 0 || tree_bytes > stream_len || szhost_huff_serial_size(node_count) > tree_bytes) FAIL(SZHIP_ERR_STREAM, "truncated stream");
+        TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+        if (g.nb != thread_num) FAIL(SZHIP_ERR_STREAM, "thread_num %d is not a box grid", thread_num);
+        n = (int64_t)r0 * r1 * r2;
+        S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb; S.intervals = intervals;
+        const size_t off_ucount = fixed + tree_bytes;
+        off_first = off_ucount + (size_t)g.nb * 4; off_unpred = off_first + (size_t)g.nb * sizeof(T);
+        TRY(in.fetch(off_unpred));
+        if (!read_tree(in.hs + fixed, node_count, intervals, D)) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
+        uoff.assign((size_t)g.nb + 1, 0);
+        for (int b = 0; b < g.nb; ++b) { uint32_t c; memcpy(&c, in.hs + off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)g.bel) FAIL(SZHIP_ERR_STREAM, "bad verbatim-value count"); uoff[b + 1] = uoff[b] + c; }
+        E = uoff[g.nb];
+        S.n_unpred = E;
+        const size_t off_sizes = off_unpred + (size_t)E * sizeof(T);
+        off_pay = off_sizes + (size_t)g.nb * 8;
+        if (off_pay > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
+        bbytes.resize((size_t)g.nb); boff.resize((size_t)g.nb);
+        if (in.on_device) { HIPCHK(hipMemcpyAsync(bbytes.data(), in.d_stream + off_sizes, (size_t)g.nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
+        else memcpy(bbytes.data(), in.stream_in + off_sizes, (size_t)g.nb * 8);
+        u64 acc = 0;
+        for (int b = 0; b < g.nb; ++b) { boff[b] = acc; if (bbytes[b] > stream_len || bbytes[b] >= ((u64)1 << 28)) FAIL(SZHIP_ERR_STREAM, "bad payload size"); acc += bbytes[b]; }
+        if (off_pay + acc > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
         return SZHIP_OK;
-    };
-    const size_t fixed = body_off + 4 + sizeof(T) + 12;
-    TRY(fetch(fixed));
-    const unsigned char *q = hs + body_off;
-    const int thread_num = (int)szhost_get_u32be(q); q += 4;
-    const T eb = sizeof(T) == 8 ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
-    const unsigned intervals = szhost_get_u32be(q); q += 4;
-    const size_t tree_bytes = szhost_get_u32be(q); q += 4;
-    const int node_count = (int)szhost_get_u32be(q); q += 4;
-    if (intervals < 4 || intervals > 65536 || !(eb > 0)) FAIL(SZHIP_ERR_STREAM, "bad OpenMP-container header");
-    if (node_count <= 0 || tree_bytes > stream_len || szhost_huff_serial_size(node_count) > tree_bytes) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-    szh_omp_geom g;
-    TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, sizeof(T), &g));
-    if (g.nb != thread_num) FAIL(SZHIP_ERR_STREAM, "thread_num %d is not a box grid", thread_num);
-    const int64_t n = (int64_t)r0 * r1 * r2;
-    S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb; S.intervals = intervals;
-    const size_t off_ucount = fixed + tree_bytes, off_first = off_ucount + (size_t)g.nb * 4, off_unpred = off_first + (size_t)g.nb * sizeof(T);
-    TRY(fetch(off_unpred));
-    szhost_huff *hf = szhost_huff_from_bytes(2 * (int)intervals, hs + fixed, node_count);
-    if (!hf) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
-    std::vector<uint32_t> dtab((size_t)hf->n_nodes * 2);
-    szhost_huff_decode_table(hf, dtab.data());
-    const int single_symbol = hf->t[0] ? (int)hf->C[0] : -1;
-    const int n_nodes_dec = hf->n_nodes;
-    szhost_huff_free(hf);
-    std::vector<u64> uoff((size_t)g.nb + 1, 0);
-    for (int b = 0; b < g.nb; ++b) { uint32_t c; memcpy(&c, hs + off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)g.bel) FAIL(SZHIP_ERR_STREAM, "bad verbatim-value count"); uoff[b + 1] = uoff[b] + c; }
-    const u64 E = uoff[g.nb];
-    S.n_unpred = E;
-    const size_t off_sizes = off_unpred + (size_t)E * sizeof(T), off_pay = off_sizes + (size_t)g.nb * 8;
-    if (off_pay > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-    std::vector<u64> bbytes((size_t)g.nb), boff((size_t)g.nb);
-    if (stream_on_device) { HIPCHK(hipMemcpyAsync(bbytes.data(), d_stream + off_sizes, (size_t)g.nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
-    else memcpy(bbytes.data(), stream_in + off_sizes, (size_t)g.nb * 8);
-    u64 acc = 0;
-    for (int b = 0; b < g.nb; ++b) { boff[b] = acc; if (bbytes[b] > stream_len || bbytes[b] >= ((u64)1 << 28)) FAIL(SZHIP_ERR_STREAM, "bad payload size"); acc += bbytes[b]; }
-    if (off_pay + acc > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-    // ---- device tables: payload offsets / sizes, ranks of the verbatim values, first values and verbatim values at aligned addresses
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
-    TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)g.nb * 8 + 8));
-    TRY(ensure(ctx, ctx->samples, (size_t)g.nb * sizeof(T))); TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
-    TRY(ensure(ctx, ctx->dec_tab, (dtab.size() * 4 + 63) / 64 * 64 + SZH_LUT_BYTES + 16));
-    HIPCHK(hipMemcpyAsync(ctx->reg_flags.p, bbytes.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->reg_rank.p, boff.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->col_off.p, uoff.data(), ((size_t)g.nb + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, dtab.data(), dtab.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->samples.p, d_stream + off_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (E > 0) HIPCHK(hipMemcpyAsync(ctx->unpred.p, d_stream + off_unpred, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
-    TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
-    uint16_t *d_codes = (uint16_t *)ctx->codes_nat.p;
-    {
+    }
+    // ---- device tables: payload offsets / sizes, ranks of the verbatim values, first values and verbatim values at aligned addresses; then the Huffman decode,
+    // a workgroup per box
+    int decode_boxes() {
+        TRY(clear_small(ctx, &sm));
+        TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)g.nb * 8 + 8));
+        TRY(ensure(ctx, ctx->samples, (size_t)g.nb * sizeof(T))); TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
+        TRY(ensure(ctx, ctx->dec_tab, (D.dtab.size() * 4 + 63) / 64 * 64 + SZH_LUT_BYTES + 16));
+        HIPCHK(hipMemcpyAsync(ctx->reg_flags.p, bbytes.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->reg_rank.p, boff.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->col_off.p, uoff.data(), ((size_t)g.nb + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, D.dtab.data(), D.dtab.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->samples.p, in.d_stream + off_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (E > 0) HIPCHK(hipMemcpyAsync(ctx->unpred.p, in.d_stream + off_unpred, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
+        d_codes = (uint16_t *)ctx->codes_nat.p;
         u64 max_box = 0;
         for (int b = 0; b < g.nb; ++b) max_box = std::max(max_box, bbytes[b]);
         // the look-up-table decoder (hdec_run_lut) when a box's payload, the table and the node table fit a workgroup's LDS
         const unsigned stage_bytes = (unsigned)((max_box + 30 + 15) / 16 * 16 + 16);
         const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
-        const int tab_lds_lut = (size_t)n_nodes_dec * 8 <= 13 * 1024;
-        const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds_lut ? ((size_t)n_nodes_dec * 8 + 15) / 16 * 16 : 0);
-        if (single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024) {
-            const size_t lut_off = (dtab.size() * 4 + 63) / 64 * 64;
-            TRY(ensure(ctx, ctx->dec_tab, lut_off + SZH_LUT_BYTES));          // (grown before the table went up: see the copy above)
+        const int tab_lds_lut = (size_t)D.n_nodes * 8 <= 13 * 1024;
+        const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds_lut ? ((size_t)D.n_nodes * 8 + 15) / 16 * 16 : 0);
+        if (D.single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024) {
+            const size_t lut_off = (D.dtab.size() * 4 + 63) / 64 * 64;
+            TRY(ensure(ctx, ctx->dec_tab, lut_off + SZH_LUT_BYTES));          // (grown before the table went up: above)
             hipLaunchKernelGGL(k_hdec_build_lut, dim3(SZH_LUT_SIZE / 256), dim3(256), 0, st, (const unsigned *)ctx->dec_tab.p, (uint4 *)((char *)ctx->dec_tab.p + lut_off));
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)g.nb), dim3(256), lds_lut, st, g.bel, (const unsigned char *)(d_stream + off_pay), (unsigned)off_pay,
-                               (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, n_nodes_dec, tab_lds_lut,
+            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)g.nb), dim3(256), lds_lut, st, g.bel, (const unsigned char *)(in.d_stream + off_pay), (unsigned)off_pay,
+                               (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds_lut,
                                (const uint4 *)((char *)ctx->dec_tab.p + lut_off), stage_bytes, d_codes, (unsigned *)(sm + SM_ERR));
         } else {
-        const int tab_lds = dtab.size() * 4 <= 16384;            // node table and payload in LDS when they are small (the usual case: 2 - 3 bits per code)
-        const unsigned pay_cap = (unsigned)std::min<u64>(max_box, 24576);
-        const size_t lds = (tab_lds ? dtab.size() * 4 : 0) + (size_t)pay_cap + 16;
-        hipLaunchKernelGGL(k_omp_hdec, dim3((unsigned)g.nb), dim3(256), lds, st, g.bel, (const unsigned char *)(d_stream + off_pay), (const u64 *)ctx->reg_rank.p,
-                           (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, n_nodes_dec, tab_lds, pay_cap, single_symbol, d_codes, (unsigned *)(sm + SM_ERR));
+            const int tab_lds = D.dtab.size() * 4 <= 16384;            // node table and payload in LDS when they are small (the usual case: 2 - 3 bits per code)
+            const unsigned pay_cap = (unsigned)std::min<u64>(max_box, 24576);
+            const size_t lds = (tab_lds ? D.dtab.size() * 4 : 0) + (size_t)pay_cap + 16;
+            hipLaunchKernelGGL(k_omp_hdec, dim3((unsigned)g.nb), dim3(256), lds, st, g.bel, (const unsigned char *)(in.d_stream + off_pay), (const u64 *)ctx->reg_rank.p,
+                               (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds, pay_cap, D.single_symbol, d_codes, (unsigned *)(sm + SM_ERR));
         }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        return SZHIP_OK;
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-    T *d_out = (T *)out;
-    if (!out_on_device) { TRY(ensure(ctx, ctx->out, (size_t)n * sizeof(T))); d_out = (T *)ctx->out.p; }
-    if ((uintptr_t)d_out & 15u) g.vec = 0;
-    const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
-    HIPCHK(hipEventRecord(ctx->ev[2], st));
-    if (omp_col_applies(g, d_out, r2 * sizeof(T))) {
-        // the verbatim values go to their places in the output first (boxes that have any); the sweep picks them up where a code is zero
-        int fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32;        // flag words per box: a bit per group of rows one load of the sweep covers
-        unsigned *d_vflags = nullptr;
-        if (fw > OC_FLAG_WORDS) fw = 0;
-        if (E > 0) {
-            if (fw > 0) {
-                TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * fw * 4));
-                d_vflags = (unsigned *)ctx->chunk_bits.p;
-                HIPCHK(hipMemsetAsync(d_vflags, 0, (size_t)g.nb * fw * 4, st));
+    // ---- reconstruct: the inverse of the compress call's sweep
+    int reconstruct() {
+        TRY(device_out(ctx, out, out_on_device, (size_t)n, &d_out));
+        if ((uintptr_t)d_out & 15u) g.vec = 0;
+        const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
+        HIPCHK(hipEventRecord(ctx->ev[2], st));
+        if (omp_col_applies(g, d_out, r2 * sizeof(T))) {
+            // the verbatim values go to their places in the output first (boxes that have any); the sweep picks them up where a code is zero
+            int fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32;        // flag words per box: a bit per group of rows one load of the sweep covers
+            unsigned *d_vflags = nullptr;
+            if (fw > OC_FLAG_WORDS) fw = 0;
+            if (E > 0) {
+                if (fw > 0) {
+                    TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * fw * 4));
+                    d_vflags = (unsigned *)ctx->chunk_bits.p;
+                    HIPCHK(hipMemsetAsync(d_vflags, 0, (size_t)g.nb * fw * 4, st));
+                }
+                hipLaunchKernelGGL((k_omp_scatter<T>), dim3((unsigned)g.nb), dim3(256), 0, st, g, (const uint16_t *)d_codes, (const u64 *)ctx->col_off.p, (const T *)ctx->unpred.p, d_out,
+                                   (unsigned *)(sm + SM_ERR), d_vflags, fw);
+                HIPCHK(hipGetLastError());
             }
-            hipLaunchKernelGGL((k_omp_scatter<T>), dim3((unsigned)g.nb), dim3(256), 0, st, g, (const uint16_t *)d_codes, (const u64 *)ctx->col_off.p, (const T *)ctx->unpred.p, d_out,
-                               (unsigned *)(sm + SM_ERR), d_vflags, fw);
-            HIPCHK(hipGetLastError());
-        }
-        szh_oc::sweep_args<T> oa;
-        oa.vflags = d_vflags; oa.fw = fw;
-        oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
-        oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = (T *)ctx->samples.p; oa.uoff = (const u64 *)ctx->col_off.p;
-        hipLaunchKernelGGL((k_omp_col<T, 32, 32, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
-    } else if (g.vec) hipLaunchKernelGGL((k_omp_box<T, true, true>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, (const T *)nullptr, d_out, eb, (T)(1 / eb),
-                                  (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, (T *)ctx->samples.p, (const T *)ctx->unpred.p, (const u64 *)ctx->col_off.p);
-    else hipLaunchKernelGGL((k_omp_box<T, true, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, (const T *)nullptr, d_out, eb, (T)(1 / eb),
-                            (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, (T *)ctx->samples.p, (const T *)ctx->unpred.p, (const u64 *)ctx->col_off.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[3], st));
-    S.quant_kernel = omp_col_applies(g, d_out, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);
-    unsigned bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
-    if (!out_on_device) TRY(staged_copy(ctx, out, d_out, (size_t)n * sizeof(T), false));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes whose payload or verbatim-value count does not fit their codes", bad);
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_entropy = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    S.ms_total = now_ms() - t_begin; S.out_bytes = (uint64_t)n * sizeof(T);
-    if (stats) *stats = S;
-    return SZHIP_OK;
+            szh_oc::sweep_args<T> oa;
+            oa.vflags = d_vflags; oa.fw = fw;
+            oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
+            oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = (T *)ctx->samples.p; oa.uoff = (const u64 *)ctx->col_off.p;
+            hipLaunchKernelGGL((k_omp_col<T, 32, 32, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
+        } else hipLaunchKernelGGL((g.vec ? k_omp_box<T, true, true> : k_omp_box<T, true, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, (const T *)nullptr,
+                                  d_out, eb, (T)(1 / eb), (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, (T *)ctx->samples.p, (const T *)ctx->unpred.p, (const u64 *)ctx->col_off.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[3], st));
+        S.quant_kernel = omp_col_applies(g, d_out, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);
+        return SZHIP_OK;
+    }
+    // ---- the array to the caller, the kernels' error count, the statistics
+    int finish() {
+        unsigned bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
+        TRY(return_out(ctx, out, out_on_device, d_out, (size_t)n));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes whose payload or verbatim-value count does not fit their codes", bad);
+        decompress_times(ctx, S, host_ms, t_begin, (size_t)n * sizeof(T));
+        return SZHIP_OK;
+    }
+};
+
+template <class T>
+int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_on_device, size_t stream_len, size_t body_off, size_t r0, size_t r1, size_t r2,
+                        void *out, int out_on_device, szhip_stats *stats)
+{
+    omp_dec<T> d{call_base(ctx), stream_len, body_off, r0, r1, r2, out, out_on_device, {ctx, stream_in, stream_on_device, stream_len}};
+    TRY(d.read_header());
+    TRY(d.decode_boxes());
+    TRY(d.reconstruct());
+    TRY(d.finish());
+    return d.done(stats);
 }

@@ -7,12 +7,8 @@ int pwr_prepare_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_
                      unsigned char *signs_host, int *positive, double *real_precision, double *value_range, double *median, double *min_log_value)
 {
     hipStream_t st = ctx->stream;
-    const T *d_in = (const T *)data;
-    if (!data_on_device) {
-        TRY(ensure(ctx, ctx->in, n * sizeof(T)));
-        TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-        d_in = (const T *)ctx->in.p;
-    }
+    const T *d_in = nullptr;
+    TRY(stage_input(ctx, data, data_on_device, n, &d_in));
     TRY(ensure(ctx, ctx->pwr_log, n * sizeof(T)));
     TRY(ensure(ctx, ctx->pwr_signs, n));
     TRY(ensure(ctx, ctx->pwr_small, PWR_RED * 8));
@@ -65,12 +61,8 @@ int msst_prepare_impl(szhip_ctx *ctx, const void *data, int data_on_device, size
                       unsigned char *signs_host, int *positive, double *near_zero_out, double *median_log, double *min_log_value)
 {
     hipStream_t st = ctx->stream;
-    const T *d_in = (const T *)data;
-    if (!data_on_device) {
-        TRY(ensure(ctx, ctx->in, n * sizeof(T)));
-        TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-        d_in = (const T *)ctx->in.p;
-    }
+    const T *d_in = nullptr;
+    TRY(stage_input(ctx, data, data_on_device, n, &d_in));
     TRY(ensure(ctx, ctx->pwr_log, n * sizeof(T)));
     TRY(ensure(ctx, ctx->pwr_signs, n));
     TRY(ensure(ctx, ctx->pwr_small, PWR_RED * 8));
@@ -125,13 +117,13 @@ int decompress14_pwr_impl(szhip_ctx *ctx, const unsigned char *stream, int strea
         HIPCHK(hipMemcpyAsync(ctx->pwr_signs.p, signs_host, n, hipMemcpyHostToDevice, st));
         d_signs = (const unsigned char *)ctx->pwr_signs.p;
     }
-    T *d_out = (T *)out;
-    if (!out_on_device) { TRY(ensure(ctx, ctx->out, n * sizeof(T))); d_out = (T *)ctx->out.p; }
+    T *d_out = nullptr;
+    TRY(device_out(ctx, out, out_on_device, n, &d_out));
     const int grid = (int)std::min<int64_t>(((int64_t)n + 255) / 256, 4096);
     if (msst) hipLaunchKernelGGL((k_msst_post<T>), dim3(grid), dim3(256), 0, st, (const T *)d_log, (int64_t)n, (T)threshold, d_signs, d_out);
     else hipLaunchKernelGGL((k_pwr_exp<T>), dim3(grid), dim3(256), 0, st, (const T *)d_log, (int64_t)n, (T)threshold, d_signs, d_out);
     HIPCHK(hipGetLastError());
-    if (!out_on_device) TRY(staged_copy(ctx, out, d_out, n * sizeof(T), false));
+    TRY(return_out(ctx, out, out_on_device, d_out, n));
     HIPCHK(hipStreamSynchronize(st));
     return SZHIP_OK;
 }

@@ -105,16 +105,6 @@ static inline u64 msst_radius_index(double pe, double divider)
     if (v >= 9223372036854775808.0) { const double w = v - 9223372036854775808.0; return (w < 9223372036854775808.0 ? (u64)(int64_t)w : 0x8000000000000000ull) ^ 0x8000000000000000ull; }
     return (u64)(int64_t)v;
 }
-static unsigned msst_pick_intervals(const std::vector<u64> &hist, u64 total, float pred_threshold, unsigned floor_)
-{
-    const unsigned max_radius = (unsigned)hist.size();
-    const size_t target = (size_t)((float)total * pred_threshold);
-    size_t sum = 0; unsigned i = 0;
-    for (; i < max_radius; ++i) { sum += hist[i]; if (sum > target) break; }
-    if (i >= max_radius) i = max_radius - 1;
-    unsigned p2 = 2 * (i + 1); p2 -= 1; p2 |= p2 >> 1; p2 |= p2 >> 2; p2 |= p2 >> 4; p2 |= p2 >> 8; p2 |= p2 >> 16; p2 += 1;
-    return p2 < floor_ ? floor_ : p2;
-}
 // optimize_intervals_float_{1,2,3}D_opt_MSST19 (sz_float.c:4468, :4518, :4578; doubles sz_double.c:4163-).  The quotients come from the device
 // (k_msst_sample: IEEE adds and divisions, the same bits as the host's), the logarithm and the bin from the host (glibc's log2, as in the reference).
 // The reference's walk skips samples that are zero WITHOUT advancing its column counter; zeros are left only when the array's first element is zero
@@ -127,8 +117,7 @@ int msst_intervals(szhip_ctx *ctx, const szh_geom3 &G, int ndim, const T *d_in, 
     const int sd = prm->sample_distance;
     const double divider = (double)(T)(log2(1 + precision) * 2);
     std::vector<u64> hist(max_radius, 0);
-    u64 total = 0;
-    auto add = [&](double pe) { u64 ri = msst_radius_index(pe, divider); if (ri >= max_radius) ri = max_radius - 1; ++hist[ri]; ++total; };
+    auto add = [&](double pe) { u64 ri = msst_radius_index(pe, divider); if (ri >= max_radius) ri = max_radius - 1; ++hist[ri]; };
     const int64_t n = G.n, r2 = G.g2.count;
     if (zeros_left) {
         std::vector<T> h((size_t)n);
@@ -179,7 +168,7 @@ int msst_intervals(szhip_ctx *ctx, const szh_geom3 &G, int ndim, const T *d_in, 
             for (int64_t k = 0; k < slots; ++k) { if (f64_bits(pe[(size_t)k]) == 0x7ff8000000000001ull) continue; add(pe[(size_t)k]); }
         }
     }
-    *out = msst_pick_intervals(hist, total, prm->pred_threshold, sizeof(T) == 8 ? 64u : 32u);
+    *out = pick_intervals(hist.data(), max_radius, prm->pred_threshold, sizeof(T) == 8 ? 64u : 32u);
     return SZHIP_OK;
 }
 static int msst_upload(szhip_ctx *ctx, const MsstHostTab &ht, unsigned intervals, bool dec, msst_tab *tb)
@@ -227,106 +216,80 @@ int msst_sweep(szhip_ctx *ctx, const szh_geom3 &G, int ndim, bool dec, const T *
     return SZHIP_OK;
 }
 
-template <class T>
-int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, double range_in,
-                    double median_in, const szhip_params *prm, const unsigned char *meta, size_t meta_len, const szhip_pwr *pw, int out_on_device,
-                    unsigned char **out, size_t *out_size, szhip_stats *stats)
+// the zero codes (exact values) of a code array in scan order: counted per chunk of SZH_LIN_CHUNK codes, the chunks' ranks to ctx->col_off, the total to SM_TOTAL_UNPRED
+static int rank_zero_codes(szhip_ctx *ctx, const uint16_t *d_codes, int64_t n, int64_t nlin, u64 *sm)
 {
-    const int is_double = sizeof(T) == 8;
-    // pw != NULL: the data are log2|x| of a point-wise-relative call and the container carries the PW_REL fields
-    // r0 == 0: the 2-D compressor SZ_compress_float_2D_MDQ (sz_float.c:610): its predictors are those of the 3-D one's first layer,
-    // so it is carried as 1 x r1 x r2 (the block size of the carried geometry plays no role here); its optimiser has the 2-D lattice
-    // r0 == 0 and r1 == 0: the 1-D compressor SZ_compress_float_1D_MDQ (sz_float.c:353): a chain through the previous reconstructed
-    // value, walked by k_chain_1d; the container and everything after the code array are the same
-    const bool one_d = r0 == 0 && r1 == 0;
-    // pw->msst19: the table-driven form of PW_REL (szh_msst.h): `data` has its zeros replaced, eb_in is the RATIO; another optimiser, another
-    // quantiser, exact values taken against 0, two more header bytes -- the entropy stage and the container are the same
-    const bool msst = pw && pw->msst19;
-    const int ndim = one_d ? 1 : r0 == 0 ? 2 : 3;
+    TRY(ensure(ctx, ctx->col_zeros64, (size_t)nlin * 8));
+    TRY(ensure(ctx, ctx->col_off, (size_t)nlin * 8));
+    hipLaunchKernelGGL(k_lin_zero_count, dim3((unsigned)nlin), dim3(256), 0, ctx->stream, d_codes, n, (u64 *)ctx->col_zeros64.p);
+    return scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, nlin, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED);
+}
+
+// One SZ 1.4 compress call: its state, and one member function per phase (compress14_impl is their sequence).
+// pw != NULL: the data are log2|x| of a point-wise-relative call and the container carries the PW_REL fields
+// r0 == 0: the 2-D compressor SZ_compress_float_2D_MDQ (sz_float.c:610): its predictors are those of the 3-D one's first layer,
+// so it is carried as 1 x r1 x r2 (the block size of the carried geometry plays no role here); its optimiser has the 2-D lattice
+// r0 == 0 and r1 == 0: the 1-D compressor SZ_compress_float_1D_MDQ (sz_float.c:353): a chain through the previous reconstructed
+// value, walked by k_chain_1d; the container and everything after the code array are the same
+// pw->msst19: the table-driven form of PW_REL (szh_msst.h): `data` has its zeros replaced, eb_in is the RATIO; another optimiser, another
+// quantiser, exact values taken against 0, two more header bytes -- the entropy stage and the container are the same
+template <class T>
+struct sz14_call : call_base {
+    static constexpr int is_double = sizeof(T) == 8;
+    // ---- arguments, geometry
+    const size_t r0, r1, r2; const szhip_params *const prm; const unsigned char *const meta; const size_t meta_len; const szhip_pwr *const pw;
+    const int out_on_device; unsigned char **const out; size_t *const out_size;
+    const double eb_in; const T eb = (T)eb_in;                 // eb: `float realPrecision` parameter of sz_float.c:946 (:353 for 1-D)
+    const bool one_d = r0 == 0 && r1 == 0, msst = pw && pw->msst19; const int ndim = one_d ? 1 : r0 == 0 ? 2 : 3;
     const szh_geom3 G = one_d ? szh_make_geom2(1, (int)r2) : r0 == 0 ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2);
-    const int64_t n = G.n;
-    const T eb = (T)eb_in;                                     // `float realPrecision` parameter of sz_float.c:946 (:353 for 1-D)
-    const double t_begin = now_ms();
-    double host_ms = 0;
-    hipStream_t st = ctx->stream;
-    szhip_stats S; memset(&S, 0, sizeof(S));
-    S.n_elements = (uint64_t)n;
+    const int64_t n = G.n, nlin = (G.n + SZH_LIN_CHUNK - 1) / SZH_LIN_CHUNK;
+    // ---- device arrays
+    const T *d_in = nullptr; u64 *sm = nullptr; uint16_t *d_codes = nullptr;
+    // ---- decisions: interval count, the format of an exact value
+    unsigned intervals = 0; T median = 0; int req_len = 0, req_bytes = 0, resi_bits = 0, ign_bits = 0;
+    // ---- the code book, the exact values, the stream's layout
+    huff_ptr hf; std::vector<u64> tab_code; std::vector<uint8_t> tab_len; unsigned maxlen = 0;
+    size_t tree_bytes = 0, pay_bytes = 0; u64 total_bits = 0, E = 0, nmid = 0;
+    size_t lead_size = 0, resi_size = 0, blob = 0, hdr_len = 0, total_len = 0;
+    std::vector<unsigned char> hdr;
 
-    const T *d_in = (const T *)data;
-    if (!data_on_device) {
-        TRY(ensure(ctx, ctx->in, (size_t)n * sizeof(T)));
-        TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-        d_in = (const T *)ctx->in.p;
+    // ---- the array staged; interval optimiser (optimize_intervals_float_3D_opt, sz_float.c:4644): the SZ 2.1 sample lattice, radius histogram only; the format
+    // of an exact value
+    int choose_intervals(const void *data, int data_on_device, double range_in, double median_in) {
+        S.n_elements = (uint64_t)n;
+        TRY(stage_input(ctx, data, data_on_device, (size_t)n, &d_in));
+        TRY(clear_small(ctx, &sm));
+        HIPCHK(hipEventRecord(ctx->ev[0], st));
+        intervals = prm->quantization_intervals;
+        if (intervals == 0 && msst) {
+            bool zeros_left = false;                                // only when the array's first element is zero (szhip_msst_prepare)
+            { T first; HIPCHK(hipMemcpyAsync(&first, d_in, sizeof(T), hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); zeros_left = first == 0; }
+            TRY(msst_intervals<T>(ctx, G, ndim, d_in, prm, eb_in, zeros_left, &intervals));
+        } else if (intervals == 0)
+            TRY(sampled_intervals<T>(ctx, G, one_d, d_in, prm, eb, sm, &intervals, &host_ms));
+        if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
+        S.intervals = intervals;
+        median = (T)median_in;
+        if (msst) {
+            // computeReqLength_float_MSST19 = 9 - exponent of (float)ratio (sz_float.c:58-62), the double rule 12 - exponent (sz_double.c:57-61) --
+            // which the FLOAT 2-D quantiser also uses (sz_float.c:2041); exact values are the values themselves (no median)
+            const int e64 = (int)((f64_bits(eb_in) & 0x7FF0000000000000ull) >> 52) - 1023;
+            const float pf = (float)eb_in; unsigned u32; memcpy(&u32, &pf, 4);
+            const int e32 = (int)((u32 & 0x7F800000u) >> 23) - 127;
+            req_len = (is_double || ndim == 2) ? 12 - e64 : 9 - e32;
+            median = 0;
+            if (req_len < 9 || req_len > (int)sizeof(T) * 8) FAIL(SZHIP_ERR_UNSUP, "point-wise ratio %g needs %d leading bits per exact value", eb_in, req_len);
+        } else req_len = req_length<T>((double)eb, (T)range_in, &median);
+        req_bytes = req_len / 8; resi_bits = req_len % 8; ign_bits = (int)sizeof(T) * 8 - req_len;
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        return SZHIP_OK;
     }
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-
-    // ---- interval optimiser (optimize_intervals_float_3D_opt, sz_float.c:4644): the SZ 2.1 sample lattice, radius histogram only
-    unsigned intervals = prm->quantization_intervals;
-    if (intervals == 0 && msst) {
-        bool zeros_left = false;                                // only when the array's first element is zero (szhip_msst_prepare)
-        { T first; HIPCHK(hipMemcpyAsync(&first, d_in, sizeof(T), hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); zeros_left = first == 0; }
-        TRY(msst_intervals<T>(ctx, G, ndim, d_in, prm, eb_in, zeros_left, &intervals));
-    } else if (intervals == 0) {
-        const unsigned max_radius = prm->max_quant_intervals / 2;
-        TRY(ensure(ctx, ctx->hist, (size_t)(max_radius + 8192) * 4 + 64));
-        TRY(ensure_pinned(ctx, (size_t)(max_radius + 8192) * 4 + 64));
-        unsigned *d_rh = (unsigned *)ctx->hist.p, *d_fh = d_rh + max_radius;
-        HIPCHK(hipMemsetAsync(d_rh, 0, (size_t)(max_radius + 8192) * 4, st));
-        const int64_t nrows = one_d ? 0 : szh_sample_row_limit(G, prm->sample_distance);
-        if (one_d) {
-            const int64_t count = (n - 2 + prm->sample_distance - 1) / prm->sample_distance;
-            int grid = (int)std::min<int64_t>((count + 255) / 256 + 1, 1024);
-            hipLaunchKernelGGL((k_sample_1d<T>), dim3(grid), dim3(256), 0, st, d_in, n, prm->sample_distance, (double)eb, max_radius, d_rh);
-            HIPCHK(hipGetLastError());
-        } else if (G.ndim == 3 && (G.g0.count <= 1 || G.g1.count <= 1)) {      // a degenerate 3-D array: the reference's walk, literally
-            hipLaunchKernelGGL((k_sample_walk<T, false>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)0, max_radius, d_rh, d_fh, sm + SM_WITHIN);
-            HIPCHK(hipGetLastError());
-        } else if (nrows > 0) {
-            int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-            hipLaunchKernelGGL((k_sample<T, false>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb, (T)0,
-                               max_radius, d_rh, d_fh, sm + SM_WITHIN);
-            HIPCHK(hipGetLastError());
-        }
-        unsigned *h_hist = (unsigned *)ctx->pinned;
-        HIPCHK(hipMemcpyAsync(h_hist, d_rh, (size_t)max_radius * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        double h0 = now_ms();
-        u64 total = 0;
-        for (unsigned i = 0; i < max_radius; ++i) total += h_hist[i];
-        const size_t target = (size_t)((float)total * prm->pred_threshold);       // `size_t targetCount = totalSampleSize*predThreshold`
-        size_t sum = 0; unsigned i = 0;
-        for (; i < max_radius; ++i) { sum += h_hist[i]; if (sum > target) break; }
-        if (i >= max_radius) i = max_radius - 1;
-        unsigned p2 = 2 * (i + 1); p2 -= 1; p2 |= p2 >> 1; p2 |= p2 >> 2; p2 |= p2 >> 4; p2 |= p2 >> 8; p2 |= p2 >> 16; p2 += 1;
-        intervals = p2 < 32 ? 32 : p2;
-        host_ms += now_ms() - h0;
-    }
-    if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
-    S.intervals = intervals;
-    T median = (T)median_in;
-    int req_len_ = 0;
-    if (msst) {
-        // computeReqLength_float_MSST19 = 9 - exponent of (float)ratio (sz_float.c:58-62), the double rule 12 - exponent (sz_double.c:57-61) --
-        // which the FLOAT 2-D quantiser also uses (sz_float.c:2041); exact values are the values themselves (no median)
-        const int e64 = (int)((f64_bits(eb_in) & 0x7FF0000000000000ull) >> 52) - 1023;
-        const float pf = (float)eb_in; unsigned u32; memcpy(&u32, &pf, 4);
-        const int e32 = (int)((u32 & 0x7F800000u) >> 23) - 127;
-        req_len_ = (is_double || ndim == 2) ? 12 - e64 : 9 - e32;
-        median = 0;
-        if (req_len_ < 9 || req_len_ > (int)sizeof(T) * 8) FAIL(SZHIP_ERR_UNSUP, "point-wise ratio %g needs %d leading bits per exact value", eb_in, req_len_);
-    } else req_len_ = req_length<T>((double)eb, (T)range_in, &median);
-    const int req_len = req_len_;
-    const int req_bytes = req_len / 8, resi_bits = req_len % 8, ign_bits = (int)sizeof(T) * 8 - req_len;
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-
-    // ---- predict + quantise
-    TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
-    uint16_t *d_codes = (uint16_t *)ctx->codes_nat.p;
-    S.quant_kernel_launches = 1;
-    if (msst) {
+    // ---- predict + quantise: the table-driven quantiser (msst), the 1-D chain, or the wavefront kernel
+    int quantise() {
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
+        d_codes = (uint16_t *)ctx->codes_nat.p;
+        S.quant_kernel_launches = 1;
+        if (!msst) return one_d ? quantise_chain() : launch_pencil14<T>(ctx, G, sm, false, d_in, nullptr, d_codes, eb, intervals, median, ign_bits);
         MsstHostTab ht;
         double hb = now_ms();
         if (msst_build_tab(ht, eb_in, intervals, pw->plus_bits, true)) FAIL(SZHIP_ERR_UNSUP, "point-wise ratio %g with %u intervals: look-up table too large", eb_in, intervals);
@@ -340,9 +303,11 @@ int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t
             TRY(msst_sweep<T>(ctx, G, ndim, false, d_in, (T *)ctx->msst_rec.p, d_codes, ht, intervals, ign_bits));
             S.quant_kernel_launches = ndim == 1 ? 1 : (unsigned)((ndim == 3 ? G.g0.count : 1) + G.g1.count + G.g2.count - 2);
         }
-    } else if (one_d) {
-        // the chain cut at its certain restarts, one thread per segment; a segment whose successor turns out not to restart raises
-        // the flag, and the array is then walked by the one-wavefront kernel (same result, by construction; SZ_HIP_1D_SERIAL=1 forces it)
+        return SZHIP_OK;
+    }
+    // the chain cut at its certain restarts, one thread per segment; a segment whose successor turns out not to restart raises
+    // the flag, and the array is then walked by the one-wavefront kernel (same result, by construction; SZ_HIP_1D_SERIAL=1 forces it)
+    int quantise_chain() {
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         unsigned violation = 1;
         if (!tune_int("SZ_HIP_1D_SERIAL", 0)) {
@@ -359,71 +324,60 @@ int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t
             S.quant_kernel_launches = 2;
         }
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-    } else
-        TRY(launch_pencil14<T>(ctx, G, sm, false, d_in, nullptr, d_codes, eb, intervals, median, ign_bits));
-
+        return SZHIP_OK;
+    }
     // ---- histogram -> code book (host), exact-value counts
-    TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
-    unsigned *d_hist = (unsigned *)ctx->hist.p;
-    TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
-    unsigned *h_hist = (unsigned *)ctx->pinned;
-    HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
-    {
-        int rshift = 0; int use_lds = intervals <= 16384;
-        if (use_lds) { while ((intervals << (rshift + 1)) <= 16384u && rshift < 6) ++rshift; }
-        const size_t lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
-        int grid = (int)std::min<int64_t>((n / 8 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), lds, st, (const uint16_t *)d_codes, n, intervals, rshift, use_lds, d_hist, (int64_t)0);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
-    const int64_t nlin = (n + SZH_LIN_CHUNK - 1) / SZH_LIN_CHUNK;
-    TRY(ensure(ctx, ctx->col_zeros64, (size_t)nlin * 8));
-    TRY(ensure(ctx, ctx->col_off, (size_t)nlin * 8));
-    hipLaunchKernelGGL(k_lin_zero_count, dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (u64 *)ctx->col_zeros64.p);
-    TRY(scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, nlin, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED));
-    u64 h_small[SM_COUNT];
-    HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
-    const u64 E = h_small[SM_TOTAL_UNPRED];
-    S.n_unpred = E;
-    double h0 = now_ms();
-    szhost_huff *hf = szhost_huff_build(2 * (int)intervals, h_hist, nullptr, intervals);
-    if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
-    const size_t tree_bytes = szhost_huff_tree_size(hf);
-    const u64 total_bits = hf->total_bits;
-    const size_t pay_bytes = (size_t)((total_bits + 7) / 8);
-    std::vector<u64> tab_code(intervals); std::vector<uint8_t> tab_len(intervals);
-    for (unsigned s2 = 0; s2 < intervals; ++s2) { tab_code[s2] = hf->code[s2]; tab_len[s2] = hf->len[s2]; }
-    host_ms += now_ms() - h0;
-
-    // ---- exact values: compact in scan order, lead numbers, mid-byte offsets
-    u64 nmid = 0;
-    if (E > 0) {
-        TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T)));
-        TRY(ensure(ctx, ctx->lor_bits, (size_t)E + 8));              // lead numbers, one byte each
-        TRY(ensure(ctx, ctx->reg_flags, (size_t)E * 8));             // mid-byte counts
-        TRY(ensure(ctx, ctx->reg_rank, (size_t)E * 8));              // mid-byte offsets
-        hipLaunchKernelGGL((k_lin_zero_move<T, 0>), dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const u64 *)ctx->col_off.p,
-                           d_in, (T *)ctx->unpred.p, (T *)nullptr);
-        hipLaunchKernelGGL((k_exact_lead<T>), dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, (const T *)ctx->unpred.p, (int64_t)E, median,
-                           req_bytes, (uint8_t *)ctx->lor_bits.p, (u64 *)ctx->reg_flags.p);
-        HIPCHK(hipGetLastError());
-        TRY(scan_u64(ctx, (const u64 *)ctx->reg_flags.p, (int64_t)E, (u64 *)ctx->reg_rank.p, sm + SM_SCRATCH));
-        HIPCHK(hipMemcpyAsync(&nmid, sm + SM_SCRATCH, 8, hipMemcpyDeviceToHost, st));
+    int hist_and_book() {
+        TRY(ensure(ctx, ctx->hist, (size_t)(65536 + 8192) * 4 + 64));
+        unsigned *d_hist = (unsigned *)ctx->hist.p;
+        TRY(ensure_pinned(ctx, (size_t)intervals * 4 + 64));
+        unsigned *h_hist = (unsigned *)ctx->pinned;
+        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, st));
+        TRY(launch_hist_u16(ctx, st, d_codes, 0, n, intervals, d_hist));
+        HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, st));
+        TRY(rank_zero_codes(ctx, d_codes, n, nlin, sm));
+        u64 h_small[SM_COUNT];
+        HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if ((unsigned)h_small[SM_ERR] != 0) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
+        E = h_small[SM_TOTAL_UNPRED];
+        S.n_unpred = E;
+        double h0 = now_ms();
+        hf = host_book(h_hist, intervals, tab_code, tab_len, &maxlen);
+        if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
+        tree_bytes = szhost_huff_tree_size(hf.get());
+        total_bits = hf->total_bits;
+        pay_bytes = (size_t)((total_bits + 7) / 8);
+        host_ms += now_ms() - h0;
+        return SZHIP_OK;
     }
-    const size_t lead_size = (size_t)((E * 2 + 7) / 8), resi_size = resi_bits ? (size_t)((E * (u64)resi_bits + 7) / 8) : 0;
-
-    // ---- container
-    h0 = now_ms();
-    const size_t type_size = 8 + tree_bytes + pay_bytes;
-    const size_t blob = pw ? (size_t)pw->signs_blob_size : 0;
-    const size_t hdr_len = meta_len + 8 + 4 + (pw ? 1 + 8 + 4 : 0) + 4 + sizeof(T) + 1 + (msst ? 2 : 0) + 8 + 8 + 8 + 8 + (pw ? sizeof(T) : 0) + 8 + tree_bytes; // ... up to the Huffman payload
-    const size_t total_len = hdr_len + pay_bytes + blob + lead_size + (size_t)nmid + resi_size;
-    std::vector<unsigned char> hdr(hdr_len, 0);
-    {
+    // ---- exact values: compact in scan order, lead numbers, mid-byte offsets
+    int compact_exact() {
+        if (E > 0) {
+            TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T)));
+            TRY(ensure(ctx, ctx->lor_bits, (size_t)E + 8));              // lead numbers, one byte each
+            TRY(ensure(ctx, ctx->reg_flags, (size_t)E * 8));             // mid-byte counts
+            TRY(ensure(ctx, ctx->reg_rank, (size_t)E * 8));              // mid-byte offsets
+            hipLaunchKernelGGL((k_lin_zero_move<T, 0>), dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const u64 *)ctx->col_off.p,
+                               d_in, (T *)ctx->unpred.p, (T *)nullptr);
+            hipLaunchKernelGGL((k_exact_lead<T>), dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, (const T *)ctx->unpred.p, (int64_t)E, median,
+                               req_bytes, (uint8_t *)ctx->lor_bits.p, (u64 *)ctx->reg_flags.p);
+            HIPCHK(hipGetLastError());
+            TRY(scan_u64(ctx, (const u64 *)ctx->reg_flags.p, (int64_t)E, (u64 *)ctx->reg_rank.p, sm + SM_SCRATCH));
+            HIPCHK(hipMemcpyAsync(&nmid, sm + SM_SCRATCH, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        lead_size = (size_t)((E * 2 + 7) / 8); resi_size = resi_bits ? (size_t)((E * (u64)resi_bits + 7) / 8) : 0;
+        return SZHIP_OK;
+    }
+    // ---- container: everything in front of the Huffman payload, on the host
+    void write_header() {
+        const double h0 = now_ms();
+        const size_t type_size = 8 + tree_bytes + pay_bytes;
+        blob = pw ? (size_t)pw->signs_blob_size : 0;
+        hdr_len = meta_len + 8 + 4 + (pw ? 1 + 8 + 4 : 0) + 4 + sizeof(T) + 1 + (msst ? 2 : 0) + 8 + 8 + 8 + 8 + (pw ? sizeof(T) : 0) + 8 + tree_bytes; // ... up to the Huffman payload
+        total_len = hdr_len + pay_bytes + blob + lead_size + (size_t)nmid + resi_size;
+        hdr.assign(hdr_len, 0);
         unsigned char *q = hdr.data();
         memcpy(q, meta, meta_len); q += meta_len;
         szhost_put_u64be(q, (uint64_t)n); q += 8;
@@ -438,11 +392,7 @@ int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t
         if (is_double) szhost_put_f64be(q, (double)median_field); else szhost_put_f32be(q, (float)median_field);
         q += sizeof(T);
         *q++ = (unsigned char)req_len;
-        if (msst) {                                              // plus_bits, max_bits (TightDataPointStorageF.c:431-435; Huffman.c:828-833)
-            int max_bits = 0;
-            for (unsigned s2 = 0; s2 < intervals; ++s2) if (tab_len[s2] > max_bits) max_bits = tab_len[s2];
-            *q++ = pw->plus_bits; *q++ = (unsigned char)max_bits;
-        }
+        if (msst) { *q++ = pw->plus_bits; *q++ = (unsigned char)maxlen; }       // plus_bits, max_bits (TightDataPointStorageF.c:431-435; Huffman.c:828-833)
         szhost_put_f64be(q, msst ? eb_in : (double)eb); q += 8;
         szhost_put_u64be(q, (uint64_t)type_size); q += 8;
         szhost_put_u64be(q, (uint64_t)E); q += 8;
@@ -453,233 +403,212 @@ int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t
         }
         szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;      // encode_withTree blob (Huffman.c:790-816)
         szhost_put_u32be(q, intervals); q += 4;
-        szhost_huff_tree_write(hf, q); q += tree_bytes;
+        szhost_huff_tree_write(hf.get(), q);
+        hf.reset();
+        host_ms += now_ms() - h0;
     }
-    szhost_huff_free(hf);
-    host_ms += now_ms() - h0;
-
-    TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
-    TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
-    HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
-    TRY(ensure(ctx, ctx->stream_buf, total_len + 64));
-    unsigned char *d_stream = (unsigned char *)ctx->stream_buf.p;
-    HIPCHK(hipMemsetAsync(d_stream, 0, total_len + 64, st));
-    HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
-    if (blob) HIPCHK(hipMemcpyAsync(d_stream + hdr_len + pay_bytes, pw->signs_blob, blob, hipMemcpyHostToDevice, st));   // after the type array (:463-467)
-    if (total_bits > 0) {
-        const int64_t nchunks = (n + SZH_ENC_CHUNK - 1) / SZH_ENC_CHUNK;
-        TRY(ensure(ctx, ctx->chunk_bits, (size_t)nchunks * 8));
-        TRY(ensure(ctx, ctx->chunk_off, (size_t)nchunks * 8));
-        hipLaunchKernelGGL(k_chunk_bits, dim3((unsigned)((nchunks + SZH_CB_PER - 1) / SZH_CB_PER)), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const uint8_t *)ctx->len_tab.p,
-                           intervals, (u64 *)ctx->chunk_bits.p);
-        TRY(scan_u64(ctx, (const u64 *)ctx->chunk_bits.p, nchunks, (u64 *)ctx->chunk_off.p, sm + SM_TOTAL_BITS));
-        hipLaunchKernelGGL(k_encode, dim3((unsigned)((nchunks + SZH_ENC_PER - 1) / SZH_ENC_PER)), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const u64 *)ctx->code_tab.p,
-                           (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)ctx->chunk_off.p, (u64)hdr_len * 8, (unsigned *)d_stream);
-        HIPCHK(hipGetLastError());
+    // ---- packing: header, Huffman payload, the sign bytes of a PW_REL call, the exact values' three tables into the stream buffer
+    int pack() {
+        TRY(upload_code_tables(ctx, tab_code, tab_len));
+        TRY(ensure(ctx, ctx->stream_buf, total_len + 64));
+        unsigned char *d_stream = (unsigned char *)ctx->stream_buf.p;
+        HIPCHK(hipMemsetAsync(d_stream, 0, total_len + 64, st));
+        HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
+        if (blob) HIPCHK(hipMemcpyAsync(d_stream + hdr_len + pay_bytes, pw->signs_blob, blob, hipMemcpyHostToDevice, st));   // after the type array (:463-467)
+        if (total_bits > 0) {
+            TRY(chunk_bit_offsets(ctx, d_codes, n, intervals, sm, 0));
+            TRY(launch_encode(ctx, d_codes, n, intervals, (u64)hdr_len * 8, d_stream));
+        }
+        if (E > 0) {
+            unsigned char *lead_out = d_stream + hdr_len + pay_bytes + blob, *mid_out = lead_out + lead_size, *resi_out = mid_out + nmid;
+            hipLaunchKernelGGL((k_exact_write<T>), dim3((unsigned)(((E + 7) / 8 + 255) / 256)), dim3(256), 0, st, (const T *)ctx->unpred.p, (int64_t)E,
+                               median, req_bytes, resi_bits, (const uint8_t *)ctx->lor_bits.p, (const u64 *)ctx->reg_rank.p, lead_out, mid_out, resi_out,
+                               (int64_t)resi_size);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        return SZHIP_OK;
     }
-    if (E > 0) {
-        unsigned char *lead_out = d_stream + hdr_len + pay_bytes + blob, *mid_out = lead_out + lead_size, *resi_out = mid_out + nmid;
-        hipLaunchKernelGGL((k_exact_write<T>), dim3((unsigned)(((E + 7) / 8 + 255) / 256)), dim3(256), 0, st, (const T *)ctx->unpred.p, (int64_t)E,
-                           median, req_bytes, resi_bits, (const uint8_t *)ctx->lor_bits.p, (const u64 *)ctx->reg_rank.p, lead_out, mid_out, resi_out,
-                           (int64_t)resi_size);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(ctx->ev[4], st));
-    if (out_on_device == 2) {
-        if (!*out || *out_size < total_len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, total_len);
-        HIPCHK(hipMemcpyAsync(*out, d_stream, total_len, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else if (out_on_device) {
-        HIPCHK(hipStreamSynchronize(st));
-        *out = d_stream;
-    } else {
-        unsigned char *h = (unsigned char *)malloc(total_len ? total_len : 1);
-        if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
-        TRY(staged_copy(ctx, h, d_stream, total_len, false));
-        *out = h;
-    }
-    *out_size = total_len;
-    {
+    // ---- delivery, the packed bit count against the book's, the statistics
+    int deliver_and_check() {
+        TRY(deliver_stream(ctx, (unsigned char *)ctx->stream_buf.p, total_len, out_on_device, out, out_size, false, false));
         u64 tb = 0;
         if (total_bits > 0) { HIPCHK(hipMemcpy(&tb, sm + SM_TOTAL_BITS, 8, hipMemcpyDeviceToHost)); }
         if (tb != total_bits) FAIL_PUBLISHED(SZHIP_ERR_INTERNAL, "encoded bit count mismatch (%llu vs %llu)", (unsigned long long)tb, (unsigned long long)total_bits);
+        compress_times(ctx, S, host_ms, t_begin, total_len);
+        return SZHIP_OK;
     }
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
-    S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = total_len;
-    if (stats) *stats = S;
-    return SZHIP_OK;
+};
+
+template <class T>
+int compress14_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, double range_in,
+                    double median_in, const szhip_params *prm, const unsigned char *meta, size_t meta_len, const szhip_pwr *pw, int out_on_device,
+                    unsigned char **out, size_t *out_size, szhip_stats *stats)
+{
+    sz14_call<T> c{call_base(ctx), r0, r1, r2, prm, meta, meta_len, pw, out_on_device, out, out_size, eb_in};
+    TRY(c.choose_intervals(data, data_on_device, range_in, median_in));
+    TRY(c.quantise());
+    TRY(c.hist_and_book());
+    TRY(c.compact_exact());
+    c.write_header();
+    TRY(c.pack());
+    TRY(c.deliver_and_check());
+    return c.done(stats);
 }
 
-// `body_off`: offset of the max_quant_intervals field (4 + 28|36 + 8)
+// One SZ 1.4 decompress call.  `body_off`: offset of the max_quant_intervals field (4 + 28|36 + 8);
+// pwr: 0 plain, 1 PW_REL log-domain form, 2 PW_REL table-driven form (szh_msst.h)
+template <class T>
+struct sz14_dec : call_base {
+    static constexpr int is_double = sizeof(T) == 8;
+    // ---- arguments, geometry
+    const size_t stream_len, body_off, r0, r1, r2; const int pwr; void *const out; const int out_on_device; stream_intake in;
+    const bool one_d = r0 == 0 && r1 == 0, msst = pwr == 2; const int ndim = one_d ? 1 : r0 == 0 ? 2 : 3;            // one_d: decompressDataSeries_float_1D (szd_float.c:185)
+    const szh_geom3 G = one_d ? szh_make_geom2(1, (int)r2) : r0 == 0 ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2);
+    const int64_t n = G.n, nlin = (G.n + SZH_LIN_CHUNK - 1) / SZH_LIN_CHUNK;
+    // ---- the header
+    unsigned intervals = 0; T median = 0, eb = 0; double eb_field = 0; int req_bytes = 0, resi_bits = 0, plus_bits = 0;
+    uint64_t type_size = 0, E = 0, nmid = 0; size_t blob = 0, type_off = 0, lead_size = 0, resi_size = 0, pay_off = 0; u64 total_bits = 0;
+    dec_table D;
+    // ---- device arrays
+    u64 *sm = nullptr; uint16_t *d_codes = nullptr; T *d_out = nullptr;
+
+    // ---- the stream taken in; header + tree on the host (TightDataPointStorageF.c:54-265); a device-resident stream hands over a prefix
+    int read_header() {
+        S.n_elements = (uint64_t)n;
+        TRY(in.open());
+        double h0 = now_ms();
+        const size_t fixed = 4 + (pwr ? 1 + 8 + 4 : 0) + 4 + sizeof(T) + 1 + (msst ? 2 : 0) + 8 + 8 + 8 + 8 + (pwr ? sizeof(T) : 0) + 8;
+        if (body_off + fixed > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
+        TRY(in.fetch(body_off + fixed));
+        const unsigned char *q = in.hs + body_off;
+        q += 4;                                                        // max_quant_intervals
+        if (pwr) { q += 1 + 8; blob = szhost_get_u32be(q); q += 4; }   // radExpo, segment_size, size of the sign bytes (TightDataPointStorageF.c:137-148)
+        intervals = szhost_get_u32be(q); q += 4;
+        median = is_double ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
+        const int req_len = *q++;
+        if (msst) { plus_bits = q[0]; q += 2; median = 0; }           // plus_bits, max_bits (TightDataPointStorageF.c:164-168); exact values carry no median
+        eb_field = szhost_get_f64be(q);
+        eb = (T)eb_field; q += 8;                                      // `float realPrecision = tdps->realPrecision`, szd_float.c:610
+        type_size = szhost_get_u64be(q); q += 8;
+        E = szhost_get_u64be(q); q += 8;
+        nmid = szhost_get_u64be(q); q += 8;
+        if (pwr) q += sizeof(T);                                       // minLogValue (the caller read it: szhip_sz14_pwr_locate)
+        type_off = body_off + fixed - 8;                               // the blob starts with nodeCount | intervals
+        if (intervals < 4 || intervals > 65536) FAIL(SZHIP_ERR_STREAM, "bad interval count %u", intervals);
+        if (req_len < 9 || req_len > (int)sizeof(T) * 8) FAIL(SZHIP_ERR_STREAM, "bad exact-value length %d", req_len);
+        if (!(eb > 0)) FAIL(SZHIP_ERR_STREAM, "bad error bound");
+        req_bytes = req_len / 8; resi_bits = req_len % 8;
+        lead_size = (size_t)((E * 2 + 7) / 8); resi_size = resi_bits ? (size_t)((E * (uint64_t)resi_bits + 7) / 8) : 0;
+        if (E >= ((uint64_t)1 << 32)) FAIL(SZHIP_ERR_UNSUP, "more than 2^32 exact values");   // the prefix counts of k_exact_* are packed in 32-bit halves
+        if (E > (uint64_t)n || type_size < 8 || type_size > stream_len || nmid > stream_len ||
+            blob > stream_len || type_off + type_size + blob + lead_size + nmid + resi_size > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
+        const int node_count = (int)szhost_get_u32be(q);
+        if (node_count <= 0 || 8 + szhost_huff_serial_size(node_count) > type_size) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree size");
+        const size_t tree_bytes = szhost_huff_serial_size(node_count);
+        TRY(in.fetch(type_off + 8 + tree_bytes));
+        if (!read_tree(in.hs + type_off + 8, node_count, intervals, D)) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
+        pay_off = type_off + 8 + tree_bytes;
+        total_bits = (u64)(type_size - 8 - tree_bytes) * 8;
+        S.intervals = intervals; S.n_unpred = E;
+        host_ms += now_ms() - h0;
+        return SZHIP_OK;
+    }
+    // ---- Huffman decode of the code array; its zero codes counted and ranked, and checked against the header
+    int decode_codes() {
+        TRY(clear_small(ctx, &sm));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
+        d_codes = (uint16_t *)ctx->codes_nat.p;
+        TRY(huff_decode_device(ctx, sm, in.d_stream + pay_off, (unsigned)std::min<size_t>(pay_off, 4096), total_bits, D.dtab, D.n_nodes, D.single_symbol, n, d_codes));
+        TRY(rank_zero_codes(ctx, d_codes, n, nlin, sm));
+        u64 zeros_found = 0;
+        HIPCHK(hipMemcpyAsync(&zeros_found, sm + SM_TOTAL_UNPRED, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return check_decoded(ctx, n, E, zeros_found, "exact");
+    }
+    // ---- exact values back into the output array
+    int place_exact() {
+        TRY(device_out(ctx, out, out_on_device, (size_t)n, &d_out));
+        if (E > 0) {
+            const unsigned char *lead_in = in.d_stream + type_off + type_size + blob, *mid_in = lead_in + lead_size, *resi_in = mid_in + nmid;
+            const unsigned gE = (unsigned)((E + 255) / 256);
+            TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T)));
+            TRY(ensure(ctx, ctx->reg_flags, (size_t)E * 8 * 3));         // flag words: f01 | f2 | mid counts
+            TRY(ensure(ctx, ctx->reg_rank, (size_t)E * 8 * 3));          // their exclusive prefix sums
+            TRY(ensure(ctx, ctx->lor_bits, (size_t)E * 3 + 8));          // compacted own bytes of positions 0..2
+            u64 *f01 = (u64 *)ctx->reg_flags.p, *f2 = f01 + E, *mc = f2 + E;
+            u64 *s01 = (u64 *)ctx->reg_rank.p, *s2 = s01 + E, *mo = s2 + E;
+            uint8_t *own0 = (uint8_t *)ctx->lor_bits.p, *own1 = own0 + E, *own2 = own1 + E;
+            hipLaunchKernelGGL(k_exact_flags, dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, f01, f2, mc);
+            TRY(scan_u64(ctx, f01, (int64_t)E, s01, sm + SM_SCRATCH));
+            TRY(scan_u64(ctx, f2, (int64_t)E, s2, sm + SM_SCRATCH));
+            TRY(scan_u64(ctx, mc, (int64_t)E, mo, sm + SM_SCRATCH));
+            u64 mid_need = 0;
+            HIPCHK(hipMemcpyAsync(&mid_need, sm + SM_SCRATCH, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (mid_need != nmid) FAIL(SZHIP_ERR_STREAM, "stream holds %llu mid bytes, lead numbers need %llu", (unsigned long long)nmid, (unsigned long long)mid_need);
+            hipLaunchKernelGGL(k_exact_own, dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, mid_in, resi_in,
+                               (const u64 *)s01, (const u64 *)s2, (const u64 *)mo, own0, own1, own2);
+            hipLaunchKernelGGL((k_exact_build<T>), dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, mid_in, resi_in,
+                               (const u64 *)s01, (const u64 *)s2, (const u64 *)mo, (const uint8_t *)own0, (const uint8_t *)own1, (const uint8_t *)own2,
+                               median, (T *)ctx->unpred.p);
+            hipLaunchKernelGGL((k_lin_zero_move<T, 1>), dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const u64 *)ctx->col_off.p,
+                               (const T *)nullptr, (T *)ctx->unpred.p, d_out);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        return SZHIP_OK;
+    }
+    // ---- reconstruct: the inverse of the compress call's quantiser
+    int reconstruct() {
+        if (msst) {
+            if (!(eb_field > 0 && eb_field < 1) || plus_bits > 16) FAIL(SZHIP_ERR_STREAM, "bad point-wise ratio / table parameters");
+            MsstHostTab ht;
+            msst_build_tab(ht, eb_field, intervals, plus_bits, false);
+            if (ndim >= 2 && !tune_int("SZ_HIP_MSST_SWEEP", 0)) {
+                msst_tab tb;
+                TRY(msst_upload(ctx, ht, intervals, true, &tb));
+                TRY(launch_pencil14<T>(ctx, G, sm, true, nullptr, d_out, d_codes, eb, intervals, (T)0, 0, &tb, ndim));
+            } else
+                TRY(msst_sweep<T>(ctx, G, ndim, true, nullptr, d_out, d_codes, ht, intervals, 0));
+        } else if (one_d) {
+            HIPCHK(hipEventRecord(ctx->ev[2], st));
+            if (tune_int("SZ_HIP_1D_SERIAL", 0))
+                hipLaunchKernelGGL((k_chain_1d<T, true>), dim3(1), dim3(64), 0, st, (const T *)nullptr, d_out, d_codes, n, eb, (T)(1 / eb), (int)intervals, median, 0);
+            else {   // decoding sees where the chain restarts (code 0): one thread per segment, nothing to verify
+                const int grid = (int)std::min<int64_t>((n + 255) / 256, 1 << 20);
+                hipLaunchKernelGGL((k_chain_seg_1d<T, true>), dim3(grid), dim3(256), 0, st, (const T *)nullptr, d_out, d_codes, n, eb, (T)(1 / eb), (int)intervals,
+                                   median, 0, 1.0, (unsigned *)nullptr);
+            }
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ev[3], st));
+        } else
+            TRY(launch_pencil14<T>(ctx, G, sm, true, nullptr, d_out, d_codes, eb, intervals, median, 0));
+        S.quant_kernel_launches = 1;
+        return SZHIP_OK;
+    }
+    // ---- the array to the caller, the wavefront kernel's error flag, the statistics
+    int finish() {
+        unsigned kerr = 0;
+        HIPCHK(hipMemcpyAsync(&kerr, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
+        TRY(return_out(ctx, out, out_on_device, d_out, (size_t)n));
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (kerr) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
+        decompress_times(ctx, S, host_ms, t_begin, (size_t)n * sizeof(T));
+        return SZHIP_OK;
+    }
+};
+
 template <class T>
 int decompress14_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_on_device, size_t stream_len, size_t body_off, int pwr,
                       size_t r0, size_t r1, size_t r2, void *out, int out_on_device, szhip_stats *stats)
 {
-    const int is_double = sizeof(T) == 8;
-    const bool one_d = r0 == 0 && r1 == 0;                     // decompressDataSeries_float_1D (szd_float.c:185)
-    const bool msst = pwr == 2;                                // pwr: 0 plain, 1 PW_REL log-domain form, 2 PW_REL table-driven form (szh_msst.h)
-    const int ndim = one_d ? 1 : r0 == 0 ? 2 : 3;
-    const szh_geom3 G = one_d ? szh_make_geom2(1, (int)r2) : r0 == 0 ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2);
-    const int64_t n = G.n;
-    const double t_begin = now_ms();
-    double host_ms = 0;
-    hipStream_t st = ctx->stream;
-    szhip_stats S; memset(&S, 0, sizeof(S));
-    S.n_elements = (uint64_t)n;
-
-    TRY(ensure(ctx, ctx->stream_buf, stream_len + 64));
-    unsigned char *d_stream = (unsigned char *)ctx->stream_buf.p;
-    if (stream_on_device) { if (stream_in != d_stream) HIPCHK(hipMemcpyAsync(d_stream, stream_in, stream_len, hipMemcpyDeviceToDevice, st)); }
-    else TRY(staged_copy(ctx, d_stream, stream_in, stream_len, true));
-    HIPCHK(hipMemsetAsync(d_stream + stream_len, 0, 64, st));
-    HIPCHK(hipEventRecord(ctx->ev[0], st));
-
-    // ---- header + tree on the host (TightDataPointStorageF.c:54-265); a device-resident stream hands over a prefix
-    double h0 = now_ms();
-    const size_t fixed = 4 + (pwr ? 1 + 8 + 4 : 0) + 4 + sizeof(T) + 1 + (msst ? 2 : 0) + 8 + 8 + 8 + 8 + (pwr ? sizeof(T) : 0) + 8;
-    if (body_off + fixed > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-    std::vector<unsigned char> hbuf;
-    const unsigned char *hs = stream_in;
-    auto fetch = [&](size_t want) -> int {
-        if (!stream_on_device) return SZHIP_OK;
-        hbuf.resize(want);
-        HIPCHK(hipMemcpyAsync(hbuf.data(), d_stream, want, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        hs = hbuf.data();
-        return SZHIP_OK;
-    };
-    TRY(fetch(body_off + fixed));
-    const unsigned char *q = hs + body_off;
-    q += 4;                                                        // max_quant_intervals
-    size_t blob = 0;
-    if (pwr) { q += 1 + 8; blob = szhost_get_u32be(q); q += 4; }   // radExpo, segment_size, size of the sign bytes (TightDataPointStorageF.c:137-148)
-    const unsigned intervals = szhost_get_u32be(q); q += 4;
-    T median = is_double ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
-    const int req_len = *q++;
-    int plus_bits = 0;
-    if (msst) { plus_bits = q[0]; q += 2; median = 0; }           // plus_bits, max_bits (TightDataPointStorageF.c:164-168); exact values carry no median
-    const double eb_field = szhost_get_f64be(q);
-    const T eb = (T)eb_field; q += 8;                              // `float realPrecision = tdps->realPrecision`, szd_float.c:610
-    const uint64_t type_size = szhost_get_u64be(q); q += 8;
-    const uint64_t E = szhost_get_u64be(q); q += 8;
-    const uint64_t nmid = szhost_get_u64be(q); q += 8;
-    if (pwr) q += sizeof(T);                                       // minLogValue (the caller read it: szhip_sz14_pwr_locate)
-    const size_t type_off = body_off + fixed - 8;                  // the blob starts with nodeCount | intervals
-    if (intervals < 4 || intervals > 65536) FAIL(SZHIP_ERR_STREAM, "bad interval count %u", intervals);
-    if (req_len < 9 || req_len > (int)sizeof(T) * 8) FAIL(SZHIP_ERR_STREAM, "bad exact-value length %d", req_len);
-    if (!(eb > 0)) FAIL(SZHIP_ERR_STREAM, "bad error bound");
-    const int req_bytes = req_len / 8, resi_bits = req_len % 8;
-    const size_t lead_size = (size_t)((E * 2 + 7) / 8), resi_size = resi_bits ? (size_t)((E * (uint64_t)resi_bits + 7) / 8) : 0;
-    if (E >= ((uint64_t)1 << 32)) FAIL(SZHIP_ERR_UNSUP, "more than 2^32 exact values");   // the prefix counts of k_exact_* are packed in 32-bit halves
-    if (E > (uint64_t)n || type_size < 8 || type_size > stream_len || nmid > stream_len ||
-        blob > stream_len || type_off + type_size + blob + lead_size + nmid + resi_size > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-    const int node_count = (int)szhost_get_u32be(q);
-    if (node_count <= 0 || 8 + szhost_huff_serial_size(node_count) > type_size) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree size");
-    const size_t tree_bytes = szhost_huff_serial_size(node_count);
-    TRY(fetch(type_off + 8 + tree_bytes));
-    szhost_huff *hf = szhost_huff_from_bytes(2 * (int)intervals, hs + type_off + 8, node_count);
-    if (!hf) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
-    std::vector<uint32_t> dtab((size_t)hf->n_nodes * 2);
-    szhost_huff_decode_table(hf, dtab.data());
-    const int single_symbol = hf->t[0] ? (int)hf->C[0] : -1;
-    const int n_nodes = hf->n_nodes;
-    szhost_huff_free(hf);
-    const size_t pay_off = type_off + 8 + tree_bytes;
-    const u64 total_bits = (u64)(type_size - 8 - tree_bytes) * 8;
-    S.intervals = intervals; S.n_unpred = E;
-    host_ms += now_ms() - h0;
-
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
-    TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
-    uint16_t *d_codes = (uint16_t *)ctx->codes_nat.p;
-    u64 total_sym = 0;
-    TRY(huff_decode_device(ctx, sm, d_stream + pay_off, (unsigned)std::min<size_t>(pay_off, 4096), total_bits, dtab, n_nodes, single_symbol, n, d_codes, &total_sym));
-
-    // ---- exact values back into the output array
-    const int64_t nlin = (n + SZH_LIN_CHUNK - 1) / SZH_LIN_CHUNK;
-    TRY(ensure(ctx, ctx->col_zeros64, (size_t)nlin * 8));
-    TRY(ensure(ctx, ctx->col_off, (size_t)nlin * 8));
-    hipLaunchKernelGGL(k_lin_zero_count, dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (u64 *)ctx->col_zeros64.p);
-    TRY(scan_u64(ctx, (const u64 *)ctx->col_zeros64.p, nlin, (u64 *)ctx->col_off.p, sm + SM_TOTAL_UNPRED));
-    u64 zeros_found = 0;
-    HIPCHK(hipMemcpyAsync(&zeros_found, sm + SM_TOTAL_UNPRED, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HDEC_CHECK(ctx);
-    total_sym = ctx->hdec_res[0];
-    if ((int64_t)total_sym < n) FAIL(SZHIP_ERR_STREAM, "Huffman payload holds %llu symbols, need %lld", (unsigned long long)total_sym, (long long)n);
-    if (zeros_found != E) FAIL(SZHIP_ERR_STREAM, "stream lists %llu exact values, codes need %llu", (unsigned long long)E, (unsigned long long)zeros_found);
-    T *d_out = (T *)out;
-    if (!out_on_device) { TRY(ensure(ctx, ctx->out, (size_t)n * sizeof(T))); d_out = (T *)ctx->out.p; }
-    if (E > 0) {
-        const unsigned char *lead_in = d_stream + type_off + type_size + blob, *mid_in = lead_in + lead_size, *resi_in = mid_in + nmid;
-        const unsigned gE = (unsigned)((E + 255) / 256);
-        TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T)));
-        TRY(ensure(ctx, ctx->reg_flags, (size_t)E * 8 * 3));         // flag words: f01 | f2 | mid counts
-        TRY(ensure(ctx, ctx->reg_rank, (size_t)E * 8 * 3));          // their exclusive prefix sums
-        TRY(ensure(ctx, ctx->lor_bits, (size_t)E * 3 + 8));          // compacted own bytes of positions 0..2
-        u64 *f01 = (u64 *)ctx->reg_flags.p, *f2 = f01 + E, *mc = f2 + E;
-        u64 *s01 = (u64 *)ctx->reg_rank.p, *s2 = s01 + E, *mo = s2 + E;
-        uint8_t *own0 = (uint8_t *)ctx->lor_bits.p, *own1 = own0 + E, *own2 = own1 + E;
-        hipLaunchKernelGGL(k_exact_flags, dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, f01, f2, mc);
-        TRY(scan_u64(ctx, f01, (int64_t)E, s01, sm + SM_SCRATCH));
-        TRY(scan_u64(ctx, f2, (int64_t)E, s2, sm + SM_SCRATCH));
-        TRY(scan_u64(ctx, mc, (int64_t)E, mo, sm + SM_SCRATCH));
-        u64 mid_need = 0;
-        HIPCHK(hipMemcpyAsync(&mid_need, sm + SM_SCRATCH, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (mid_need != nmid) FAIL(SZHIP_ERR_STREAM, "stream holds %llu mid bytes, lead numbers need %llu", (unsigned long long)nmid, (unsigned long long)mid_need);
-        hipLaunchKernelGGL(k_exact_own, dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, mid_in, resi_in,
-                           (const u64 *)s01, (const u64 *)s2, (const u64 *)mo, own0, own1, own2);
-        hipLaunchKernelGGL((k_exact_build<T>), dim3(gE), dim3(256), 0, st, lead_in, (int64_t)E, req_bytes, resi_bits, mid_in, resi_in,
-                           (const u64 *)s01, (const u64 *)s2, (const u64 *)mo, (const uint8_t *)own0, (const uint8_t *)own1, (const uint8_t *)own2,
-                           median, (T *)ctx->unpred.p);
-        hipLaunchKernelGGL((k_lin_zero_move<T, 1>), dim3((unsigned)nlin), dim3(256), 0, st, (const uint16_t *)d_codes, n, (const u64 *)ctx->col_off.p,
-                           (const T *)nullptr, (T *)ctx->unpred.p, d_out);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-
-    // ---- reconstruct
-    if (msst) {
-        if (!(eb_field > 0 && eb_field < 1) || plus_bits > 16) FAIL(SZHIP_ERR_STREAM, "bad point-wise ratio / table parameters");
-        MsstHostTab ht;
-        msst_build_tab(ht, eb_field, intervals, plus_bits, false);
-        if (ndim >= 2 && !tune_int("SZ_HIP_MSST_SWEEP", 0)) {
-            msst_tab tb;
-            TRY(msst_upload(ctx, ht, intervals, true, &tb));
-            TRY(launch_pencil14<T>(ctx, G, sm, true, nullptr, d_out, d_codes, eb, intervals, (T)0, 0, &tb, ndim));
-        } else
-            TRY(msst_sweep<T>(ctx, G, ndim, true, nullptr, d_out, d_codes, ht, intervals, 0));
-    } else if (one_d) {
-        HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (tune_int("SZ_HIP_1D_SERIAL", 0))
-            hipLaunchKernelGGL((k_chain_1d<T, true>), dim3(1), dim3(64), 0, st, (const T *)nullptr, d_out, d_codes, n, eb, (T)(1 / eb), (int)intervals, median, 0);
-        else {   // decoding sees where the chain restarts (code 0): one thread per segment, nothing to verify
-            const int grid = (int)std::min<int64_t>((n + 255) / 256, 1 << 20);
-            hipLaunchKernelGGL((k_chain_seg_1d<T, true>), dim3(grid), dim3(256), 0, st, (const T *)nullptr, d_out, d_codes, n, eb, (T)(1 / eb), (int)intervals,
-                               median, 0, 1.0, (unsigned *)nullptr);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ctx->ev[3], st));
-    } else
-        TRY(launch_pencil14<T>(ctx, G, sm, true, nullptr, d_out, d_codes, eb, intervals, median, 0));
-    S.quant_kernel_launches = 1;
-    unsigned kerr = 0;
-    HIPCHK(hipMemcpyAsync(&kerr, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
-    if (!out_on_device) TRY(staged_copy(ctx, out, d_out, (size_t)n * sizeof(T), false));
-    HIPCHK(hipEventRecord(ctx->ev[4], st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (kerr) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_entropy = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = (uint64_t)n * sizeof(T);
-    if (stats) *stats = S;
-    return SZHIP_OK;
+    sz14_dec<T> d{call_base(ctx), stream_len, body_off, r0, r1, r2, pwr, out, out_on_device, {ctx, stream_in, stream_on_device, stream_len}};
+    TRY(d.read_header());
+    TRY(d.decode_codes());
+    TRY(d.place_exact());
+    TRY(d.reconstruct());
+    TRY(d.finish());
+    return d.done(stats);
 }

@@ -3,9 +3,6 @@
 // outgrew the buffers), or the tests' switch -- any of them sends the call round again with the host's book
 static bool book_declines(unsigned rec_status, unsigned long long plan_status, int test_switch) { return rec_status != 0 || plan_status != 0 || test_switch != 0; }
 
-// how often a histogram of `intervals` bins is replicated in LDS (k_hist_u16, k_col_hist): 2^shift copies within `cap_bins` bins, 64 copies at the most
-static int hist_rshift(unsigned intervals, size_t cap_bins) { int r = 0; while (r < 6 && ((size_t)intervals << (r + 1)) <= cap_bins) ++r; return r; }
-
 // Which sweep a compress call takes and how its codes are packed: a pure function of the geometry, the alphabet, the regression-block count, the switches and the
 // context's flags, made once the chains' overlap is settled; `revise` is its one later change.
 struct sz21_plan {
@@ -91,18 +88,16 @@ sz21_plan sz21_make_plan(const szhip_ctx *ctx, const szh_geom3 &G, unsigned inte
 // it, in reverse order of declaration: fed_guard is lowered after the join.
 // se_segs, tab_code and tab_len are copied to the device asynchronously and live until the final synchronisation.  The object is neither copied nor moved.
 template <class T>
-struct sz21_call {
+struct sz21_call : call_base {
     static constexpr int is_double = sizeof(T) == 8;
     static constexpr int64_t LINE = 128 / (int64_t)sizeof(T);         // values per 128-byte cache line
     // ---- arguments, geometry
-    szhip_ctx *const ctx; const szhip_params *const prm; const unsigned char *meta; const size_t meta_len; const int out_on_device; unsigned char **const out; size_t *const out_size;
-    const double eb_in; const T eb; const hipStream_t st;
+    const szhip_params *const prm; const unsigned char *meta; const size_t meta_len; const int out_on_device; unsigned char **const out; size_t *const out_size;
+    const double eb_in; const T eb;
     const bool two_d;                                          // r0 == 0: a 2-D array r1 x r2 (sz_float.c:5516)
     const szh_geom3 G; const int ncoef, ncols; const int64_t n, nb;
-    // ---- statistics and the SZ_HIP_TIMING trace
-    const double t_begin = now_ms(); double host_ms = 0;
+    // ---- the SZ_HIP_TIMING trace
     const int tp_on = tune_int("SZ_HIP_TIMING", 0); double tp_t[32]; const char *tp_n[32]; int tp_k = 0;
-    szhip_stats S;
     // ---- device arrays, the pinned words the fit pass fills
     const T *d_in = nullptr; u64 *sm = nullptr; T *d_coef = nullptr; uint8_t *d_lor = nullptr; uint16_t *d_nat = nullptr, *d_blk = nullptr; unsigned *d_hist = nullptr, *h_hist = nullptr;
     T noise = 0; bool fit_tile = false; int ft_nseg = 0;
@@ -118,7 +113,6 @@ struct sz21_call {
     unsigned enc_maxlen = 0; bool enc32 = false; size_t lds_e32 = 0;
     unsigned char *hdr = nullptr; size_t pre_len = 0, sections_total = 0, hdr_len = 0, unpred_bytes = 0, total_len = 0; u64 total_bits = 0, total_unpred = 0;
     u64 h_small[SM_COUNT];                                     // the device's small words, read after the final synchronisation
-    bool synced = false;                                       // the call's final synchronisation is behind us (the device book checks before it delivers)
     // ---- the coefficient chains: everything the host threads touch (see LIFETIMES)
     szhost_coeffs cf;
     size_t sec_len[4] = {0, 0, 0, 0};           // the coefficient sections (built by the chain threads in the context's PINNED buffers: they go to the device from where they are, beside
@@ -136,10 +130,10 @@ struct sz21_call {
     bool pool_busy = false;                     // a job of this call is on the context's chain workers
     bool cf_own = false;                        // cf's output arrays belong to the context
     sz21_call(szhip_ctx *c, size_t r0, size_t r1, size_t r2, double eb_, const szhip_params *p, const unsigned char *m, size_t ml, int ood, unsigned char **o, size_t *os)
-        : ctx(c), prm(p), meta(m), meta_len(ml), out_on_device(ood), out(o), out_size(os), eb_in(eb_), eb((T)eb_), st(c->stream), two_d(r0 == 0),
+        : call_base(c), prm(p), meta(m), meta_len(ml), out_on_device(ood), out(o), out_size(os), eb_in(eb_), eb((T)eb_), two_d(r0 == 0),
           G(r0 == 0 ? szh_make_geom2((int)r1, (int)r2) : szh_make_geom3((int)r0, (int)r1, (int)r2)), ncoef(r0 == 0 ? 3 : 4), ncols(G.g0.num * G.g1.num), n(G.n), nb(G.nblocks)
     {
-        memset(&S, 0, sizeof(S)); memset(&cf, 0, sizeof(cf));
+        memset(&cf, 0, sizeof(cf));
         S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)nb;
     }
     // no return may leave the section threads (or the pool's workers) running on this object, or the pool armed
@@ -187,15 +181,8 @@ struct sz21_call {
     //      needs only the bound -- except for the mean shortcut of the selection, which the optimiser may switch on; it is run WITHOUT it here and repeated in the
     //      (rare) use_mean case (join_fit).
     int stage_and_fit(const void *data, int data_on_device) {
-        d_in = (const T *)data;
-        if (!data_on_device) {
-            TRY(ensure(ctx, ctx->in, (size_t)n * sizeof(T)));
-            TRY(staged_copy(ctx, ctx->in.p, data, (size_t)n * sizeof(T), true));
-            d_in = (const T *)ctx->in.p;
-        }
-        TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-        sm = (u64 *)ctx->small.p;
-        HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
+        TRY(stage_input(ctx, data, data_on_device, (size_t)n, &d_in));
+        TRY(clear_small(ctx, &sm));
         static const u64 minmax_init[2] = {~0ull, 0ull};          // ordered encodings: the fit pass reduces the array's range into these
         HIPCHK(hipMemcpyAsync(sm + SM_MINMAX, minmax_init, 16, hipMemcpyHostToDevice, st));
         TRY(ensure(ctx, ctx->coef, (size_t)nb * 4 * sizeof(T)));
@@ -328,11 +315,11 @@ struct sz21_call {
     void make_section(int e) {
         std::vector<uint32_t> h32(65536, 0);
         for (size_t i = 0; i < reg_count; ++i) h32[(size_t)cf.codes[e][i]]++;
-        szhost_huff *ch = szhost_huff_build(131072, h32.data(), nullptr, 65536);
+        const huff_ptr ch(szhost_huff_build(131072, h32.data(), nullptr, 65536));
         if (!ch) { section_failed = 1; return; }
-        const size_t tb = szhost_huff_tree_size(ch);
+        const size_t tb = szhost_huff_tree_size(ch.get());
         const size_t enc_cap = (size_t)((ch->total_bits + 7) / 8) + 16;
-        if (sizeof(T) + 12 + tb + 8 + enc_cap + 4 + cf.unpred_count[e] * sizeof(T) > ctx->sec_pin_cap[e]) { szhost_huff_free(ch); section_failed = 1; return; }
+        if (sizeof(T) + 12 + tb + 8 + enc_cap + 4 + cf.unpred_count[e] * sizeof(T) > ctx->sec_pin_cap[e]) { section_failed = 1; return; }
         unsigned char *const sec0 = ctx->sec_pin[e];
         unsigned char *q = sec0;
         if (is_double) szhost_put_f64be(q, cf.prec[e]); else szhost_put_f32be(q, (float)cf.prec[e]);
@@ -340,13 +327,12 @@ struct sz21_call {
         szhost_put_u32be(q, 32768); q += 4;
         szhost_put_u32be(q, (uint32_t)tb); q += 4;
         szhost_put_u32be(q, (uint32_t)ch->n_nodes); q += 4;
-        szhost_huff_tree_write(ch, q); q += tb;
-        const size_t enc = szhost_huff_encode_i32(ch, cf.codes[e], reg_count, q + 8);
+        szhost_huff_tree_write(ch.get(), q); q += tb;
+        const size_t enc = szhost_huff_encode_i32(ch.get(), cf.codes[e], reg_count, q + 8);
         szhost_put_u64be(q, enc); q += 8 + enc;
         szhost_put_u32be(q, (uint32_t)cf.unpred_count[e]); q += 4;
         memcpy(q, cf.unpred[e], cf.unpred_count[e] * sizeof(T)); q += cf.unpred_count[e] * sizeof(T);
         sec_len[e] = (size_t)(q - sec0);
-        szhost_huff_free(ch);
     }
     // ---- regression coefficient chain (a serial recurrence with reconstruction feedback: host) and its Huffman streams.
     //      The chains of the four (three) coefficients are independent of each other and each is bound by the latency of its own
@@ -621,11 +607,7 @@ struct sz21_call {
         HIPCHK(hipEventRecord(ctx->ev_in, st));                    // codes complete
         HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, ctx->stream2));
-        const int use_lds = intervals <= 16384, rshift = use_lds ? hist_rshift(intervals, 16384) : 0;
-        const size_t lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
-        int grid = (int)std::min<int64_t>((n / 8 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), lds, ctx->stream2, (const uint16_t *)d_nat, n, intervals, rshift, use_lds, d_hist, (int64_t)0);
-        HIPCHK(hipGetLastError());
+        TRY(launch_hist_u16(ctx, ctx->stream2, d_nat, 0, n, intervals, d_hist));
         HIPCHK(hipMemcpyAsync(h_hist, d_hist, (size_t)intervals * 4, hipMemcpyDeviceToHost, ctx->stream2));
         HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
         return SZHIP_OK;
@@ -663,8 +645,6 @@ struct sz21_call {
     int hist_and_order_sliced() {
         const int NS = std::min(P.slices_req, G.g0.num);
         TRY(prepare_permute());
-        const int use_lds = intervals <= 16384, rshift = use_lds ? hist_rshift(intervals, 16384) : 0;
-        const size_t hist_lds = use_lds ? ((size_t)intervals << rshift) * 4 : 16;
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)intervals * 4, ctx->stream2));
         HIPCHK(hipMemsetAsync(ctx->col_zeros.p, 0, (size_t)ncols * 4, ctx->stream3));
         const unsigned tag = (ctx->epoch & 0xfffu) << 20;
@@ -690,8 +670,7 @@ struct sz21_call {
                 // (k_hist_u16 counts groups of eight codes: a slice of it ends on a multiple of eight below the slice's last code, the last slice takes the rest)
                 const int64_t h_lo = hist_first, h_hi = b0_hi >= G.g0.num ? (int64_t)n : ((int64_t)rows_need * G.d0) / 8 * 8;
                 hist_first = h_hi;
-                const int grid = (int)std::min<int64_t>(((h_hi - h_lo) / 8 + 255) / 256 + 1, 2048);
-                if (h_hi > h_lo) hipLaunchKernelGGL(k_hist_u16, dim3(grid), dim3(256), hist_lds, ctx->stream2, (const uint16_t *)d_nat, h_hi, intervals, rshift, use_lds, d_hist, h_lo);
+                if (h_hi > h_lo) TRY(launch_hist_u16(ctx, ctx->stream2, d_nat, h_lo, h_hi, intervals, d_hist));
                 if (!P.segenc) launch_permute(ctx->stream3, b0_done * G.g1.num, (b0_hi - b0_done) * G.g1.num);
                 HIPCHK(hipGetLastError());
                 b0_done = b0_hi;
@@ -784,27 +763,6 @@ struct sz21_call {
         HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
         return SZHIP_OK;
     }
-    // the stream to the caller: into its device buffer (of capacity *out_size), as a pointer into the context's buffer, or as a malloc'd host copy; synchronises
-    // the first stream unless that is behind us and nothing was enqueued since
-    int deliver(unsigned char *d_stream, size_t len, bool in_place) {
-        if (out_on_device == 2) {
-            if (!*out || *out_size < len) FAIL(SZHIP_ERR_ARG, "caller's device buffer too small (%zu < %zu)", *out_size, len);
-            if (!in_place) { HIPCHK(hipMemcpyAsync(*out, d_stream, len, hipMemcpyDeviceToDevice, st)); synced = false; }
-            if (!synced) HIPCHK(hipStreamSynchronize(st));
-        } else if (out_on_device) {
-            if (!synced) HIPCHK(hipStreamSynchronize(st));
-            *out = d_stream;
-        } else {
-            unsigned char *h = (unsigned char *)malloc(len ? len : 1);
-            if (!h) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
-            const int rc_copy = staged_copy(ctx, h, d_stream, len, false);
-            if (rc_copy != SZHIP_OK) { free(h); return rc_copy; }
-            *out = h;
-        }
-        *out_size = len;
-        synced = true;
-        return SZHIP_OK;
-    }
     // after the final synchronisation: the wavefront kernel's error flag; the device book's verdict (`declined`, with its status; the caller's wrapper repeats the
     // call with the host's book, so no message on stderr); the packed bit count and the device's count of zero codes must match what the code book predicted
     int check_final(bool declined, unsigned book_status, u64 bits, u64 unpred) {
@@ -821,11 +779,8 @@ struct sz21_call {
         return SZHIP_OK;
     }
     void finish_stats(size_t len, u64 unpred, int packing, int book_on_device) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms;
-        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-        hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
-        S.n_unpred = unpred; S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = len; S.packing = packing; S.book_on_device = book_on_device;
+        compress_times(ctx, S, host_ms, t_begin, len);
+        S.n_unpred = unpred; S.packing = packing; S.book_on_device = book_on_device;
     }
     // ---- the code book on the device (k_huff_book), the header written by kernels, the packing passes: nothing waits for the host before the call's one
     //      synchronisation; the checks come before an output is published
@@ -866,7 +821,6 @@ struct sz21_call {
         TRY(enqueue_readback());
         HIPCHK(hipMemcpyAsync(ctx->book_pin, ctx->book_rec.p, 32 + SZH_PLAN_COUNT * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));                                      // the call's one wait behind the sweep
-        synced = true;
         TP("final sync");
         szh_book_rec rec; memcpy(&rec, ctx->book_pin, sizeof(rec));
         const u64 *const plan = (const u64 *)ctx->book_pin + 4;
@@ -874,7 +828,7 @@ struct sz21_call {
         TRY(check_final(book_declines(rec.status, plan[SZH_PLAN_STATUS], tune_int("SZ_HIP_TEST_BOOK_FALLBACK", 0)), rec.status ? rec.status : (unsigned)plan[SZH_PLAN_STATUS],
                         rec.total_bits, rec.total_unpred));
         const size_t len = (size_t)plan[SZH_PLAN_TOTAL_LEN];
-        TRY(deliver(d_stream, len, in_place));
+        TRY(deliver_stream(ctx, d_stream, len, out_on_device, out, out_size, in_place, true));     // (the final synchronisation is behind us)
         finish_stats(len, rec.total_unpred, 1, 1);
         return SZHIP_OK;
     }
@@ -888,43 +842,38 @@ struct sz21_call {
         HIPCHK(hipEventSynchronize(ctx->ev_fit));
         TP("hist on host");
         double h0 = now_ms();
-        szhost_huff *hf = szhost_huff_build(2 * (int)intervals, h_hist, nullptr, intervals);
+        const huff_ptr hf = host_book(h_hist, intervals, tab_code, tab_len, &enc_maxlen);
         host_ms += now_ms() - h0;
         total_unpred = h_hist[0];
         if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
         TP("tree built");
         join_sections();
         TP("sections joined");
-        if (section_failed) { szhost_huff_free(hf); FAIL(SZHIP_ERR_INTERNAL, "coefficient Huffman build failed"); }
+        if (section_failed) FAIL(SZHIP_ERR_INTERNAL, "coefficient Huffman build failed");
         for (int e = 0; e < ncoef; ++e) sections_total += sec_len[e];
         h0 = now_ms();
-        const size_t tree_bytes = szhost_huff_tree_size(hf);
+        const size_t tree_bytes = szhost_huff_tree_size(hf.get());
         pre_len = meta_len + 8 + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes + 1 + sizeof(T) + ind_bytes;     // the header in front of the coefficient sections
         hdr_len = pre_len + sections_total + 8;
         unpred_bytes = (size_t)total_unpred * sizeof(T);
         total_len = hdr_len + unpred_bytes + (size_t)((hf->total_bits + 7) / 8);
         // assembled in pinned memory (the histogram that lived there has been consumed): with coefficient sections the header is megabytes,
         // and an asynchronous copy from pageable memory of that size makes the runtime pin and unpin the pages
-        { const int rc = ensure_pinned(ctx, pre_len + 8 + 64); if (rc != SZHIP_OK) { szhost_huff_free(hf); return rc; } }
+        TRY(ensure_pinned(ctx, pre_len + 8 + 64));
         hdr = (unsigned char *)ctx->pinned;                              // [the header in front of the sections][the eight bytes behind them]
         memset(hdr, 0, pre_len + 8);
         unsigned char *q = put_front(hdr);
         szhost_put_u32be(q, intervals); q += 4;
         szhost_put_u32be(q, (uint32_t)tree_bytes); q += 4;
         szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;
-        szhost_huff_tree_write(hf, q); q += tree_bytes;
+        szhost_huff_tree_write(hf.get(), q); q += tree_bytes;
         *q++ = (unsigned char)use_mean;
         memcpy(q, &mean, sizeof(T)); q += sizeof(T);
         memcpy(q, ind_bits, ind_bytes); q += ind_bytes;
         const uint64_t tu = total_unpred; memcpy(q, &tu, 8);
-        // device code tables: right-aligned code bits + lengths, one entry per symbol < intervals
-        tab_code.resize(intervals); tab_len.resize(intervals);
-        for (unsigned s = 0; s < intervals; ++s) { tab_code[s] = hf->code[s]; tab_len[s] = hf->len[s]; }
         total_bits = hf->total_bits;
-        szhost_huff_free(hf);
         // code words of up to 32 bits and a table that fits beside the window in LDS: k_encode32 (32 consecutive codes per thread) packs the
         // payload, from the table `code << 8 | length`; anything else stays with k_encode
-        for (unsigned s = 0; s < intervals; ++s) enc_maxlen = std::max<unsigned>(enc_maxlen, tab_len[s]);
         lds_e32 = (size_t)intervals * 8 + ((size_t)SZH_E32_ROUND * enc_maxlen / 32 + 4) * 4 + 16;
         enc32 = enc_maxlen >= 1 && enc_maxlen <= 32 && lds_e32 <= 60 * 1024 && tune_int("SZ_HIP_ENC32", 1);
         if (P.revise(enc_maxlen)) {                                      // (the code book does not fit the packing passes on natural-order codes)
@@ -935,11 +884,7 @@ struct sz21_call {
         if (P.segenc) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 32) | tab_len[s] | (s == 0 ? 0x10000u : 0u);      // (k_col_encode's table: szh_segenc.h)
         else if (enc32) for (unsigned s = 0; s < intervals; ++s) tab_code[s] = (tab_code[s] << 8) | tab_len[s];
         host_ms += now_ms() - h0;
-        TRY(ensure(ctx, ctx->code_tab, (size_t)intervals * 8));
-        TRY(ensure(ctx, ctx->len_tab, (size_t)intervals));
-        HIPCHK(hipMemcpyAsync(ctx->code_tab.p, tab_code.data(), (size_t)intervals * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->len_tab.p, tab_len.data(), (size_t)intervals, hipMemcpyHostToDevice, st));
-        return SZHIP_OK;
+        return upload_code_tables(ctx, tab_code, tab_len);
     }
     // the header in front of the coefficient sections and the eight bytes behind them; the sections themselves from the chain threads' pinned buffers, beside the encoder
     int copy_header(unsigned char *d_stream) {
@@ -971,19 +916,14 @@ struct sz21_call {
             HIPCHK(hipEventRecord(ctx->ev_fit, ctx->stream2));
         }
         if (total_bits > 0) {
-            const int64_t nchunks = (n + SZH_ENC_CHUNK - 1) / SZH_ENC_CHUNK;
-            TRY(ensure(ctx, ctx->chunk_bits, (size_t)nchunks * 8 + 64));
-            TRY(ensure(ctx, ctx->chunk_off, (size_t)nchunks * 8));
-            hipLaunchKernelGGL(k_chunk_bits, dim3((unsigned)((nchunks + SZH_CB_PER - 1) / SZH_CB_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const uint8_t *)ctx->len_tab.p, intervals, (u64 *)ctx->chunk_bits.p);
-            TRY(scan_u64(ctx, (const u64 *)ctx->chunk_bits.p, nchunks, (u64 *)ctx->chunk_off.p, sm + SM_TOTAL_BITS));
+            TRY(chunk_bit_offsets(ctx, d_blk, n, intervals, sm, 64));
             if (enc32) {
                 const int64_t nrounds = (n + SZH_E32_ROUND - 1) / SZH_E32_ROUND;
                 hipLaunchKernelGGL(k_encode32, dim3((unsigned)((nrounds + SZH_E32_PER - 1) / SZH_E32_PER)), dim3(256), lds_e32, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
                                    intervals, (const u64 *)ctx->chunk_off.p, base_bits, (unsigned *)d_stream);
+                HIPCHK(hipGetLastError());
             } else
-                hipLaunchKernelGGL(k_encode, dim3((unsigned)((nchunks + SZH_ENC_PER - 1) / SZH_ENC_PER)), dim3(256), 0, st, (const uint16_t *)d_blk, n, (const u64 *)ctx->code_tab.p,
-                                   (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)ctx->chunk_off.p, base_bits, (unsigned *)d_stream);
-            HIPCHK(hipGetLastError());
+                TRY(launch_encode(ctx, d_blk, n, intervals, base_bits, d_stream));
         }
         if (total_unpred > 0) HIPCHK(hipStreamWaitEvent(st, ctx->ev_fit, 0));
         return SZHIP_OK;
@@ -1009,7 +949,7 @@ struct sz21_call {
         if (total_unpred > 0) HIPCHK(hipMemcpyAsync(d_stream + hdr_len, ctx->unpred.p, unpred_bytes, hipMemcpyDeviceToDevice, st));
         if (sections_total) HIPCHK(hipStreamWaitEvent(st, ctx->ev_sec, 0));
         TRY(enqueue_readback());
-        TRY(deliver(d_stream, total_len, in_place));
+        TRY(deliver_stream(ctx, d_stream, total_len, out_on_device, out, out_size, in_place, false));
         TP("final sync");
         print_trace();
         const int rc = check_final(false, 0, total_bits, total_unpred);
@@ -1041,8 +981,7 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
     TRY(c.launch_sweep());
     TRY(c.hist_and_order());
     TRY(c.P.dev_book ? c.encode_with_device_book() : c.encode_with_host_book());
-    if (stats) *stats = c.S;
-    return SZHIP_OK;
+    return c.done(stats);
 }
 
 // Huffman decode of `n` symbols on the device (self-synchronising sub-sequence decode, k_hdec_*): `d_bits` points at the payload,
@@ -1052,13 +991,12 @@ int compress_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r
         /* (no message on stderr: the caller's wrapper repeats the call with a synchronisation per round) */ \
         snprintf((ctx)->err, sizeof((ctx)->err), "Huffman decode: %llu start guesses still moving after two rounds", (ctx)->hdec_res[1]); return SZHIP_ERR_INTERNAL; } } while (0)
 int huff_decode_device(szhip_ctx *ctx, u64 *sm, const unsigned char *d_bits, unsigned bytes_before, u64 total_bits, const std::vector<uint32_t> &dtab, int n_nodes,
-                       int single_symbol, int64_t n, uint16_t *d_out_codes, u64 *total_sym_host)
+                       int single_symbol, int64_t n, uint16_t *d_out_codes)
 {
-    // *total_sym_host receives the number of symbols the payload holds ASYNCHRONOUSLY: the caller compares it with n after its next
-    // synchronisation of the stream (the write pass below never stores beyond n, so a short payload is harmless until then)
+    // ctx->hdec_res[0] receives the number of symbols the payload holds ASYNCHRONOUSLY: the caller compares it with n after its next
+    // synchronisation of the stream (check_decoded; the write pass below never stores beyond n, so a short payload is harmless until then)
     if (!ctx->hdec_res) HIPCHK(hipHostMalloc((void **)&ctx->hdec_res, 64, hipHostMallocDefault));
     ctx->hdec_res[0] = (u64)n; ctx->hdec_res[1] = 0;
-    *total_sym_host = (u64)n;
     hipStream_t st = ctx->stream;
     if (single_symbol >= 0) {
         hipLaunchKernelGGL(k_fill_u16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_out_codes, n, (uint16_t)single_symbol);
@@ -1117,12 +1055,22 @@ int huff_decode_device(szhip_ctx *ctx, u64 *sm, const unsigned char *d_bits, uns
     return SZHIP_OK;
 }
 
+// behind that synchronisation: every start guess settled, the payload holds n symbols, the codes' zeros are as many as the `listed` values of the stream (`what` they are)
+int check_decoded(szhip_ctx *ctx, int64_t n, u64 listed, u64 zeros_found, const char *what)
+{
+    HDEC_CHECK(ctx);
+    if ((int64_t)ctx->hdec_res[0] < n) FAIL(SZHIP_ERR_STREAM, "Huffman payload holds %llu symbols, need %lld", ctx->hdec_res[0], (long long)n);
+    if (zeros_found != listed) FAIL(SZHIP_ERR_STREAM, "stream lists %llu %s values, codes need %llu", (unsigned long long)listed, what, (unsigned long long)zeros_found);
+    return SZHIP_OK;
+}
+
 // everything the host reads from an SZ 2.1 regression-type stream before the unpredictable values
 template <class T> struct dec_header {
     T eb = 0, mean = 0;
-    unsigned intervals = 0; int use_mean = 0, n_nodes = 0, single_symbol = -1;
+    unsigned intervals = 0; int use_mean = 0;
+    dec_table D;                                       // of the type array's tree
     size_t reg_count = 0, ind_off = 0, unpred_off = 0, pay_off = 0; uint64_t total_unpred = 0;
-    std::vector<T> coef; std::vector<uint32_t> dtab;   // coef: decoded regression coefficients, compact [4][reg_count]
+    std::vector<T> coef;                               // decoded regression coefficients, compact [4][reg_count]
     bool defer = false;                                // in: the caller runs the coefficient sections' decode itself (finish), beside other work
     std::function<int()> finish; char finish_err[200] = {0};
 };
@@ -1134,11 +1082,10 @@ int parse_header(const unsigned char *hs, size_t avail, size_t stream_len, size_
 {
     const int ncoef = want_block_size == SZH_BLOCK_SIZE_2D ? 3 : 4;
     const int is_double = sizeof(T) == 8;
-#define PFAIL(code, ...) do { snprintf(err, errlen, __VA_ARGS__); if (hf) szhost_huff_free(hf); return (code); } while (0)
+#define PFAIL(code, ...) do { snprintf(err, errlen, __VA_ARGS__); return (code); } while (0)
 #define NEED(k) do { const size_t end_ = (size_t)(q - hs) + (size_t)(k); if (end_ > stream_len) PFAIL(SZHIP_ERR_STREAM, "truncated stream"); \
-                     if (end_ > avail) { *need = std::min(stream_len, end_ + need_more); if (hf) szhost_huff_free(hf); return 1; } } while (0)
+                     if (end_ > avail) { *need = std::min(stream_len, end_ + need_more); return 1; } } while (0)
     size_t need_more = 0;                      // what a longer prefix should hold beyond the bytes asked for (the coefficient sections still to come)
-    szhost_huff *hf = nullptr;
     const unsigned char *q = hs + body_off;
     const int tp_on = tune_int("SZ_HIP_TIMING", 0); const double tp0 = now_ms();
     auto mark = [&](const char *nm) { if (tp_on) fprintf(stderr, "[header %s %.3f] ", nm, now_ms() - tp0); };
@@ -1152,8 +1099,7 @@ int parse_header(const unsigned char *hs, size_t avail, size_t stream_len, size_
     if (H.intervals < 4 || H.intervals > 65536) PFAIL(SZHIP_ERR_STREAM, "bad interval count %u", H.intervals);
     NEED(tree_size);
     if (node_count <= 0 || szhost_huff_serial_size(node_count) > tree_size) PFAIL(SZHIP_ERR_STREAM, "bad Huffman tree size");
-    hf = szhost_huff_from_bytes(2 * (int)H.intervals, q, node_count);
-    if (!hf) PFAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
+    if (!read_tree(q, node_count, H.intervals, H.D)) PFAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
     q += tree_size;
     NEED(1 + sizeof(T));
     H.use_mean = *q++;
@@ -1214,12 +1160,10 @@ int parse_header(const unsigned char *hs, size_t avail, size_t stream_len, size_
             size_t sec_zeros[4] = {0, 0, 0, 0};
             const std::vector<unsigned char> all_reg(reg_count, 0);
             auto decode_section = [&](int e) {
-                szhost_huff *ch = szhost_huff_from_bytes(4 * sd[e].crad, sd[e].tree_at, sd[e].cnc);
+                const huff_ptr ch(szhost_huff_from_bytes(4 * sd[e].crad, sd[e].tree_at, sd[e].cnc));
                 if (!ch) { sec_rc[e] = 1; return; }
                 std::vector<int> codes(reg_count);
-                const int ok = szhost_huff_decode_i32(ch, sd[e].pay_at, sd[e].enc, reg_count, codes.data());   // bounded by the section's own length
-                szhost_huff_free(ch);
-                if (!ok) { sec_rc[e] = 2; return; }
+                if (!szhost_huff_decode_i32(ch.get(), sd[e].pay_at, sd[e].enc, reg_count, codes.data())) { sec_rc[e] = 2; return; }   // (bounded by the section's own length)
                 // every zero code takes one verbatim coefficient (szd_float.c:5809-5820): the list must hold them all
                 size_t zeros = 0;
                 for (size_t i = 0; i < reg_count; ++i) zeros += codes[i] == 0;
@@ -1255,11 +1199,6 @@ int parse_header(const unsigned char *hs, size_t avail, size_t stream_len, size_
     H.unpred_off = (size_t)(q - hs);
     if (H.total_unpred > (stream_len - H.unpred_off) / sizeof(T)) PFAIL(SZHIP_ERR_STREAM, "truncated stream");
     H.pay_off = H.unpred_off + (size_t)H.total_unpred * sizeof(T);
-    H.dtab.resize((size_t)hf->n_nodes * 2);
-    szhost_huff_decode_table(hf, H.dtab.data());
-    H.single_symbol = hf->t[0] ? (int)hf->C[0] : -1;
-    H.n_nodes = hf->n_nodes;
-    szhost_huff_free(hf);
     mark("done");
     return 0;
 #undef NEED
@@ -1334,18 +1273,17 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     if (tune_int("SZ_HIP_TIMING", 0)) fprintf(stderr, "[header on host %.3f ms after the call began]\n", now_ms() - t_begin);
     const T eb = H.eb, mean = H.mean;
     const unsigned intervals = H.intervals;
-    const int use_mean = H.use_mean, n_nodes = H.n_nodes, single_symbol = H.single_symbol;
+    const int use_mean = H.use_mean, n_nodes = H.D.n_nodes, single_symbol = H.D.single_symbol;
     const size_t reg_count = H.reg_count, unpred_off = H.unpred_off, pay_off = H.pay_off;
     const uint64_t total_unpred = H.total_unpred;
     std::vector<T> &hcoef = H.coef;
-    std::vector<uint32_t> &dtab = H.dtab;
+    std::vector<uint32_t> &dtab = H.D.dtab;
     const u64 total_bits = (u64)(stream_len - pay_off) * 8;
     S.intervals = intervals; S.use_mean = use_mean; S.n_reg_blocks = reg_count; S.n_unpred = total_unpred;
     host_ms += now_ms() - h0;
 
-    TRY(ensure(ctx, ctx->small, SM_COUNT * 8));
-    u64 *sm = (u64 *)ctx->small.p;
-    HIPCHK(hipMemsetAsync(sm, 0, SM_COUNT * 8, st));
+    u64 *sm = nullptr;
+    TRY(clear_small(ctx, &sm));
     // The inverse sweep: k_beam wherever it applies (szh_beam.h), k_pencil on natural-order codes for the rest (2-D, SZ 1.4, rows that are no multiple of four values).
     // (Rounds 3 - 5 ran Lorenzo-only 3-D arrays through the hyperplane "ribbon" mapping in its own code / value order, k_unribbon behind it: removed in round 6.)
     const size_t nat_elems = (size_t)n;
@@ -1355,8 +1293,7 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     uint16_t *d_nat = (uint16_t *)ctx->codes_nat.p, *d_blk = (uint16_t *)ctx->codes_blk.p;
 
     // ---- Huffman decode of the type array
-    u64 total_sym = 0;
-    TRY(huff_decode_device(ctx, sm, d_stream + pay_off, (unsigned)std::min<size_t>(pay_off, 4096), total_bits, dtab, n_nodes, single_symbol, n, d_blk, &total_sym));
+    TRY(huff_decode_device(ctx, sm, d_stream + pay_off, (unsigned)std::min<size_t>(pay_off, 4096), total_bits, dtab, n_nodes, single_symbol, n, d_blk));
 
     // ---- natural order, unpredictable values into the output array
     const int ncols = G.g0.num * G.g1.num;
@@ -1364,8 +1301,8 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     TRY(ensure(ctx, ctx->col_zeros64, (size_t)ncols * 8));
     TRY(ensure(ctx, ctx->col_off, (size_t)ncols * 8));
     int perm_segb = 1, perm_nseg = 1;
-    T *d_out = (T *)out;
-    if (!out_on_device) { TRY(ensure(ctx, ctx->out, (size_t)n * sizeof(T))); d_out = (T *)ctx->out.p; }
+    T *d_out = nullptr;
+    TRY(device_out(ctx, out, out_on_device, (size_t)n, &d_out));
     T *d_sweep = d_out;                        // what the inverse sweep works on: the output array, or (mode 2) a ribbon-order value array
     // (the inverse sweep fed slice by slice while it runs, tried in round 5, measured slower -- 2.34 against 2.12 - 2.21 ms, profiles/r05_tried_fed_inverse_sweep.txt -- and
     //  removed in round 6)
@@ -1416,15 +1353,7 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     // device's time line.  The older passes (k_unpred<1> trusts the counts) keep the synchronisation here.
     ctx->hdec_res[2] = 0;
     HIPCHK(hipMemcpyAsync(&ctx->hdec_res[2], sm + SM_TOTAL_UNPRED, 8, hipMemcpyDeviceToHost, st));      // (pinned, as the decoder's own two words)
-    auto decoder_checks = [&]() -> int {
-        HDEC_CHECK(ctx);
-        total_sym = ctx->hdec_res[0];
-        const u64 zeros_found = ctx->hdec_res[2];
-        if ((int64_t)total_sym < n) FAIL(SZHIP_ERR_STREAM, "Huffman payload holds %llu symbols, need %lld", (unsigned long long)total_sym, (long long)n);
-        if (zeros_found != total_unpred) FAIL(SZHIP_ERR_STREAM, "stream lists %llu unpredictable values, codes need %llu",
-                                              (unsigned long long)total_unpred, (unsigned long long)zeros_found);
-        return SZHIP_OK;
-    };
+    auto decoder_checks = [&]() { return check_decoded(ctx, n, total_unpred, ctx->hdec_res[2], "unpredictable"); };
     const bool checks_last = col_unpack && tune_int("SZ_HIP_DEC_CHECKS_LAST", 1) != 0;
     if (!checks_last) {
         HIPCHK(hipStreamSynchronize(st));
@@ -1499,15 +1428,12 @@ int decompress_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_o
     }
     unsigned kerr = 0;
     HIPCHK(hipMemcpyAsync(&kerr, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
-    if (!out_on_device) TRY(staged_copy(ctx, out, d_out, (size_t)n * sizeof(T), false));
+    TRY(return_out(ctx, out, out_on_device, d_out, (size_t)n));
     HIPCHK(hipEventRecord(ctx->ev[4], st));
     HIPCHK(hipStreamSynchronize(st));
     if (checks_last) TRY(decoder_checks());
     if (kerr) { ctx->wave_timeout = true; FAIL(SZHIP_ERR_INTERNAL, "wavefront kernel: halo wait timed out"); }
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_entropy = ms;
-    hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
-    S.ms_host = host_ms; S.ms_total = now_ms() - t_begin; S.out_bytes = (uint64_t)n * sizeof(T);
+    decompress_times(ctx, S, host_ms, t_begin, (size_t)n * sizeof(T));
     if (stats) *stats = S;
     return SZHIP_OK;
 }
