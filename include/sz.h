@@ -224,6 +224,15 @@ unsigned char *SZ_compress_float_3D_MDQ_openmp(float *oriData, size_t r1, size_t
 unsigned char *SZ_compress_double_3D_MDQ_openmp(double *oriData, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size);
 void decompressDataSeries_float_3D_openmp(float **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data);
 void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data);
+/* A sub-box of a 3-D array out of its stream: start / end per dimension in the order r3, r2, r1 (slowest first), end exclusive.  Returns a malloc'd array of
+ * (end[0]-start[0]) x (end[1]-start[1]) x (end[2]-start[2]) values (caller frees), bit for bit that part of what SZ_decompress returns; NULL with a printed
+ * reason otherwise.  Reads what this library's SZ_decompress recognises as an OpenMP container: the streams SZ_compress_args writes for 3-D arrays under
+ * SZ_HIP_MODE=omp, where every box decodes on its own -- only the boxes that meet the region are decoded (szhip_decompress_omp_region; boxes outside it are
+ * not validated).  A stream wrapped by the zstd or gzip stage (szMode other than SZ_BEST_SPEED) has to be unwrapped WHOLE first: only the decode is partial
+ * then.  Every other stream (SZ 2.1, SZ 1.4, constant, raw, not 3-D) is refused with a message that names SZ_HIP_MODE=omp.  An unmarked stream of the
+ * `*_openmp` entry points goes to szhip_decompress_omp_region (szhip.h) with its body offset. */
+void *SZ_hip_decompress_region(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
+                               const size_t start[3], const size_t end[3]);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

@@ -61,7 +61,10 @@ void sz_slab_multi_release(void);
 /* decompress every slab of a container into one malloc'd array of dims[0] x dims[1] x dims[2] values (caller frees); NULL on error */
 void *sz_slab_decompress(const unsigned char *blob, size_t len, int *dataType, size_t dims[3]);
 
+/* reading a sub-box of a container's array back (sz_slab_decompress_region): sz_slab_region.h, which this header brings with it */
+
 #ifdef __cplusplus
 }
 #endif
+#include "sz_slab_region.h"
 #endif

@@ -182,6 +182,21 @@ int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_
                        int out_on_device, unsigned char **out, size_t *out_size, szhip_stats *stats);
 int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len,
                          size_t body_off, size_t r0, size_t r1, size_t r2, void *out, int out_on_device, szhip_stats *stats);
+/*
+ * A sub-box of an OpenMP-container stream: `out` (host or device, as above) receives the (hi[0]-lo[0]) x (hi[1]-lo[1]) x (hi[2]-lo[2]) values of
+ * [lo, hi) -- dim 0 slowest, `hi` exclusive --, contiguous, bit for bit the crop of what szhip_decompress_omp writes for the same stream; no byte
+ * outside that buffer is written.  Only the boxes that meet the region are decoded (every box restarts the predictor and has its own payload):
+ * device work, copies and workspace grow with their number, the host walks the stream's per-box tables once.  Of a host stream the tables and the
+ * spans of the covered boxes are uploaded, not the stream.  A region that ends on box boundaries is written by the sweeps themselves; any other goes
+ * through a staging array of the covered boxes and is cropped out of it (k_omp_crop).
+ * stats: n_blocks the boxes decoded, n_elements the region's values, n_unpred the verbatim values of the decoded boxes; quant_kernel as above.
+ * NOT validated: boxes the region does not touch.  The header and table checks of szhip_decompress_omp are made (SZHIP_ERR_STREAM / SZHIP_ERR_UNSUP
+ * exactly where it gives them), the payloads and verbatim-value counts are checked for the decoded boxes only -- a damaged payload elsewhere is
+ * neither detected nor does it affect the result.  SZHIP_ERR_ARG: lo[d] >= hi[d], or hi[d] beyond the extent.
+ */
+int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len,
+                                size_t body_off, size_t r0, size_t r1, size_t r2, const size_t lo[3], const size_t hi[3],
+                                void *out, int out_on_device, szhip_stats *stats);
 
 /*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of

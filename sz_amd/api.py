@@ -144,10 +144,23 @@ def _bind(L):
         L.szhip_decompress_omp.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
                                            ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_stats)]
         L.szhip_decompress_omp.restype = ctypes.c_int
+    if hasattr(L, "szhip_decompress_omp_region"):
+        L.szhip_decompress_omp_region.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
+                                                  ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_region.restype = ctypes.c_int
     if hasattr(L, "szhip_huff_book"):
         L.szhip_huff_book.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.POINTER(szhip_book_record)]
         L.szhip_huff_book.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_decompress_region"):
+        L.SZ_hip_decompress_region.argtypes = [ctypes.c_int, ctypes.c_void_p, sz] + [sz] * 5 + [ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.SZ_hip_decompress_region.restype = ctypes.c_void_p
+        L.sz_slab_compress.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, sz, sz, sz, ctypes.c_int]
+        L.sz_slab_compress.restype = ctypes.c_void_p
+        L.sz_slab_decompress.argtypes = [ctypes.c_void_p, sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(sz * 3)]
+        L.sz_slab_decompress.restype = ctypes.c_void_p
+        L.sz_slab_decompress_region.argtypes = [ctypes.c_void_p, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]
+        L.sz_slab_decompress_region.restype = ctypes.c_void_p
     L.szhost_write_meta.argtypes = [ctypes.POINTER(szhost_meta), ctypes.c_ubyte, ctypes.c_char_p]
     L.szhost_write_meta.restype = sz
     L.free.argtypes = [ctypes.c_void_p]
@@ -223,6 +236,62 @@ def SZ_decompress(stream, shape, dtype):
     arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(n,)).copy().reshape(shape)
     lib().free(p)
     return arr
+
+
+def _take(p, shape, dt):
+    """a malloc'd array of the library as a numpy array of its own; the library's memory is freed"""
+    ct = ctypes.c_float if dt == SZ_FLOAT else ctypes.c_double
+    arr = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(int(np.prod(shape)),)).copy().reshape(shape)
+    lib().free(p)
+    return arr
+
+
+def _box(lo, hi):
+    return (ctypes.c_size_t * 3)(*[int(v) for v in lo]), (ctypes.c_size_t * 3)(*[int(v) for v in hi])
+
+
+def SZ_hip_decompress_region(stream, shape, dtype, lo, hi):
+    """The sub-box [lo, hi) (per dimension, slowest first, hi exclusive) of a 3-D array out of the stream SZ_compress_args wrote for it under SZ_HIP_MODE=omp
+    (include/sz.h): only the boxes of the OpenMP container that meet the region are decoded.  Any other stream raises."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    buf = ctypes.create_string_buffer(bytes(stream), len(stream))
+    c_lo, c_hi = _box(lo, hi)
+    p = lib().SZ_hip_decompress_region(dt, buf, len(stream), *_dims5(shape), c_lo, c_hi)
+    if not p:
+        raise SZError("SZ_hip_decompress_region returned NULL")
+    return _take(p, tuple(int(h) - int(l) for l, h in zip(lo, hi)), dt)
+
+
+def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
+    """include/sz_slab.h: a 3-D array as `slabs` slabs in one container (bytes)."""
+    a = np.ascontiguousarray(data)
+    n = ctypes.c_size_t(0)
+    p = lib().sz_slab_compress(_dtype_code(a), a.ctypes.data, ctypes.byref(n), errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, *a.shape, slabs)
+    if not p:
+        raise SZError("sz_slab_compress returned NULL")
+    out = ctypes.string_at(p, n.value)
+    lib().free(p)
+    return out
+
+
+def sz_slab_decompress(blob):
+    """include/sz_slab.h: the whole array of a slab container."""
+    dt, dims = ctypes.c_int(0), (ctypes.c_size_t * 3)()
+    p = lib().sz_slab_decompress(bytes(blob), len(blob), ctypes.byref(dt), ctypes.byref(dims))
+    if not p:
+        raise SZError("sz_slab_decompress returned NULL")
+    return _take(p, tuple(dims), dt.value)
+
+
+def sz_slab_decompress_region(blob, lo, hi):
+    """include/sz_slab_region.h (part of sz_slab.h): the sub-box [lo, hi) of a slab container's array; only the slabs that meet it are touched, and of a slab that is an OpenMP container only
+    the boxes that do."""
+    dt = ctypes.c_int(0)
+    c_lo, c_hi = _box(lo, hi)
+    p = lib().sz_slab_decompress_region(bytes(blob), len(blob), c_lo, c_hi, ctypes.byref(dt))
+    if not p:
+        raise SZError("sz_slab_decompress_region returned NULL")
+    return _take(p, tuple(int(h) - int(l) for l, h in zip(lo, hi)), dt.value)
 
 
 def SZ_hip_last_stats():
@@ -423,6 +492,17 @@ class HipContext:
                                         body_off, shape3[0], shape3[1], shape3[2], out_ptr, int(out_on_device), ctypes.byref(st))
         if rc:
             self._err(rc, "szhip_decompress_omp")
+        return st
+
+    def decompress_omp_region(self, stream_ptr, stream_on_device, stream_len, body_off, shape3, dtype, lo, hi, out_ptr, out_on_device):
+        """The sub-box [lo, hi) (per dimension, dim 0 slowest, hi exclusive) of an OpenMP-container stream (szhip_decompress_omp_region): only the boxes that
+        meet it are decoded.  out_ptr receives prod(hi - lo) values, contiguous.  Returns the stats (n_blocks: the boxes decoded)."""
+        st = szhip_stats()
+        c_lo, c_hi = (ctypes.c_size_t * 3)(*[int(v) for v in lo]), (ctypes.c_size_t * 3)(*[int(v) for v in hi])
+        rc = lib().szhip_decompress_omp_region(self._h, 0 if np.dtype(dtype) == np.float32 else 1, stream_ptr, int(stream_on_device), stream_len,
+                                               body_off, shape3[0], shape3[1], shape3[2], c_lo, c_hi, out_ptr, int(out_on_device), ctypes.byref(st))
+        if rc:
+            self._err(rc, "szhip_decompress_omp_region")
         return st
 
     def huff_book(self, hist, on_device=False, intervals=None, tree_cap=None):

@@ -800,20 +800,19 @@ void *detransposeData(void *data, int dataType, size_t r5, size_t r4, size_t r3,
 }
 
 static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data, size_t avail);
-static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+/* the stream behind its lossless stage (zstd or gzip; none: the stream itself): *sz, *szlen, *owned = 1 when *sz was malloc'd here.  0 with a printed reason on failure */
+static int unwrap_lossless(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t dataLength, unsigned char **sz_out, size_t *szlen_out, int *owned_out)
 {
     const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
     const size_t meta_len = dataType == SZ_FLOAT ? MetaDataByteLength : MetaDataByteLength_double;
-    size_t dataLength = computeDataLength(r5, r4, r3, r2, r1);
     unsigned char *sz = cmpBytes; size_t szlen = cmpSize; int owned = 0;
-
     /* the two sizes a constant-data stream can have (SZ_SIZE_TYPE 4 or 8) are never sniffed: szd_float.c:62, szd_double.c:32 */
     const size_t cbase = (dataType == SZ_FLOAT ? 8 : 12) + meta_len;
     if (cmpSize != cbase + 4 && cmpSize != cbase + 8) { /* szd_float.c:62-95 */
         int lossless = -1;
         if (cmpSize >= 4 && zstd_load() && g_zstd.fcs(cmpBytes, cmpSize) != (unsigned long long)-2) lossless = ZSTD_COMPRESSOR; /* != ZSTD_CONTENTSIZE_ERROR */
         else if (cmpSize >= 4 && cmpBytes[0] == 0x28 && cmpBytes[1] == 0xB5 && cmpBytes[2] == 0x2F && cmpBytes[3] == 0xFD && !zstd_load()) {
-            printf("Error: zstd-wrapped stream but libzstd.so.1 is not available.\n"); return NULL;
+            printf("Error: zstd-wrapped stream but libzstd.so.1 is not available.\n"); return 0;
         }
         if (lossless == -1 && cmpSize >= 2 && is_zlib_format(cmpBytes[0], cmpBytes[1])) lossless = GZIP_COMPRESSOR;
         confparams_dec->losslessCompressor = lossless;
@@ -824,25 +823,37 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
             if (lossless == ZSTD_COMPRESSOR) {
                 unsigned long long fcs = g_zstd.fcs(cmpBytes, cmpSize);
                 if (fcs != (unsigned long long)-1 && fcs > target) {
-                    if (fcs > (unsigned long long)dataLength * esz * 2 + (64u << 20)) { printf("Error: implausible zstd frame size.\n"); return NULL; }
+                    if (fcs > (unsigned long long)dataLength * esz * 2 + (64u << 20)) { printf("Error: implausible zstd frame size.\n"); return 0; }
                     target = (size_t)fcs;
                 }
                 unsigned char *buf = (unsigned char *)malloc(target);
-                if (!buf) { printf("Error: out of memory.\n"); return NULL; }
+                if (!buf) { printf("Error: out of memory.\n"); return 0; }
                 size_t got = zstd_decompress_stream(buf, target, cmpBytes, cmpSize);
-                if (g_zstd.iserr(got)) { printf("Error: ZSTD_decompress failed.\n"); free(buf); return NULL; }
+                if (g_zstd.iserr(got)) { printf("Error: ZSTD_decompress failed.\n"); free(buf); return 0; }
                 sz = buf; szlen = got; owned = 1;
             } else {
-                if (!zlib_load()) { printf("Error: gzip-wrapped stream but libz.so.1 is not available.\n"); return NULL; }
+                if (!zlib_load()) { printf("Error: gzip-wrapped stream but libz.so.1 is not available.\n"); return 0; }
                 unsigned char *buf = (unsigned char *)malloc(target);
-                if (!buf) { printf("Error: out of memory.\n"); return NULL; }
+                if (!buf) { printf("Error: out of memory.\n"); return 0; }
                 unsigned long got = (unsigned long)target;
                 int zr = g_zlib.uncompress(buf, &got, cmpBytes, (unsigned long)cmpSize);
-                if (zr != 0) { printf("Error: zlib uncompress failed (%d).\n", zr); free(buf); return NULL; }
+                if (zr != 0) { printf("Error: zlib uncompress failed (%d).\n", zr); free(buf); return 0; }
                 sz = buf; szlen = (size_t)got; owned = 1;
             }
         }
     }
+    *sz_out = sz; *szlen_out = szlen; *owned_out = owned;
+    return 1;
+}
+
+static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    const size_t meta_len = dataType == SZ_FLOAT ? MetaDataByteLength : MetaDataByteLength_double;
+    size_t dataLength = computeDataLength(r5, r4, r3, r2, r1);
+    unsigned char *sz = cmpBytes; size_t szlen = cmpSize; int owned = 0;
+
+    if (!unwrap_lossless(dataType, cmpBytes, cmpSize, dataLength, &sz, &szlen, &owned)) return NULL;
     if (dataLength <= MIN_NUM_OF_ELEMENTS) { /* raw copy written by SZ_skip_compress */
         void *o = malloc(dataLength * esz != 0 ? dataLength * esz : 1);
         if (!o) { printf("Error: out of memory\n"); if (owned) free(sz); return NULL; }
@@ -957,16 +968,69 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
     return out;
 }
 
-void *SZ_decompress(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+static void fresh_dec_state(void)
 {
-    size_t _r[5];
-    filterDimension(r5, r4, r3, r2, r1, _r);
     if (confparams_dec == NULL) confparams_dec = (sz_params *)malloc(sizeof(sz_params));
     memset(confparams_dec, 0, sizeof(sz_params));
     if (exe_params == NULL) exe_params = (sz_exedata *)malloc(sizeof(sz_exedata));
     memset(exe_params, 0, sizeof(sz_exedata));
     exe_params->SZ_SIZE_TYPE = 8;
     sysEndianType = LITTLE_ENDIAN_SYSTEM;
+}
+
+/* The sub-box [start, end) of a 3-D array out of an OpenMP container that SZ_compress_args wrote under SZ_HIP_MODE=omp; only the boxes that meet it are decoded
+ * (szhip_decompress_omp_region).  A stream wrapped by the zstd or gzip stage is unwrapped WHOLE first: that stage has no random access.
+ * 1: *out is the malloc'd region; 0: the stream is no such container (*what names what it is; nothing printed, nothing decoded); -1: failed, the reason printed.
+ * (Not in sz.h: sz_slab_decompress_region asks it slab by slab.) */
+int sz_hip_region_try(int dataType, unsigned char *bytes, size_t byteLength, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3],
+                      void **out, const char **what)
+{
+    fresh_dec_state();
+    const size_t d[3] = {r3, r2, r1}, esz = dataType == SZ_FLOAT ? 4 : 8, dataLength = r3 * r2 * r1;
+    *out = NULL;
+    for (int k = 0; k < 3; k++)
+        if (start[k] >= end[k] || end[k] > d[k]) { printf("Error: region [%zu, %zu) of dimension %d is empty or beyond its extent %zu.\n", start[k], end[k], k, d[k]); return -1; }
+    unsigned char *sz; size_t szlen; int owned, rc = 0;
+    if (!unwrap_lossless(dataType, bytes, byteLength, dataLength, &sz, &szlen, &owned)) return -1;
+    const size_t body = 4 + (size_t)MetaDataByteLength;                /* (both types: sz_omp.c:221, :733) */
+    if (dataLength <= MIN_NUM_OF_ELEMENTS || szlen <= body + 4) *what = "a raw copy or too short";
+    else if (!(sz[3] & 0x80) || (sz[3] & 0x31) || sz[19] != SZH_OMP_MARK)
+        *what = (sz[3] & 0x01) ? "constant data" : (sz[3] & 0x10) ? "a lossless copy" : !(sz[3] & 0x80) ? "SZ 1.4" : (sz[3] & 0x20) ? "point-wise relative" : "SZ 2.1";
+    else {
+        szhip_ctx *ctx = get_ctx();
+        void *o = ctx ? malloc((end[0] - start[0]) * (end[1] - start[1]) * (end[2] - start[2]) * esz) : NULL;
+        rc = -1;
+        if (!o) printf("Error: SZ_hip_decompress_region: %s.\n", ctx ? "out of memory" : "no device");
+        else {
+            const int hrc = szhip_decompress_omp_region(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, sz + body, 0, szlen - body, 0, r3, r2, r1, start, end, o, 0, &g_last_stats);
+            if (hrc != SZHIP_OK) { printf("Error: szhip_decompress_omp_region failed (%d): %s\n", hrc, szhip_last_error(ctx)); free(o); }
+            else { *out = o; rc = 1; }
+        }
+    }
+    if (owned) free(sz);
+    return rc;
+}
+
+void *SZ_hip_decompress_region(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
+                               const size_t start[3], const size_t end[3])
+{
+    static const char *const only = "SZ_hip_decompress_region reads the OpenMP containers that SZ_compress_args writes for 3-D float / double arrays under SZ_HIP_MODE=omp";
+    size_t _r[5];
+    filterDimension(r5, r4, r3, r2, r1, _r);
+    if (!bytes || !start || !end) { printf("Error: SZ_hip_decompress_region: null argument.\n"); return NULL; }
+    if ((dataType != SZ_FLOAT && dataType != SZ_DOUBLE) || computeDimension(_r[4], _r[3], _r[2], _r[1], _r[0]) != 3) {
+        printf("Error: %s; this is not a 3-D float / double array.\n", only); return NULL;
+    }
+    void *out = NULL; const char *what = "";
+    if (sz_hip_region_try(dataType, bytes, byteLength, _r[2], _r[1], _r[0], start, end, &out, &what) == 0) printf("Error: %s; this stream (%s) is none.\n", only, what);
+    return out;
+}
+
+void *SZ_decompress(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    size_t _r[5];
+    filterDimension(r5, r4, r3, r2, r1, _r);
+    fresh_dec_state();
     if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE) return decompress_fp(dataType, bytes, byteLength, _r[4], _r[3], _r[2], _r[1], _r[0]);
     printf("Error: the MI355X build handles SZ_FLOAT and SZ_DOUBLE; integer types are outside its scope.\n");
     return NULL;

@@ -8,6 +8,10 @@
 #include "sz.h"
 #include "sz_slab.h"
 
+/* sz_api.c: the region out of an OpenMP-container stream (1), or 0 when the stream is none (nothing decoded, nothing printed), or -1 (failed, printed) */
+int sz_hip_region_try(int dataType, unsigned char *bytes, size_t byteLength, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3],
+                      void **out, const char **what);
+
 static void put_u32(unsigned char *p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (unsigned char)(v >> (8 * i)); }
 static void put_u64(unsigned char *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (unsigned char)(v >> (8 * i)); }
 static uint32_t get_u32(const unsigned char *p) { uint32_t v = 0; for (int i = 0; i < 4; i++) v |= (uint32_t)p[i] << (8 * i); return v; }
@@ -119,9 +123,10 @@ done:
     return out;
 }
 
-void *sz_slab_decompress(const unsigned char *blob, size_t len, int *dataType, size_t dims[3])
+/* a container's table, checked: the entries (malloc'd), the type and the dimensions; NULL for a container that sz_slab_decompress refuses */
+static sz_slab_entry *checked_entries(const unsigned char *blob, size_t len, int *dt_out, size_t d[3], int *n_out)
 {
-    int dt = 0, n = 0; size_t d[3];
+    int dt = 0, n = 0;
     if (sz_slab_unpack(blob, len, &dt, d, &n, NULL, 0) != SZ_SCES) return NULL;
     sz_slab_entry *e = (sz_slab_entry *)malloc((size_t)n * sizeof(sz_slab_entry));
     if (!e || sz_slab_unpack(blob, len, &dt, d, &n, e, n) != SZ_SCES) { free(e); return NULL; }
@@ -131,9 +136,19 @@ void *sz_slab_decompress(const unsigned char *blob, size_t len, int *dataType, s
      * slab covers would come back as uninitialised memory) */
     if (d[0] == 0 || d[1] == 0 || d[2] == 0 || d[1] > SIZE_MAX / d[2] || d[0] > SIZE_MAX / (d[1] * d[2]) || d[0] * d[1] * d[2] > SIZE_MAX / esz ||
         d[0] * d[1] * d[2] >= ((size_t)1 << 46)) { free(e); return NULL; }
+    { size_t z = 0; for (int s = 0; s < n; s++) { if (e[s].z_begin != z || e[s].z_end < z || e[s].z_end > d[0]) { free(e); return NULL; } z = e[s].z_end; } if (z != d[0]) { free(e); return NULL; } }
+    *dt_out = dt; *n_out = n;
+    return e;
+}
+
+void *sz_slab_decompress(const unsigned char *blob, size_t len, int *dataType, size_t dims[3])
+{
+    int dt = 0, n = 0; size_t d[3];
+    sz_slab_entry *e = checked_entries(blob, len, &dt, d, &n);
+    if (!e) return NULL;
+    const size_t esz = dt == SZ_FLOAT ? 4 : 8;
     const size_t plane = d[1] * d[2];
     const size_t total = d[0] * plane * esz;
-    { size_t z = 0; for (int s = 0; s < n; s++) { if (e[s].z_begin != z || e[s].z_end < z || e[s].z_end > d[0]) { free(e); return NULL; } z = e[s].z_end; } if (z != d[0]) { free(e); return NULL; } }
     unsigned char *out = (unsigned char *)malloc(total);
     if (!out) { free(e); return NULL; }
     for (int s = 0; s < n; s++) {
@@ -147,5 +162,37 @@ void *sz_slab_decompress(const unsigned char *blob, size_t len, int *dataType, s
     free(e);
     if (dataType) *dataType = dt;
     if (dims) { dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2]; }
+    return out;
+}
+
+/* sz_slab_region.h: the slabs that meet [start[0], end[0]) only; OpenMP-container sub-streams through SZ_hip_decompress_region, the others whole and cropped here */
+void *sz_slab_decompress_region(const unsigned char *blob, size_t len, const size_t start[3], const size_t end[3], int *dataType)
+{
+    int dt = 0, n = 0; size_t d[3];
+    if (!start || !end) return NULL;
+    sz_slab_entry *e = checked_entries(blob, len, &dt, d, &n);
+    if (!e) return NULL;
+    for (int k = 0; k < 3; k++) if (start[k] >= end[k] || end[k] > d[k]) { free(e); return NULL; }
+    const size_t esz = dt == SZ_FLOAT ? 4 : 8, e1 = end[1] - start[1], e2 = end[2] - start[2], rplane = e1 * e2;
+    unsigned char *out = (unsigned char *)malloc((end[0] - start[0]) * rplane * esz);
+    if (!out) { free(e); return NULL; }
+    for (int s = 0; s < n; s++) {
+        const size_t z0 = e[s].z_begin > start[0] ? e[s].z_begin : start[0], z1 = e[s].z_end < end[0] ? e[s].z_end : end[0], h = e[s].z_end - e[s].z_begin;
+        if (z0 >= z1) continue;                                       /* the slab does not meet the region */
+        unsigned char *sub = (unsigned char *)blob + e[s].offset, *dst = out + (z0 - start[0]) * rplane * esz;
+        void *part = NULL; const char *what = "";
+        const size_t lo[3] = {z0 - e[s].z_begin, start[1], start[2]}, hi[3] = {z1 - e[s].z_begin, end[1], end[2]};
+        const int rc = sz_hip_region_try(dt, sub, e[s].bytes, h, d[1], d[2], lo, hi, &part, &what);
+        if (rc < 0) { free(out); free(e); return NULL; }
+        if (rc > 0) { memcpy(dst, part, (z1 - z0) * rplane * esz); free(part); continue; }
+        part = SZ_decompress(dt, sub, e[s].bytes, 0, 0, h, d[1], d[2]);            /* any other sub-stream: the whole slab, cropped here */
+        if (!part) { free(out); free(e); return NULL; }
+        for (size_t z = z0; z < z1; z++)
+            for (size_t y = 0; y < e1; y++)
+                memcpy(dst + ((z - z0) * e1 + y) * e2 * esz, (unsigned char *)part + (((z - e[s].z_begin) * d[1] + start[1] + y) * d[2] + start[2]) * esz, e2 * esz);
+        free(part);
+    }
+    free(e);
+    if (dataType) *dataType = dt;
     return out;
 }

@@ -755,3 +755,45 @@ __global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned ch
     if (oend > bel) oend = bel;
     hdec_run_lut<true>(l, total, ltab, table, lut4, wr ? start : 0u, wr ? limit : 0u, &e, out, (int64_t)o, oend, wr);
 }
+
+// =====================================================================================================================
+// A sub-box of the array (szhip_decompress_omp_region): the boxes that meet the region are decoded -- by the kernels above, launched over
+// compact tables of those boxes -- into a staging array of just those boxes, and the region is cut out of it.
+// =====================================================================================================================
+// The covered boxes' pieces of a DEVICE-resident stream into the call's compact arrays, a workgroup per span {source offset, destination
+// offset, bytes}: 16 bytes per lane where source and destination are aligned alike (the host places the payload spans so), else byte by byte.
+__global__ __launch_bounds__(256) void k_omp_gather(const unsigned char *__restrict__ src, unsigned char *__restrict__ dst, const u64 *__restrict__ spans)
+{
+    const u64 *sp = spans + 3 * (u64)blockIdx.x;
+    const unsigned char *s = src + sp[0];
+    unsigned char *d = dst + sp[1];
+    const u64 n = sp[2], tid = threadIdx.x;
+    if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0) {
+        u64 head = (16u - (unsigned)((uintptr_t)s & 15u)) & 15u;
+        if (head > n) head = n;
+        const u64 n16 = (n - head) / 16, tail = head + n16 * 16;
+        if (tid < head) d[tid] = s[tid];
+        for (u64 i = tid; i < n16; i += 256) reinterpret_cast<uint4 *>(d + head)[i] = reinterpret_cast<const uint4 *>(s + head)[i];
+        if (tail + tid < n) d[tail + tid] = s[tail + tid];            // (fewer than 16 bytes)
+    } else for (u64 i = tid; i < n; i += 256) d[i] = s[i];
+}
+
+// The region out of the staging array: row (k, i) of the region starts at src + k s0 + i s1 (src: the region's first value in the staging
+// array) and goes to dst + (k e1 + i) e2.  A lane takes one 16-byte piece of one row -- consecutive lanes consecutive pieces, `cpr` pieces a
+// row, so a wavefront reads and writes whole lines of a row -- and copies it in one access when both row starts are 16-byte aligned and the
+// piece lies inside the row; else (any address of `dst`, rows that are no multiple of the piece, the last piece of a row) value by value.
+template <class T>
+__global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int64_t s0, int64_t s1, T *__restrict__ dst, int e1, int e2, int cpr, int64_t pieces)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    const int64_t row = idx / cpr, k = row / e1;
+    const int j0 = (int)(idx - row * cpr) * VW, i = (int)(row - k * e1);
+    const T *s = src + k * s0 + (int64_t)i * s1;
+    T *d = dst + row * e2;
+    if (j0 + VW <= e2 && ((((uintptr_t)s) | ((uintptr_t)d)) & 15u) == 0)
+        *reinterpret_cast<uint4 *>(d + j0) = *reinterpret_cast<const uint4 *>(s + j0);
+    else
+        for (int j = j0; j < e2 && j < j0 + VW; ++j) d[j] = s[j];
+}

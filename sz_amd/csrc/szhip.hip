@@ -492,6 +492,22 @@ int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream,
                BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats));
 }
 
+int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
+                                size_t r0, size_t r1, size_t r2, const size_t lo[3], const size_t hi[3], void *out, int out_on_device, szhip_stats *stats)
+{
+    if (!ctx || !stream || !out || !lo || !hi || body_off >= stream_len) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    const size_t r[3] = {r0, r1, r2};
+    for (int k = 0; k < 3; ++k)
+        if (lo[k] >= hi[k] || hi[k] > r[k]) {
+            snprintf(ctx->err, sizeof(ctx->err), "region [%zu, %zu) of dimension %d is empty or beyond its extent %zu", lo[k], hi[k], k, r[k]);
+            return SZHIP_ERR_ARG;
+        }
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, decompress_omp_region_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, lo, hi, out, out_on_device, stats));
+}
+
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,
                       void **d_log, unsigned char *signs_host, int *positive, double *real_precision, double *value_range, double *median,
                       double *min_log_value)

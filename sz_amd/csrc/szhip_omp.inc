@@ -262,6 +262,7 @@ struct omp_dec : call_base {
     std::vector<u64> uoff, bbytes, boff;
     // ---- device arrays
     u64 *sm = nullptr; uint16_t *d_codes = nullptr; T *d_out = nullptr;
+    const u64 *d_uoff = nullptr; const T *d_first = nullptr, *d_unpred = nullptr;      // per box: ranks of its verbatim values, its first value; the verbatim values
 
     // ---- the stream taken in; the fixed fields, the box grid, the tree, the boxes' counts of verbatim values and payload sizes: on the host
     int read_header() {
@@ -312,10 +313,16 @@ struct omp_dec : call_base {
         HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, D.dtab.data(), D.dtab.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->samples.p, in.d_stream + off_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
         if (E > 0) HIPCHK(hipMemcpyAsync(ctx->unpred.p, in.d_stream + off_unpred, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        d_uoff = (const u64 *)ctx->col_off.p; d_first = (const T *)ctx->samples.p; d_unpred = (const T *)ctx->unpred.p;
         TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
         d_codes = (uint16_t *)ctx->codes_nat.p;
         u64 max_box = 0;
         for (int b = 0; b < g.nb; ++b) max_box = std::max(max_box, bbytes[b]);
+        return huffman_decode(g.nb, in.d_stream + off_pay, (unsigned)off_pay, (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, max_box);
+    }
+    // the Huffman decode of `nb` boxes into d_codes, box after box: their payloads at payload + box_off[b] (`bytes_before` bytes of the buffer lie in front of
+    // `payload`, 64 behind the last one), the largest of `max_box` bytes; the node table is in ctx->dec_tab
+    int huffman_decode(int nb, const unsigned char *payload, unsigned bytes_before, const u64 *box_off, const u64 *box_bytes, u64 max_box) {
         // the look-up-table decoder (hdec_run_lut) when a box's payload, the table and the node table fit a workgroup's LDS
         const unsigned stage_bytes = (unsigned)((max_box + 30 + 15) / 16 * 16 + 16);
         const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
@@ -326,15 +333,15 @@ struct omp_dec : call_base {
             TRY(ensure(ctx, ctx->dec_tab, lut_off + SZH_LUT_BYTES));          // (grown before the table went up: above)
             hipLaunchKernelGGL(k_hdec_build_lut, dim3(SZH_LUT_SIZE / 256), dim3(256), 0, st, (const unsigned *)ctx->dec_tab.p, (uint4 *)((char *)ctx->dec_tab.p + lut_off));
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)g.nb), dim3(256), lds_lut, st, g.bel, (const unsigned char *)(in.d_stream + off_pay), (unsigned)off_pay,
-                               (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds_lut,
+            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)nb), dim3(256), lds_lut, st, g.bel, payload, bytes_before,
+                               box_off, box_bytes, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds_lut,
                                (const uint4 *)((char *)ctx->dec_tab.p + lut_off), stage_bytes, d_codes, (unsigned *)(sm + SM_ERR));
         } else {
             const int tab_lds = D.dtab.size() * 4 <= 16384;            // node table and payload in LDS when they are small (the usual case: 2 - 3 bits per code)
             const unsigned pay_cap = (unsigned)std::min<u64>(max_box, 24576);
             const size_t lds = (tab_lds ? D.dtab.size() * 4 : 0) + (size_t)pay_cap + 16;
-            hipLaunchKernelGGL(k_omp_hdec, dim3((unsigned)g.nb), dim3(256), lds, st, g.bel, (const unsigned char *)(in.d_stream + off_pay), (const u64 *)ctx->reg_rank.p,
-                               (const u64 *)ctx->reg_flags.p, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds, pay_cap, D.single_symbol, d_codes, (unsigned *)(sm + SM_ERR));
+            hipLaunchKernelGGL(k_omp_hdec, dim3((unsigned)nb), dim3(256), lds, st, g.bel, payload, box_off,
+                               box_bytes, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds, pay_cap, D.single_symbol, d_codes, (unsigned *)(sm + SM_ERR));
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[1], st));
@@ -343,10 +350,15 @@ struct omp_dec : call_base {
     // ---- reconstruct: the inverse of the compress call's sweep
     int reconstruct() {
         TRY(device_out(ctx, out, out_on_device, (size_t)n, &d_out));
+        return sweep();
+    }
+    // the boxes of `g` from d_codes, d_first, d_unpred / d_uoff into d_out, whose pitches `g` has
+    int sweep() {
         if ((uintptr_t)d_out & 15u) g.vec = 0;
+        const size_t row_bytes = (size_t)g.d1 * sizeof(T);
         const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (omp_col_applies(g, d_out, r2 * sizeof(T))) {
+        if (omp_col_applies(g, d_out, row_bytes)) {
             // the verbatim values go to their places in the output first (boxes that have any); the sweep picks them up where a code is zero
             int fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32;        // flag words per box: a bit per group of rows one load of the sweep covers
             unsigned *d_vflags = nullptr;
@@ -357,20 +369,20 @@ struct omp_dec : call_base {
                     d_vflags = (unsigned *)ctx->chunk_bits.p;
                     HIPCHK(hipMemsetAsync(d_vflags, 0, (size_t)g.nb * fw * 4, st));
                 }
-                hipLaunchKernelGGL((k_omp_scatter<T>), dim3((unsigned)g.nb), dim3(256), 0, st, g, (const uint16_t *)d_codes, (const u64 *)ctx->col_off.p, (const T *)ctx->unpred.p, d_out,
+                hipLaunchKernelGGL((k_omp_scatter<T>), dim3((unsigned)g.nb), dim3(256), 0, st, g, (const uint16_t *)d_codes, d_uoff, d_unpred, d_out,
                                    (unsigned *)(sm + SM_ERR), d_vflags, fw);
                 HIPCHK(hipGetLastError());
             }
             szh_oc::sweep_args<T> oa;
             oa.vflags = d_vflags; oa.fw = fw;
             oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
-            oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = (T *)ctx->samples.p; oa.uoff = (const u64 *)ctx->col_off.p;
+            oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = const_cast<T *>(d_first); oa.uoff = d_uoff;
             hipLaunchKernelGGL((k_omp_col<T, 32, 32, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
         } else hipLaunchKernelGGL((g.vec ? k_omp_box<T, true, true> : k_omp_box<T, true, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, (const T *)nullptr,
-                                  d_out, eb, (T)(1 / eb), (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, (T *)ctx->samples.p, (const T *)ctx->unpred.p, (const u64 *)ctx->col_off.p);
+                                  d_out, eb, (T)(1 / eb), (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, const_cast<T *>(d_first), d_unpred, d_uoff);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel = omp_col_applies(g, d_out, r2 * sizeof(T)) ? 3 : (g.vec ? 4 : 5);
+        S.quant_kernel = omp_col_applies(g, d_out, row_bytes) ? 3 : (g.vec ? 4 : 5);
         return SZHIP_OK;
     }
     // ---- the array to the caller, the kernels' error count, the statistics
@@ -394,5 +406,144 @@ int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stre
     TRY(d.decode_boxes());
     TRY(d.reconstruct());
     TRY(d.finish());
+    return d.done(stats);
+}
+
+// One call for a sub-box [lo, hi) of the array (szhip_decompress_omp_region).  The boxes that meet the region are a rectangular sub-grid of the box grid; the
+// call decodes them alone, with the kernels of the full decode launched over COMPACT tables (sub-grid order: box (i0, i1, i2) of the sub-grid is number
+// (i0 n1 + i1) n2 + i2, as szh_omp_box_origin_bytes counts the boxes of a geometry) and a sub-geometry `gs` whose box counts are the sub-grid's and whose pitches
+// are those of an array of just these boxes.  That array is `out` itself when the region ends on box boundaries (the direct form), else a staging array in the
+// context out of which k_omp_crop cuts the region.  The host's walk over the stream's tables (read_header) is the only step that grows with all boxes.
+template <class T>
+struct omp_region {
+    omp_dec<T> &d; const size_t *const lo, *const hi;
+    szhip_ctx *const ctx = d.ctx; const hipStream_t st = d.st;
+    int b0[3], cn[3]; int nbc = 0; size_t ext[3], n_out = 0; bool direct = false;
+    // the call's device blob: [payload sizes][payload offsets][ranks + 1][spans] | [first values][verbatim values][64 bytes, the payloads, 64 zero bytes]
+    size_t o_bytes = 0, o_off = 0, o_uoff = 0, o_spans = 0, o_first = 0, o_unp = 0, o_pay = 0, blob_len = 0, n_spans = 0;
+    u64 Ec = 0, max_box = 0;
+    unsigned char *d_blob = nullptr; T *d_stage = nullptr, *d_crop = nullptr;
+
+    // ---- the covered sub-grid; the compact tables and, of a host stream, the covered boxes' values and payloads: one blob, one upload.  Of a device
+    // stream the spans go up instead and k_omp_gather fetches them.  (For a fixed (dim 0, dim 1) box coordinate the covered boxes are consecutive: a run.)
+    int tables() {
+        const szh_omp_geom &g = d.g;
+        const int c[3] = {g.c0, g.c1, g.c2};
+        direct = true;
+        for (int k = 0; k < 3; ++k) {
+            b0[k] = (int)(lo[k] / c[k]); cn[k] = (int)((hi[k] - 1) / c[k]) + 1 - b0[k]; ext[k] = hi[k] - lo[k];
+            if (lo[k] % c[k] || hi[k] % c[k]) direct = false;
+        }
+        nbc = cn[0] * cn[1] * cn[2]; n_out = ext[0] * ext[1] * ext[2];
+        const size_t runs = (size_t)cn[0] * cn[1];
+        std::vector<u64> cbytes((size_t)nbc), coff((size_t)nbc), cu((size_t)nbc + 1, 0), spans;
+        struct piece { size_t src, dst, len; };
+        std::vector<piece> pieces; pieces.reserve(runs * 3);
+        u64 pos = 0;
+        const bool dev = d.in.on_device != 0;
+        for (size_t r = 0; r < runs; ++r) {
+            const int bi = b0[0] + (int)(r / cn[1]), bj = b0[1] + (int)(r % cn[1]);
+            const size_t bf = ((size_t)bi * g.ny + bj) * g.nz + b0[2], i0 = r * cn[2];
+            for (int q = 0; q < cn[2]; ++q) {
+                cbytes[i0 + q] = d.bbytes[bf + q]; max_box = std::max(max_box, d.bbytes[bf + q]);
+                cu[i0 + q + 1] = cu[i0 + q] + (d.uoff[bf + q + 1] - d.uoff[bf + q]);
+            }
+            // the run's payloads lie one behind the other in the stream; in the blob they start at the source's place modulo 16 (k_omp_gather)
+            const size_t src = d.off_pay + (size_t)d.boff[bf], len = (size_t)(d.boff[bf + cn[2] - 1] + d.bbytes[bf + cn[2] - 1] - d.boff[bf]);
+            if (dev) pos += (((uintptr_t)(d.in.stream_in + src) & 15u) - (pos & 15u)) & 15u;
+            for (int q = 0; q < cn[2]; ++q) coff[i0 + q] = pos + (d.boff[bf + q] - d.boff[bf]);
+            pieces.push_back({d.off_first + bf * sizeof(T), i0 * sizeof(T), (size_t)cn[2] * sizeof(T)});
+            pieces.push_back({d.off_unpred + (size_t)d.uoff[bf] * sizeof(T), (size_t)cu[i0] * sizeof(T), (size_t)(cu[i0 + cn[2]] - cu[i0]) * sizeof(T)});
+            pieces.push_back({src, (size_t)pos, len});
+            pos += len;
+        }
+        Ec = cu[(size_t)nbc];
+        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+        o_bytes = 0; o_off = up16(o_bytes + (size_t)nbc * 8); o_uoff = up16(o_off + (size_t)nbc * 8); o_spans = up16(o_uoff + ((size_t)nbc + 1) * 8);
+        n_spans = dev ? pieces.size() : 0;
+        o_first = up16(o_spans + n_spans * 24); o_unp = up16(o_first + (size_t)nbc * sizeof(T)); o_pay = up16(o_unp + (size_t)Ec * sizeof(T)) + 64;
+        blob_len = o_pay + (size_t)pos + 64;
+        for (size_t p = 0; p < pieces.size(); ++p) pieces[p].dst += p % 3 == 0 ? o_first : p % 3 == 1 ? o_unp : o_pay;
+        TRY(ensure(ctx, ctx->seg_hist, blob_len));
+        d_blob = (unsigned char *)ctx->seg_hist.p;
+        const size_t up_len = dev ? o_first : blob_len;
+        TRY(ensure_pinned3(ctx, up_len));
+        unsigned char *hb = (unsigned char *)ctx->pinned3;
+        memcpy(hb + o_bytes, cbytes.data(), (size_t)nbc * 8); memcpy(hb + o_off, coff.data(), (size_t)nbc * 8); memcpy(hb + o_uoff, cu.data(), ((size_t)nbc + 1) * 8);
+        if (dev) {
+            u64 *sp = (u64 *)(hb + o_spans);
+            for (size_t p = 0; p < pieces.size(); ++p) { sp[3 * p] = pieces[p].src; sp[3 * p + 1] = pieces[p].dst; sp[3 * p + 2] = pieces[p].len; }
+            HIPCHK(hipMemcpyAsync(d_blob, hb, up_len, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(d_blob + blob_len - 64, 0, 64, st));
+            hipLaunchKernelGGL(k_omp_gather, dim3((unsigned)n_spans), dim3(256), 0, st, d.in.stream_in, d_blob, (const u64 *)(d_blob + o_spans));
+            HIPCHK(hipGetLastError());
+        } else {
+            for (const piece &pc : pieces) memcpy(hb + pc.dst, d.in.stream_in + pc.src, pc.len);
+            memset(hb + blob_len - 64, 0, 64);
+            HIPCHK(hipMemcpyAsync(d_blob, hb, up_len, hipMemcpyHostToDevice, st));
+        }
+        d.S.n_blocks = (uint64_t)nbc; d.S.n_elements = (uint64_t)n_out; d.S.n_unpred = Ec;
+        return SZHIP_OK;
+    }
+    // ---- the covered boxes' codes (compact, box after box), then the sweeps over the sub-geometry, then the crop
+    int decode() {
+        const szh_omp_geom g = d.g;
+        TRY(clear_small(ctx, &d.sm));
+        TRY(ensure(ctx, ctx->dec_tab, (d.D.dtab.size() * 4 + 63) / 64 * 64 + SZH_LUT_BYTES + 16));
+        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, d.D.dtab.data(), d.D.dtab.size() * 4, hipMemcpyHostToDevice, st));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)nbc * g.bel * 2 + 64));
+        d.d_codes = (uint16_t *)ctx->codes_nat.p;
+        d.d_uoff = (const u64 *)(d_blob + o_uoff); d.d_first = (const T *)(d_blob + o_first); d.d_unpred = (const T *)(d_blob + o_unp);
+        TRY(d.huffman_decode(nbc, d_blob + o_pay, (unsigned)o_pay, (const u64 *)(d_blob + o_off), (const u64 *)(d_blob + o_bytes), max_box));
+        // the sub-geometry: the sub-grid's box counts, the pitches of an array of exactly these boxes
+        szh_omp_geom gs = g;
+        gs.nx = cn[0]; gs.ny = cn[1]; gs.nz = cn[2]; gs.nb = nbc;
+        gs.d1 = (int64_t)cn[2] * g.c2; gs.d0 = (int64_t)cn[1] * g.c1 * gs.d1;
+        gs.vec = g.c2 % 4 == 0 ? 1 : 0;
+        const size_t n_stage = (size_t)nbc * g.bel;
+        if (direct) TRY(device_out(ctx, d.out, d.out_on_device, n_out, &d_crop));        // (n_stage == n_out)
+        else {
+            TRY(ensure(ctx, ctx->out, n_stage * sizeof(T)));
+            d_stage = (T *)ctx->out.p;
+            d_crop = (T *)d.out;
+            if (!d.out_on_device) { TRY(ensure(ctx, ctx->codes_blk, n_out * sizeof(T))); d_crop = (T *)ctx->codes_blk.p; }
+        }
+        d.g = gs; d.E = Ec; d.d_out = direct ? d_crop : d_stage;
+        TRY(d.sweep());
+        if (!direct) {
+            const int cpr = (int)((ext[2] + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+            const int64_t total = (int64_t)(ext[0] * ext[1]) * cpr;
+            const T *src = d_stage + (int64_t)(lo[0] - (size_t)b0[0] * g.c0) * gs.d0 + (int64_t)(lo[1] - (size_t)b0[1] * g.c1) * gs.d1 + (int64_t)(lo[2] - (size_t)b0[2] * g.c2);
+            hipLaunchKernelGGL((k_omp_crop<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, gs.d0, gs.d1, d_crop, (int)ext[1], (int)ext[2], cpr, total);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ev[3], st));
+        }
+        return SZHIP_OK;
+    }
+    // ---- the region to the caller, the kernels' error count (covered boxes only), the statistics
+    int finish() {
+        unsigned bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, d.sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
+        TRY(return_out(ctx, d.out, d.out_on_device, d_crop, n_out));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes of the region whose payload or verbatim-value count does not fit their codes", bad);
+        decompress_times(ctx, d.S, d.host_ms, d.t_begin, n_out * sizeof(T));
+        return SZHIP_OK;
+    }
+};
+
+template <class T>
+int decompress_omp_region_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_on_device, size_t stream_len, size_t body_off, size_t r0, size_t r1, size_t r2,
+                               const size_t *lo, const size_t *hi, void *out, int out_on_device, szhip_stats *stats)
+{
+    omp_dec<T> d{call_base(ctx), stream_len, body_off, r0, r1, r2, out, out_on_device, {ctx, stream_in, stream_on_device, stream_len}};
+    d.in.whole = false;
+    const double h0 = now_ms();                                // (szhip_stats.ms_host: the header and tables read, the walk over them, the compact tables built)
+    TRY(d.read_header());
+    omp_region<T> r{d, lo, hi};
+    TRY(r.tables());
+    d.host_ms += now_ms() - h0;
+    TRY(r.decode());
+    TRY(r.finish());
     return d.done(stats);
 }

@@ -165,8 +165,10 @@ struct stream_intake {
     const unsigned char *hs;                                   // the stream on the host (valid up to the last fetch)
     std::vector<unsigned char> hbuf;
     stream_intake(szhip_ctx *c, const unsigned char *s, int od, size_t len) : ctx(c), stream_in(s), on_device(od), stream_len(len), hs(s) {}
+    bool whole = true;                                         // false (a region call): the stream stays where it is, d_stream is the caller's device pointer or null
     int open() {
         hipStream_t st = ctx->stream;
+        if (!whole) { d_stream = on_device ? const_cast<unsigned char *>(stream_in) : nullptr; HIPCHK(hipEventRecord(ctx->ev[0], st)); return SZHIP_OK; }
         TRY(ensure(ctx, ctx->stream_buf, stream_len + 64));
         d_stream = (unsigned char *)ctx->stream_buf.p;
         if (on_device) { if (stream_in != d_stream) HIPCHK(hipMemcpyAsync(d_stream, stream_in, stream_len, hipMemcpyDeviceToDevice, st)); }
