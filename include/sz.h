@@ -233,6 +233,16 @@ void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, 
  * `*_openmp` entry points goes to szhip_decompress_omp_region (szhip.h) with its body offset. */
 void *SZ_hip_decompress_region(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
                                const size_t start[3], const size_t end[3]);
+/* The opposite direction: a sub-box of a larger 3-D HOST array compressed from, and decoded into, where it lies.  r5 .. r1 are the extents of the PARENT
+ * (r5 = r4 = 0); start / end as above.  SZ_hip_compress_region returns exactly what SZ_compress_args returns for a contiguous copy of the sub-box under the same
+ * configuration -- every error-bound mode (the range is the sub-box's), SZ 2.1, SZ 1.4 and SZ_HIP_MODE=omp, the lossless stage, the constant and raw-store rules --
+ * without the caller making that copy: only the sub-box's rows go to the device (szhip_pack_view, szhip.h).  SZ_hip_decompress_into_region decodes a stream of the
+ * sub-box's extents (anything SZ_decompress reads) into the parent and writes nothing outside the sub-box; SZ_SCES, or SZ_NSCS with nothing written.  Anything but a
+ * 3-D parent, or an empty or out-of-range box, gives NULL / SZ_NSCS with a printed reason.  (The reference's SZ_compress_args3 is not provided: INTEGRATION.md.) */
+unsigned char *SZ_hip_compress_region(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound, double relBoundRatio, double pwrBoundRatio,
+                                      size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3]);
+int SZ_hip_decompress_into_region(int dataType, unsigned char *bytes, size_t byteLength, void *parent, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
+                                  const size_t start[3], const size_t end[3]);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

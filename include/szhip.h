@@ -199,6 +199,41 @@ int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *
                                 void *out, int out_on_device, szhip_stats *stats);
 
 /*
+ * VIEWS: a sub-box of a larger array, compressed from and decoded into where it lies.  A view is r0 x r1 x r2 values (dim 0 slowest), given by a pointer to its
+ * first value and two ELEMENT pitches: pitch0 between successive dim-0 planes, pitch1 between successive dim-1 rows; pitch1 >= r2 and pitch0 >= r1 * pitch1 (pitch0
+ * need not be a multiple of pitch1), anything else is SZHIP_ERR_ARG before anything is launched or written.  pitch1 == r2 and pitch0 == r1 * r2 is the contiguous
+ * array.  The bar: a stream made from a view is byte for byte the stream the same call makes from a contiguous copy of the sub-box; decoding into a view writes bit for
+ * bit what the contiguous decode writes, into the sub-box and nowhere else -- not between rows, not between planes, not in front or behind; an input view is never
+ * written.  Alignment: the base pointer to its element, as everywhere; the restrictions and error codes of the contiguous calls apply to the sub-box's extents.
+ *
+ * szhip_compress_omp_view / szhip_decompress_omp_view: the OpenMP container, DIRECTLY on a device view -- no packing pass, no staging array: the sweeps, the encoders'
+ * reads of verbatim values and the inverse sweeps address the parent array through the pitches, and the interval optimiser (params->quantization_intervals == 0)
+ * samples the points it samples on the contiguous copy (the lattice is the sub-box's, only the addresses take the pitches: k_sample_view).  The 16-byte forms
+ * (stats.quant_kernel 3 and 4) need the base address, pitch1 and pitch0 to be multiples of 16 bytes.  A view that misses them while its boxes have 32 x 32 faces (the
+ * column form's shape; e.g. float32 with 1 - 3 ghost values) is packed into (decoded in) the context's contiguous buffer by the call itself and runs the column form
+ * there -- value by value it took 4.3 x / 2.7 x as long --; stats.quant_kernel reports 3.  Any other view that misses them takes the value-by-value form (5) where it
+ * lies.  The stream is the same in every case.  A view on the HOST (data_on_device = 0 / out_on_device = 0): only the sub-box's rows cross the bus, into or out of the context's contiguous buffer
+ * (the host's copy into the pinned staging buffers walks the rows); then the contiguous call runs, and of a damaged stream nothing reaches the caller's array.
+ *
+ * szhip_pack_view / szhip_scatter_view serve every other stream type at the cost of ONE pass over the sub-box: the strided reads are NOT inside k_beam, k_pencil,
+ * k_fit_select or the SZ 1.4 sweeps (their geometry also places the codes).  szhip_pack_view gathers the view (device or host) into the context's input buffer, as
+ * szhip_stage_input does with a contiguous host array: *d_packed then serves as `data` with data_on_device = 1 for szhip_minmax, szhip_compress,
+ * szhip_compress_sz14 and the PW_REL prepare calls (valid until the next call that stages an input).  szhip_scatter_view puts a decoded contiguous DEVICE array
+ * (r0 x r1 x r2 values at d_packed) into a view on the device (k_view_scatter: rows move 16 bytes per lane between the 16-byte boundaries of the destination, a
+ * value-by-value head and tail per row, no read of the view) or on the host.  Both take 2-D views as r0 == 0 (pitch0 is ignored).
+ * Costs (MI355X, 512^3 float32, device-resident): the direct calls on an aligned view 1.04 x / 1.03 x the contiguous calls and 0.85 x / 0.83 x pack + compress /
+ * decompress + scatter; packing 0.15 ms, scattering 0.24 ms; SZ 2.1 from a view 1.11 x the contiguous call.
+ * Not covered: a strided szhip_minmax, region decode into a view, the slab container.
+ */
+int szhip_compress_omp_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
+                            double eb, int thread_num, const szhip_params *params, const unsigned char *meta, size_t meta_len,
+                            int out_on_device, unsigned char **out, size_t *out_size, szhip_stats *stats);
+int szhip_decompress_omp_view(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len,
+                              size_t body_off, size_t r0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats);
+int szhip_pack_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, void **d_packed);
+int szhip_scatter_view(szhip_ctx *ctx, int dtype, const void *d_packed, size_t r0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1);
+
+/*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of
  * sz/src/sz_float_pwr.c:1791-1975 / sz_double_pwr.c:1781-1965 (dispatch sz_float.c:2888-2996) and their inverses
  * szd_float_pwr.c:1353-1422.  Three steps, the sign bytes being compressed on the host (zstd) in between:
@@ -271,7 +306,7 @@ int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsign
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)
  *        4 code histogram (u32) 5 per-column zero counts (u32) 6 per-column unpredictable offsets (u64)
- *        7 unpredictable values (T) 8 stream buffer */
+ *        7 unpredictable values (T) 8 stream buffer 12 the input buffer (szhip_stage_input, szhip_pack_view) */
 int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes);
 
 #ifdef __cplusplus

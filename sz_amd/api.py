@@ -148,6 +148,24 @@ def _bind(L):
         L.szhip_decompress_omp_region.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
                                                   ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_stats)]
         L.szhip_decompress_omp_region.restype = ctypes.c_int
+    if hasattr(L, "szhip_compress_omp_view"):
+        L.szhip_compress_omp_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz, ctypes.c_double, ctypes.c_int,
+                                              ctypes.POINTER(szhip_params), ctypes.c_char_p, sz, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(szhip_stats)]
+        L.szhip_compress_omp_view.restype = ctypes.c_int
+        L.szhip_decompress_omp_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
+                                                ctypes.c_void_p, ctypes.c_int, sz, sz, ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_view.restype = ctypes.c_int
+        L.szhip_pack_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz, ctypes.POINTER(ctypes.c_void_p)]
+        L.szhip_pack_view.restype = ctypes.c_int
+        L.szhip_scatter_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, sz, sz, ctypes.c_void_p, ctypes.c_int, sz, sz]
+        L.szhip_scatter_view.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_compress_region"):
+        L.SZ_hip_compress_region.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [sz] * 5 + \
+                                            [ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.SZ_hip_compress_region.restype = ctypes.c_void_p
+        L.SZ_hip_decompress_into_region.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_void_p] + [sz] * 5 + [ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.SZ_hip_decompress_into_region.restype = ctypes.c_int
     if hasattr(L, "szhip_huff_book"):
         L.szhip_huff_book.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.POINTER(szhip_book_record)]
@@ -260,6 +278,34 @@ def SZ_hip_decompress_region(stream, shape, dtype, lo, hi):
     if not p:
         raise SZError("SZ_hip_decompress_region returned NULL")
     return _take(p, tuple(int(h) - int(l) for l, h in zip(lo, hi)), dt)
+
+
+def _parent3(parent):
+    if not (isinstance(parent, np.ndarray) and parent.flags["C_CONTIGUOUS"]):
+        raise SZError("the parent must be a C-contiguous numpy array (it is read / written where it lies)")
+    return _dtype_code(parent)
+
+
+def SZ_hip_compress_region(parent, lo, hi, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
+    """The sub-box [lo, hi) of a 3-D host array compressed where it lies (include/sz.h): the bytes SZ_compress_args returns for np.ascontiguousarray(parent[lo:hi])."""
+    dt = _parent3(parent)
+    n = ctypes.c_size_t(0)
+    c_lo, c_hi = _box(lo, hi)
+    p = lib().SZ_hip_compress_region(dt, parent.ctypes.data, ctypes.byref(n), errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, *_dims5(parent.shape), c_lo, c_hi)
+    if not p:
+        raise SZError("SZ_hip_compress_region returned NULL")
+    out = ctypes.string_at(p, n.value)
+    lib().free(p)
+    return out
+
+
+def SZ_hip_decompress_into_region(stream, parent, lo, hi):
+    """A stream of the extents hi - lo decoded into the sub-box [lo, hi) of a 3-D host array (include/sz.h); nothing else of the parent is written."""
+    dt = _parent3(parent)
+    buf = ctypes.create_string_buffer(bytes(stream), len(stream))
+    c_lo, c_hi = _box(lo, hi)
+    if lib().SZ_hip_decompress_into_region(dt, buf, len(stream), parent.ctypes.data, *_dims5(parent.shape), c_lo, c_hi) != SZ_SCES:
+        raise SZError("SZ_hip_decompress_into_region failed")
 
 
 def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
@@ -504,6 +550,49 @@ class HipContext:
         if rc:
             self._err(rc, "szhip_decompress_omp_region")
         return st
+
+    def compress_omp_view(self, ptr, on_device, shape3, pitches, dtype, eb, thread_num, meta, params=None, out_on_device=False):
+        """szhip_compress_omp_view: the OpenMP container of the sub-box of shape3 values at ptr inside a larger array, pitches = (pitch0, pitch1) in elements (planes,
+        rows).  Byte for byte the stream compress_omp makes of a contiguous copy.  Returns (bytes | device pointer int, size, stats)."""
+        p = params or szhip_params(100, 0.99, 65536, 0)
+        out = ctypes.c_void_p()
+        n = ctypes.c_size_t(0)
+        st = szhip_stats()
+        rc = lib().szhip_compress_omp_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ptr, int(on_device), shape3[0], shape3[1], shape3[2],
+                                           int(pitches[0]), int(pitches[1]), eb, thread_num, ctypes.byref(p), meta, len(meta), int(out_on_device),
+                                           ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        if rc:
+            self._err(rc, "szhip_compress_omp_view")
+        if out_on_device:
+            return out.value, n.value, st
+        b = ctypes.string_at(out.value, n.value)
+        lib().free(out)
+        return b, n.value, st
+
+    def decompress_omp_view(self, stream_ptr, stream_on_device, stream_len, body_off, shape3, dtype, out_ptr, out_on_device, pitches):
+        """szhip_decompress_omp_view: a stream of shape3 values decoded into the sub-box at out_ptr of a larger array (pitches as above); nothing else of it is written."""
+        st = szhip_stats()
+        rc = lib().szhip_decompress_omp_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, stream_ptr, int(stream_on_device), stream_len,
+                                             body_off, shape3[0], shape3[1], shape3[2], out_ptr, int(out_on_device), int(pitches[0]), int(pitches[1]), ctypes.byref(st))
+        if rc:
+            self._err(rc, "szhip_decompress_omp_view")
+        return st
+
+    def pack_view(self, ptr, on_device, shape3, pitches, dtype):
+        """szhip_pack_view: the view gathered into the context's input buffer; returns its device pointer (shape3[0] == 0: a 2-D view, pitches[0] ignored)."""
+        out = ctypes.c_void_p()
+        rc = lib().szhip_pack_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ptr, int(on_device), shape3[0], shape3[1], shape3[2],
+                                   int(pitches[0]), int(pitches[1]), ctypes.byref(out))
+        if rc:
+            self._err(rc, "szhip_pack_view")
+        return out.value
+
+    def scatter_view(self, packed_ptr, shape3, dtype, out_ptr, out_on_device, pitches):
+        """szhip_scatter_view: the contiguous device array at packed_ptr into the view at out_ptr."""
+        rc = lib().szhip_scatter_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, packed_ptr, shape3[0], shape3[1], shape3[2], out_ptr, int(out_on_device),
+                                      int(pitches[0]), int(pitches[1]))
+        if rc:
+            self._err(rc, "szhip_scatter_view")
 
     def huff_book(self, hist, on_device=False, intervals=None, tree_cap=None):
         """The device's code book of a histogram (szhip_huff_book; k_huff_book alone).  hist: a numpy uint32 array, or a device pointer with `intervals`.

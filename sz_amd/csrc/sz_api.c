@@ -413,6 +413,16 @@ static int finish_lossless(unsigned char *tmp, size_t tmpSize, unsigned char **n
 }
 
 /* ---- compression ---- */
+/* SZ_hip_compress_region: compress_fp reads a sub-box of a larger host array.  t_view = {rows per plane, values per row, pitch0, pitch1} of the sub-box whose first value
+ * `oriData` points at (NULL: a contiguous array): the array goes to the device through szhip_pack_view, and the few places that read it on the host (the raw copies)
+ * take the i-th value of the sub-box from ori_at(i) */
+static __thread const size_t *t_view = NULL;
+static inline size_t ori_at(size_t i)
+{
+    if (!t_view) return i;
+    const size_t plane = t_view[0] * t_view[1], k = i / plane, rem = i - k * plane, r = rem / t_view[1];
+    return k * t_view[2] + r * t_view[3] + (rem - r * t_view[1]);
+}
 static unsigned char *omp_compress_at(int dataType, const void *data, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size);
 static int omp_pick_threads(size_t r1, size_t r2, size_t r3);
 #define SZH_OMP_MARK 0x4f         /* stream byte 19 (parameter byte 15, which convertSZParamsToBytes never writes: ByteToolkit.c:874-972) of an OpenMP container that
@@ -431,12 +441,17 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     if (dataLength <= MIN_NUM_OF_ELEMENTS) { /* SZ_skip_compress_float, sz_float.c:37 */
         *outSize = dataLength * esz;
         *newByteData = (unsigned char *)malloc(dataLength * esz != 0 ? dataLength * esz : 1);
-        memcpy(*newByteData, oriData, dataLength * esz);
+        if (!t_view) memcpy(*newByteData, oriData, dataLength * esz);
+        else for (size_t i = 0; i < dataLength; i++) memcpy(*newByteData + i * esz, (const char *)oriData + ori_at(i) * esz, esz);
         return SZ_SCES;
     }
     szhip_ctx *ctx = get_ctx();
     if (!ctx) return SZ_NSCS;
     void *d_in = NULL;
+    if (t_view) {                                                  /* only the sub-box's rows go to the device */
+        int prc = szhip_pack_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, 0, dataLength / (t_view[0] * t_view[1]), t_view[0], t_view[1], t_view[2], t_view[3], &d_in);   /* (the sub-box's own extents: r3 .. r1 may be folded) */
+        if (prc != SZHIP_OK) { printf("Error: szhip_pack_view failed (%d): %s\n", prc, szhip_last_error(ctx)); return SZ_NSCS; }
+    } else
     if (szhip_stage_input(ctx, oriData, dataLength * esz, &d_in) != SZHIP_OK) return SZ_NSCS;
     /* The value range (computeRangeSize_float, sz_float.c:2845).  With an absolute bound on the SZ 2.1 path nothing before the
      * quantiser depends on it -- it only goes into the header and decides the constant-data case -- so it is taken from the library's
@@ -559,8 +574,8 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
             const float zf = msst19 ? (float)msst_near_zero * (float)pow(1 + pwRelBoundRatio, -3.0001) : 0.0f;
             const double zd = msst19 ? msst_near_zero * pow(1 + pwRelBoundRatio, -3.0001) : 0.0;
             for (size_t i = 0; i < dataLength; i++, q += esz) {
-                if (dataType == SZ_FLOAT) { const float v = ((float *)oriData)[i]; szhost_put_f32be(q, v == 0 ? zf : v); }
-                else { const double v = ((double *)oriData)[i]; szhost_put_f64be(q, v == 0 ? zd : v); }
+                if (dataType == SZ_FLOAT) { const float v = ((float *)oriData)[ori_at(i)]; szhost_put_f32be(q, v == 0 ? zf : v); }
+                else { const double v = ((double *)oriData)[ori_at(i)]; szhost_put_f64be(q, v == 0 ? zd : v); }
             }
             free(ptmp); ptmp = o; ptmpSize = tot;
         }
@@ -645,7 +660,7 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
         szhost_put_u64be(o + 4 + meta_len, dataLength);
         unsigned char *q = o + 4 + meta_len + 8;
         for (size_t i = 0; i < dataLength; i++, q += esz) {
-            if (dataType == SZ_FLOAT) szhost_put_f32be(q, ((float *)oriData)[i]); else szhost_put_f64be(q, ((double *)oriData)[i]);
+            if (dataType == SZ_FLOAT) szhost_put_f32be(q, ((float *)oriData)[ori_at(i)]); else szhost_put_f64be(q, ((double *)oriData)[ori_at(i)]);
         }
         free(tmp); tmp = o; tmpSize = tot;
     }
@@ -1024,6 +1039,48 @@ void *SZ_hip_decompress_region(int dataType, unsigned char *bytes, size_t byteLe
     void *out = NULL; const char *what = "";
     if (sz_hip_region_try(dataType, bytes, byteLength, _r[2], _r[1], _r[0], start, end, &out, &what) == 0) printf("Error: %s; this stream (%s) is none.\n", only, what);
     return out;
+}
+
+/* the sub-box [start, end) of a 3-D parent r3 x r2 x r1: 1 when the call is one the region entries take, else 0 with the reason printed */
+static int region_of_parent(const char *who, int dataType, const void *p, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3])
+{
+    if (!p || !start || !end) { printf("Error: %s: null argument.\n", who); return 0; }
+    if ((dataType != SZ_FLOAT && dataType != SZ_DOUBLE) || r5 != 0 || r4 != 0 || r3 == 0 || r2 == 0 || r1 == 0) {
+        printf("Error: %s takes a sub-box of a 3-D float / double array; this parent is none.\n", who); return 0;
+    }
+    const size_t d[3] = {r3, r2, r1};
+    for (int k = 0; k < 3; k++)
+        if (start[k] >= end[k] || end[k] > d[k]) { printf("Error: %s: region [%zu, %zu) of dimension %d is empty or beyond its extent %zu.\n", who, start[k], end[k], k, d[k]); return 0; }
+    return 1;
+}
+
+unsigned char *SZ_hip_compress_region(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound, double relBoundRatio, double pwrBoundRatio,
+                                      size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3])
+{
+    if (!outSize || !region_of_parent("SZ_hip_compress_region", dataType, data, r5, r4, r3, r2, r1, start, end)) return NULL;
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8, e[3] = {end[0] - start[0], end[1] - start[1], end[2] - start[2]};
+    /* SZ_compress_args on the sub-box's extents (its dimension filter included: an extent of 1 folds as it does for the contiguous copy) */
+    const size_t view[4] = {e[1], e[2], r2 * r1, r1};
+    t_view = view;
+    unsigned char *out = SZ_compress_args(dataType, (char *)data + ((start[0] * r2 + start[1]) * r1 + start[2]) * esz, outSize, errBoundMode, absErrBound, relBoundRatio,
+                                          pwrBoundRatio, 0, 0, e[0], e[1], e[2]);
+    t_view = NULL;
+    return out;
+}
+
+int SZ_hip_decompress_into_region(int dataType, unsigned char *bytes, size_t byteLength, void *parent, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
+                                  const size_t start[3], const size_t end[3])
+{
+    if (!bytes || !region_of_parent("SZ_hip_decompress_into_region", dataType, parent, r5, r4, r3, r2, r1, start, end)) return SZ_NSCS;
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8, e[3] = {end[0] - start[0], end[1] - start[1], end[2] - start[2]};
+    /* the whole stream is decoded and checked first: nothing of a stream that fails reaches the parent */
+    void *sub = SZ_decompress(dataType, bytes, byteLength, 0, 0, e[0], e[1], e[2]);
+    if (!sub) return SZ_NSCS;
+    char *base = (char *)parent + ((start[0] * r2 + start[1]) * r1 + start[2]) * esz;
+    for (size_t k = 0; k < e[0]; k++)
+        for (size_t i = 0; i < e[1]; i++) memcpy(base + (k * r2 * r1 + i * r1) * esz, (char *)sub + (k * e[1] + i) * e[2] * esz, e[2] * esz);
+    free(sub);
+    return SZ_SCES;
 }
 
 void *SZ_decompress(int dataType, unsigned char *bytes, size_t byteLength, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)

@@ -201,6 +201,26 @@ SZH_HD void szh_sample_point(const T *data, int64_t pos, int64_t r2, int64_t r12
     *freq_index = szh_freq_index<T>(*d, mean, ebD);
 }
 
+// The same sample of a VIEW (a sub-box of r1 x r2 rows and columns per plane inside a larger array, planes p0 and rows p1 elements apart): `pos` and the
+// seven neighbours are FLAT positions of the sub-box, exactly those szh_sample_point reads of a contiguous copy -- a flat position may run over a row's
+// end into the next row, as the reference's walk does --, and only the address of each takes the pitches.  Same sum, same order.
+SZH_HD int64_t szh_view_addr(int64_t flat, int64_t r2, int64_t r12, int64_t p0, int64_t p1)
+{
+    const int64_t k = flat / r12, rem = flat - k * r12, i = rem / r2;
+    return k * p0 + i * p1 + (rem - i * r2);
+}
+template <class T>
+SZH_HD void szh_sample_point_view(const T *data, int64_t pos, int64_t r2, int64_t r12, int64_t p0, int64_t p1, double ebD, unsigned max_radius,
+                                  unsigned *radius_index, int *within_eb)
+{
+    auto at = [&](int64_t back) { return data[szh_view_addr(pos - back, r2, r12, p0, p1)]; };
+    const T cur = at(0);
+    const T pred = at(1) + at(r2) + at(r12) - at(1 + r12) - at(r2 + 1) - at(r2 + r12) + at(r2 + r12 + 1);
+    const T pred_err = szh_abs((T)(pred - cur));
+    *within_eb = ((double)pred_err < ebD) ? 1 : 0;
+    *radius_index = szh_radius_index(((double)pred_err / ebD + 1) / 2, max_radius);
+}
+
 // number of logical sample rows the sequential walk of the reference visits before its first
 // position >= len (rows are linearised as (n1-1)*(r1-1) + (n2-1)); host-side helper.
 SZH_HD int64_t szh_sample_col0_2d(int64_t n, int sd) { return n == 1 ? sd - 1 : sd - (n % sd); }

@@ -797,3 +797,30 @@ __global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int
     else
         for (int j = j0; j < e2 && j < j0 + VW; ++j) d[j] = s[j];
 }
+
+// The inverse of k_omp_crop (szhip_scatter_view): a contiguous array of e0 x e1 x e2 values into a VIEW whose planes lie d0 and whose rows d1 elements apart.
+// Every row is cut at the 16-byte boundaries of its DESTINATION: a head of fewer than 16 bytes up to the first boundary, whole 16-byte pieces -- one
+// store each, the values read from the source one by one where its address is not aligned alike --, and a tail behind the last boundary; head and tail go
+// value by value.  A lane takes one piece of one row, consecutive lanes consecutive pieces (`ppr` pieces a row: the head and (e2 + VW - 1) / VW more).
+// Nothing outside a row's e2 values is written, and no value of the view is read.
+template <class T>
+__global__ __launch_bounds__(256) void k_view_scatter(const T *__restrict__ src, T *__restrict__ dst, int64_t d0, int64_t d1, int e1, int e2, int ppr, int64_t pieces)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    const int64_t row = idx / ppr, k = row / e1;
+    const int p = (int)(idx - row * ppr), i = (int)(row - k * e1);
+    const T *s = src + row * e2;
+    T *d = dst + k * d0 + (int64_t)i * d1;
+    int head = (int)(((16u - (unsigned)((uintptr_t)d & 15u)) & 15u) / (unsigned)sizeof(T));      // (`d` is aligned to its element)
+    if (head > e2) head = e2;
+    const int j0 = p == 0 ? 0 : head + (p - 1) * VW, j1 = p == 0 ? head : (j0 + VW < e2 ? j0 + VW : e2);
+    if (p > 0 && j1 - j0 == VW) {
+        uint4 v;
+        if ((((uintptr_t)(s + j0)) & 15u) == 0) v = *reinterpret_cast<const uint4 *>(s + j0);
+        else { T t[VW]; for (int q = 0; q < VW; ++q) t[q] = s[j0 + q]; __builtin_memcpy(&v, t, 16); }
+        *reinterpret_cast<uint4 *>(d + j0) = v;
+    } else
+        for (int j = j0; j < j1; ++j) d[j] = s[j];
+}

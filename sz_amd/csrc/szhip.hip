@@ -479,7 +479,7 @@ int szhip_compress_omp(szhip_ctx *ctx, int dtype, const void *data, int data_on_
     if (!(eb > 0)) return SZHIP_ERR_ARG;
     TRY(check_alignment_set_device(ctx, dtype, data));
     return synced_on_failure(ctx,
-               BY_DTYPE(dtype, compress_omp_impl, ctx, data, data_on_device, r0, r1, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats));
+               BY_DTYPE(dtype, compress_omp_impl, ctx, data, data_on_device, r0, r1, r2, r1 * r2, r2, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats));
 }
 
 int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -489,7 +489,7 @@ int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream,
     if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
     TRY(check_alignment_set_device(ctx, dtype, out));
     return synced_on_failure(ctx,
-               BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, stats));
+               BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, 0, 0, stats));
 }
 
 int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -506,6 +506,71 @@ int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *
     TRY(check_alignment_set_device(ctx, dtype, out));
     return synced_on_failure(ctx,
                BY_DTYPE(dtype, decompress_omp_region_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, lo, hi, out, out_on_device, stats));
+}
+
+// ---- views (szhip.h): a sub-box of r0 x r1 x r2 values whose planes lie pitch0 and whose rows pitch1 elements apart
+static int check_view(szhip_ctx *ctx, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1)
+{
+    if (pitch1 < r2 || pitch1 > ((size_t)1 << 48) || (r0 != 0 && (pitch0 / pitch1 < r1 || pitch0 > ((size_t)1 << 48)))) {      // (a 2-D view: pitch0 is not looked at)
+        snprintf(ctx->err, sizeof(ctx->err), "view pitches %zu / %zu below its extents %zu x %zu x %zu (pitch1 >= r2, pitch0 >= r1 * pitch1)", pitch0, pitch1, r0, r1, r2);
+        return SZHIP_ERR_ARG;
+    }
+    return SZHIP_OK;
+}
+static bool view_dims_ok(size_t r0, size_t r1, size_t r2)      // 3-D, or (r0 == 0) 2-D; the launch grids count 16-byte pieces in 32 bits of workgroups
+{
+    return r1 >= 1 && r2 >= 1 && r0 <= 0x7fffffff && r1 <= 0x7fffffff && r2 <= 0x7fffffff - 64 &&       /* (the kernels step through a row in `int`, 16 bytes at a time) */ (double)(r0 ? r0 : 1) * (double)r1 * ((double)r2 / 2 + 2) < 256.0 * 4.0e9;
+}
+
+int szhip_pack_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, void **d_packed)
+{
+    if (!ctx || !data || !d_packed || !view_dims_ok(r0, r1, r2)) return SZHIP_ERR_ARG;
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    const size_t n0 = r0 ? r0 : 1;
+    TRY(ensure(ctx, ctx->in, n0 * r1 * r2 * (dtype == SZHIP_F32 ? 4 : 8)));
+    TRY(synced_on_failure(ctx, BY_DTYPE(dtype, pack_view_impl, ctx, data, data_on_device, n0, r1, r2, r0 ? pitch0 : 0, pitch1, ctx->in.p)));
+    *d_packed = ctx->in.p;
+    return SZHIP_OK;
+}
+
+int szhip_scatter_view(szhip_ctx *ctx, int dtype, const void *d_packed, size_t r0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1)
+{
+    if (!ctx || !d_packed || !out || !view_dims_ok(r0, r1, r2)) return SZHIP_ERR_ARG;
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    TRY(check_alignment_set_device(ctx, dtype, d_packed));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, scatter_view_impl, ctx, d_packed, r0 ? r0 : 1, r1, r2, out, out_on_device, r0 ? pitch0 : 0, pitch1));
+}
+
+int szhip_compress_omp_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, double eb,
+                            int thread_num, const szhip_params *params, const unsigned char *meta, size_t meta_len, int out_on_device, unsigned char **out,
+                            size_t *out_size, szhip_stats *stats)
+{
+    if (!ctx || !data || !params || !meta || !out || !out_size) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff || thread_num < 1) return SZHIP_ERR_ARG;
+    if (!(eb > 0)) return SZHIP_ERR_ARG;
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    TRY(check_alignment_set_device(ctx, dtype, data));
+    if (!data_on_device && (pitch1 != r2 || pitch0 != r1 * r2)) {      // a view on the host: its rows alone go to the device, packed; then the contiguous call
+        if (r0 * r1 * r2 >= ((size_t)1 << 40)) return SZHIP_ERR_UNSUP;
+        TRY(ensure(ctx, ctx->in, r0 * r1 * r2 * (dtype == SZHIP_F32 ? 4 : 8)));
+        TRY(synced_on_failure(ctx, BY_DTYPE(dtype, pack_view_impl, ctx, data, 0, r0, r1, r2, pitch0, pitch1, ctx->in.p)));
+        data = ctx->in.p; data_on_device = 1; pitch0 = r1 * r2; pitch1 = r2;
+    }
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, compress_omp_impl, ctx, data, data_on_device, r0, r1, r2, pitch0, pitch1, eb, thread_num, params, meta, meta_len, out_on_device, out, out_size, stats));
+}
+
+int szhip_decompress_omp_view(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
+                              size_t r0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
+{
+    if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    TRY(check_alignment_set_device(ctx, dtype, out));
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, pitch0, pitch1, stats));
 }
 
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,
@@ -618,7 +683,7 @@ int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes)
     if (!ctx || !dst) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     DevBuf *bufs[] = {&ctx->coef, &ctx->blk_lor, &ctx->codes_nat, &ctx->codes_blk, &ctx->hist, &ctx->col_zeros, &ctx->col_off,
-                      &ctx->unpred, &ctx->stream_buf, &ctx->rb_down, &ctx->rb_right, &ctx->small};
+                      &ctx->unpred, &ctx->stream_buf, &ctx->rb_down, &ctx->rb_right, &ctx->small, &ctx->in};
     if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0]))) return SZHIP_ERR_ARG;
     if (!bufs[which]->p || bufs[which]->cap < bytes) return SZHIP_ERR_ARG;
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -438,6 +438,66 @@ __global__ void k_sample_walk(szh_geom3 G, const T *__restrict__ data, int sd, d
     if (w) atomicAdd(within, w);
 }
 
+// k_sample<T, false> and k_sample_walk<T, false> on a VIEW (szhip_compress_omp_view): `G` is the geometry of the sub-box -- the lattice, the row limit and
+// the end test are those of a contiguous copy --, `p0` / `p1` the element pitches of the planes and rows of the array it lies in.  Siblings, not a
+// parameter of the kernels above: those keep their code.  A sample whose column lies inside its row (all but the one overflow sample a row may
+// have when the sample distance exceeds the row) reads its neighbours at pitch offsets; the others map every flat position (szh_sample_point_view).
+template <class T>
+__global__ __launch_bounds__(256) void k_sample_view(szh_geom3 G, const T *__restrict__ data, int64_t p0, int64_t p1, int64_t nrows, int sd, double ebD,
+                                                     unsigned max_radius, unsigned *radius_hist, u64 *within)
+{
+    __shared__ unsigned sh_r[SZH_LDS_RADIUS_BINS];
+    for (int i = threadIdx.x; i < SZH_LDS_RADIUS_BINS; i += 256) sh_r[i] = 0;
+    __syncthreads();
+    const int64_t rpp = G.g1.count - 1, r2 = G.g2.count;
+    unsigned w = 0;
+    for (int64_t ridx = (int64_t)blockIdx.x * 256 + threadIdx.x; ridx < nrows; ridx += (int64_t)gridDim.x * 256) {
+        const int64_t n1 = ridx / rpp + 1, n2 = ridx - (n1 - 1) * rpp + 1;
+        const int64_t c0 = sd - ((n1 + n2) % sd);
+        const int64_t origin = n1 * G.d0 + n2 * r2;
+        for (int64_t m = 0;; ++m) {
+            const int64_t col = c0 + m * sd;
+            if (m > 0 && col >= r2) break;
+            const int64_t pos = origin + col;
+            if (pos >= G.n) break;
+            unsigned ri; int fi, we;
+            if (col < r2) szh_sample_point<T>(data, n1 * p0 + n2 * p1 + col, p1, p0, ebD, (T)0, max_radius, &ri, &fi, &we);
+            else szh_sample_point_view<T>(data, pos, r2, G.d0, p0, p1, ebD, max_radius, &ri, &we);
+            if (ri < SZH_LDS_RADIUS_BINS) atomicAdd(&sh_r[ri], 1u); else atomicAdd(&radius_hist[ri], 1u);
+            w += (unsigned)we;
+        }
+    }
+    w = wave_sum_u32(w);
+    if ((threadIdx.x & 63) == 0 && w) atomicAdd(within, (u64)w);
+    __syncthreads();
+    for (int i = threadIdx.x; i < SZH_LDS_RADIUS_BINS; i += 256) if (sh_r[i]) atomicAdd(&radius_hist[i], sh_r[i]);
+}
+template <class T>
+__global__ void k_sample_walk_view(szh_geom3 G, const T *__restrict__ data, int64_t p0, int64_t p1, int sd, double ebD, unsigned max_radius,
+                                   unsigned *radius_hist, u64 *within)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t r3 = G.g2.count, r2 = G.g1.count, r23 = r2 * r3, len = G.n;
+    int64_t oc = sd - 2, n1 = 1, n2 = 1, pos = r23 + r3 + oc;
+    u64 w = 0;
+    while (pos < len) {
+        unsigned ri; int we;
+        szh_sample_point_view<T>(data, pos, r3, r23, p0, p1, ebD, max_radius, &ri, &we);
+        atomicAdd(&radius_hist[ri], 1u);
+        w += (unsigned)we;
+        oc += sd;
+        if (oc >= r3) {
+            n2++;
+            if (n2 == r2) { n1++; n2 = 1; pos += r3; }
+            const int64_t oc2 = (n1 + n2) % sd;
+            pos += (r3 + sd - oc) + (sd - oc2);
+            oc = sd - oc2;
+            if (oc == 0) oc++;
+        } else pos += sd;
+    }
+    if (w) atomicAdd(within, w);
+}
+
 // sequential (order-preserving) sum of the values within eb of dense_pos: ONE wavefront, every lane
 // carries the same running sum; the additions happen in array order so the float rounding sequence
 // is the reference's.  Only launched when use_mean is decided.

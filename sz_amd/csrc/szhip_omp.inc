@@ -36,9 +36,57 @@ static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, si
 }
 
 // the column-per-lane sweep of szh_ompcol.h serves 32 x 32 box faces (any number of planes), two boxes to a wavefront, rows read 16 bytes at a time
-static bool omp_col_applies(const szh_omp_geom &g, const void *base, size_t row_pitch_bytes)
+static bool omp_col_applies(const szh_omp_geom &g, const void *base, size_t row_pitch_bytes, size_t plane_pitch_bytes)
 {
-    return g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0 && ((uintptr_t)base & 15u) == 0 && row_pitch_bytes % 16 == 0;
+    return g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0 && ((uintptr_t)base & 15u) == 0 && row_pitch_bytes % 16 == 0 && plane_pitch_bytes % 16 == 0;
+}
+// A VIEW (szhip_compress_omp_view / szhip_decompress_omp_view): the boxes of `g` lie in an array whose planes are pitch0 and whose rows pitch1 elements apart.  The
+// sweeps, the encoders' reads of verbatim values and k_omp_scatter address the array through g.d0 / g.d1; rows may be taken 16 bytes at a time only where every row
+// of every plane starts on such a boundary (the base address is looked at by the caller, as for a contiguous array)
+static void omp_view_pitches(szh_omp_geom *g, size_t pitch0, size_t pitch1, size_t elem)
+{
+    g->d0 = (int64_t)pitch0; g->d1 = (int64_t)pitch1;
+    g->vec = (g->c2 % 4 == 0 && pitch1 * elem % 16 == 0 && pitch0 * elem % 16 == 0) ? 1 : 0;
+}
+
+// ---- views (szhip.h): what szhip_pack_view / szhip_scatter_view and the host-view form of szhip_compress_omp_view run
+// the gather (k_omp_crop, or the rows of a host view through the staging buffers) into `d_dst`, n0 x r1 x r2 values, contiguous
+template <class T>
+int pack_view_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t n0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, void *d_dst)
+{
+    const size_t n = n0 * r1 * r2;
+    if (!data_on_device) {
+        const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
+        return staged_copy(ctx, d_dst, data, n * sizeof(T), true, &hv);
+    }
+    const int cpr = (int)((r2 + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+    const int64_t total = (int64_t)(n0 * r1) * cpr;
+    hipLaunchKernelGGL((k_omp_crop<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const T *)data, (int64_t)pitch0, (int64_t)pitch1, (T *)d_dst, (int)r1, (int)r2, cpr, total);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+template <class T>
+int scatter_view_impl(szhip_ctx *ctx, const void *d_packed, size_t n0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1)
+{
+    if (!out_on_device) {
+        const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
+        return staged_copy(ctx, out, d_packed, n0 * r1 * r2 * sizeof(T), false, &hv);
+    }
+    const int ppr = 1 + (int)((r2 + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+    const int64_t total = (int64_t)(n0 * r1) * ppr;
+    hipLaunchKernelGGL((k_view_scatter<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const T *)d_packed, (T *)out, (int64_t)pitch0, (int64_t)pitch1, (int)r1, (int)r2, ppr, total);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+// A device view that misses the 16-byte conditions while a packed copy of it would take the column form: value by value it costs 4.3 x (compress) / 2.7 x (decode) the
+// packing pass plus the column sweep (512^3 float32, DESIGN 4.5.2), so such a view is gathered into / decoded in the context's contiguous buffer.  Same stream, same values.
+// (`g`: the grid of the sub-box.)  Shapes whose packed copy takes k_omp_box either way run where they lie: that pair was not measured.
+static bool omp_view_packs(const szh_omp_geom &g, const void *base, size_t pitch0, size_t pitch1, size_t elem)
+{
+    const bool aligned = ((uintptr_t)base & 15u) == 0 && pitch1 * elem % 16 == 0 && pitch0 * elem % 16 == 0;
+    return !aligned && g.c1 == 32 && g.c2 == 32 && g.nb % 2 == 0;
 }
 
 // One compress call into the OpenMP container: its state, and one member function per phase (compress_omp_impl is their sequence).
@@ -48,7 +96,7 @@ struct omp_call : call_base {
     const szhip_params *const prm; const unsigned char *const meta; const size_t meta_len;
     const int out_on_device; unsigned char **const out; size_t *const out_size;
     const T eb;                                                // `float realPrecision` of sz_omp.c:63 (double: :578)
-    szh_omp_geom g; const szh_geom3 G; const size_t row_bytes; const int64_t n = G.n;
+    szh_omp_geom g; const szh_geom3 G; const size_t row_bytes, plane_bytes; const int64_t n = G.n;      // (`G`: the box of values, contiguous; `g`, the pitches in bytes: the array they lie in)
     // ---- device arrays
     const T *d_in = nullptr; u64 *sm = nullptr; uint16_t *d_codes = nullptr; unsigned char *d_stream = nullptr;
     unsigned *d_ucount = nullptr, *d_hist_box = nullptr; T *d_first = nullptr; u64 *d_ucount64 = nullptr, *d_uoff = nullptr, *d_box_bytes = nullptr, *d_box_off = nullptr;
@@ -67,7 +115,7 @@ struct omp_call : call_base {
         TRY(clear_small(ctx, &sm));
         HIPCHK(hipEventRecord(ctx->ev[0], st));
         intervals = prm->quantization_intervals;
-        if (intervals == 0) TRY(sampled_intervals<T>(ctx, G, false, d_in, prm, eb, sm, &intervals, &host_ms));
+        if (intervals == 0) TRY(sampled_intervals<T>(ctx, G, false, d_in, prm, eb, sm, &intervals, &host_ms, g.d0, g.d1));
         if (intervals > 65536 || intervals < 4) FAIL(SZHIP_ERR_UNSUP, "quantization interval count %u outside [4,65536]", intervals);
         S.intervals = intervals;
         HIPCHK(hipEventRecord(ctx->ev[1], st));
@@ -85,7 +133,7 @@ struct omp_call : call_base {
         const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
         box_hist = intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (omp_col_applies(g, d_in, row_bytes)) {             // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
+        if (omp_col_applies(g, d_in, row_bytes, plane_bytes)) {             // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
             szh_oc::sweep_args<T> oa;
             oa.g = g; oa.data = d_in; oa.out = nullptr; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
             oa.ucount = d_ucount; oa.ucount64 = d_ucount64; oa.first = d_first; oa.uoff = nullptr; oa.vflags = nullptr; oa.fw = 0;
@@ -98,7 +146,7 @@ struct omp_call : call_base {
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
         S.quant_kernel_launches = 1;
-        S.quant_kernel = omp_col_applies(g, d_in, row_bytes) ? 3 : (g.vec ? 4 : 5);      // (szhip.h: which form the address and the box shape allowed)
+        S.quant_kernel = omp_col_applies(g, d_in, row_bytes, plane_bytes) ? 3 : (g.vec ? 4 : 5);      // (szhip.h: which form the address and the box shape allowed)
         return SZHIP_OK;
     }
     // ---- ONE histogram over all boxes -> code book (host); the ranks of the boxes' verbatim values meanwhile.  Small alphabets: a
@@ -233,14 +281,20 @@ struct omp_call : call_base {
 };
 
 template <class T>
-int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb_in, int thread_num,
+int compress_omp_impl(szhip_ctx *ctx, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, double eb_in, int thread_num,
                       const szhip_params *prm, const unsigned char *meta, size_t meta_len, int out_on_device, unsigned char **out, size_t *out_size,
                       szhip_stats *stats)
 {
     szh_omp_geom g;
     TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
     if (!((T)eb_in > 0)) FAIL(SZHIP_ERR_ARG, "error bound %g", eb_in);
-    omp_call<T> c{call_base(ctx), prm, meta, meta_len, out_on_device, out, out_size, (T)eb_in, g, szh_make_geom3((int)r0, (int)r1, (int)r2), r2 * sizeof(T)};
+    if ((pitch1 != r2 || pitch0 != r1 * r2) && omp_view_packs(g, data, pitch0, pitch1, sizeof(T))) {      // (a view on the device; one on the host was packed by the caller)
+        TRY(ensure(ctx, ctx->in, r0 * r1 * r2 * sizeof(T)));
+        TRY(pack_view_impl<T>(ctx, data, 1, r0, r1, r2, pitch0, pitch1, ctx->in.p));
+        data = ctx->in.p; pitch0 = r1 * r2; pitch1 = r2;
+    }
+    if (pitch1 != r2 || pitch0 != r1 * r2) omp_view_pitches(&g, pitch0, pitch1, sizeof(T));
+    omp_call<T> c{call_base(ctx), prm, meta, meta_len, out_on_device, out, out_size, (T)eb_in, g, szh_make_geom3((int)r0, (int)r1, (int)r2), pitch1 * sizeof(T), pitch0 * sizeof(T)};
     TRY(c.choose_intervals(data, data_on_device));
     TRY(c.quantise());
     TRY(c.hist_and_book());
@@ -255,6 +309,8 @@ struct omp_dec : call_base {
     // ---- arguments
     const size_t stream_len, body_off, r0, r1, r2; void *const out; const int out_on_device;
     stream_intake in;
+    bool packed = false;
+    size_t pitch0 = 0, pitch1 = 0;                             // a view (szhip_decompress_omp_view): the element pitches of the array `out` lies in; 0: contiguous
     // ---- the header and the tables behind it
     szh_omp_geom g; int64_t n = 0; T eb = 0; unsigned intervals = 0; u64 E = 0;
     size_t off_first = 0, off_unpred = 0, off_pay = 0;
@@ -349,16 +405,19 @@ struct omp_dec : call_base {
     }
     // ---- reconstruct: the inverse of the compress call's sweep
     int reconstruct() {
-        TRY(device_out(ctx, out, out_on_device, (size_t)n, &d_out));
+        packed = view() && out_on_device && omp_view_packs(g, out, pitch0, pitch1, sizeof(T));      // (then: decoded contiguous, k_view_scatter in finish)
+        TRY(device_out(ctx, out, out_on_device && !packed, (size_t)n, &d_out));
+        if (view() && out_on_device && !packed) omp_view_pitches(&g, pitch0, pitch1, sizeof(T));       // (a view on the host: decoded contiguous, its rows copied out in finish)
         return sweep();
     }
+    bool view() const { return pitch1 != 0 && (pitch1 != r2 || pitch0 != r1 * r2); }
     // the boxes of `g` from d_codes, d_first, d_unpred / d_uoff into d_out, whose pitches `g` has
     int sweep() {
         if ((uintptr_t)d_out & 15u) g.vec = 0;
-        const size_t row_bytes = (size_t)g.d1 * sizeof(T);
+        const size_t row_bytes = (size_t)g.d1 * sizeof(T), plane_bytes = (size_t)g.d0 * sizeof(T);
         const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (omp_col_applies(g, d_out, row_bytes)) {
+        if (omp_col_applies(g, d_out, row_bytes, plane_bytes)) {
             // the verbatim values go to their places in the output first (boxes that have any); the sweep picks them up where a code is zero
             int fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32;        // flag words per box: a bit per group of rows one load of the sweep covers
             unsigned *d_vflags = nullptr;
@@ -382,14 +441,18 @@ struct omp_dec : call_base {
                                   d_out, eb, (T)(1 / eb), (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, const_cast<T *>(d_first), d_unpred, d_uoff);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel = omp_col_applies(g, d_out, row_bytes) ? 3 : (g.vec ? 4 : 5);
+        S.quant_kernel = omp_col_applies(g, d_out, row_bytes, plane_bytes) ? 3 : (g.vec ? 4 : 5);
         return SZHIP_OK;
     }
     // ---- the array to the caller, the kernels' error count, the statistics
     int finish() {
         unsigned bad = 0;
         HIPCHK(hipMemcpyAsync(&bad, sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
-        TRY(return_out(ctx, out, out_on_device, d_out, (size_t)n));
+        if (view() && (!out_on_device || packed)) {                // only a stream whose boxes all decoded reaches the caller's array
+            HIPCHK(hipStreamSynchronize(st));
+            if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes whose payload or verbatim-value count does not fit their codes", bad);
+            TRY(scatter_view_impl<T>(ctx, d_out, r0, r1, r2, out, out_on_device, pitch0, pitch1));
+        } else TRY(return_out(ctx, out, out_on_device, d_out, (size_t)n));
         HIPCHK(hipStreamSynchronize(st));
         if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes whose payload or verbatim-value count does not fit their codes", bad);
         decompress_times(ctx, S, host_ms, t_begin, (size_t)n * sizeof(T));
@@ -399,9 +462,10 @@ struct omp_dec : call_base {
 
 template <class T>
 int decompress_omp_impl(szhip_ctx *ctx, const unsigned char *stream_in, int stream_on_device, size_t stream_len, size_t body_off, size_t r0, size_t r1, size_t r2,
-                        void *out, int out_on_device, szhip_stats *stats)
+                        void *out, int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
 {
     omp_dec<T> d{call_base(ctx), stream_len, body_off, r0, r1, r2, out, out_on_device, {ctx, stream_in, stream_on_device, stream_len}};
+    d.pitch0 = pitch0; d.pitch1 = pitch1;
     TRY(d.read_header());
     TRY(d.decode_boxes());
     TRY(d.reconstruct());
@@ -547,3 +611,4 @@ int decompress_omp_region_impl(szhip_ctx *ctx, const unsigned char *stream_in, i
     TRY(r.finish());
     return d.done(stats);
 }
+

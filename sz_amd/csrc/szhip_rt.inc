@@ -161,13 +161,36 @@ static void settle_streams(szhip_ctx *ctx, const hipStream_t *mains, int n_mains
 // unpinning stalled LATER calls (see the coefficient transfers in compress_impl).  Here the array is cut into 8 MiB chunks; SZH_STAGE_T
 // host threads each own two pinned buffers and take every SZH_STAGE_T-th chunk: memcpy into (out of) a pinned buffer, asynchronous DMA on
 // the context's stream, the other buffer meanwhile.  The call returns when the last byte has arrived.
+// The host side may be a VIEW (`hv`; the calls that take pitches): rows of hv->row bytes, hv->pitch1 bytes apart, hv->r1 of them a plane, planes hv->pitch0
+// bytes apart.  The device side stays contiguous, so only the rows' bytes cross the bus: the memcpy into (out of) the pinned buffer walks the rows.
 int tune_int(const char *name, int def);
 constexpr size_t SZH_STAGE_CHUNK = 8u << 20;
-int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool to_device)
+struct host_view { size_t r1, row, pitch0, pitch1; };
+// bytes [off, off + len) of the view's packed order: out of the view at `base` into `buf` (gather) or out of `buf` into the view
+static void host_view_move(const host_view &v, char *base, char *buf, size_t off, size_t len, bool gather)
+{
+    size_t rw = off / v.row, col = off - rw * v.row;
+    while (len) {
+        const size_t k = rw / v.r1, i = rw - k * v.r1, take = std::min(len, v.row - col);
+        char *p = base + k * v.pitch0 + i * v.pitch1 + col;
+        if (gather) memcpy(buf, p, take); else memcpy(p, buf, take);
+        buf += take; len -= take; col = 0; ++rw;
+    }
+}
+int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool to_device, const host_view *hv = nullptr)
 {
     hipStream_t st = ctx->stream;
     // (SZ_HIP_STAGE_CHUNK_KB: smaller chunks, so that tests reach this path with small arrays)
     const size_t chunk = std::min(SZH_STAGE_CHUNK, (size_t)std::max(1, tune_int("SZ_HIP_STAGE_CHUNK_KB", (int)(SZH_STAGE_CHUNK >> 10))) << 10);
+    if (bytes < 4 * chunk && hv) {                                 // a small view: through one pinned buffer
+        TRY(ensure_pinned3(ctx, bytes));
+        HIPCHK(hipStreamSynchronize(st));
+        if (to_device) host_view_move(*hv, (char *)const_cast<void *>(src), (char *)ctx->pinned3, 0, bytes, true);
+        HIPCHK(hipMemcpyAsync(to_device ? dst : ctx->pinned3, to_device ? ctx->pinned3 : src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (!to_device) host_view_move(*hv, (char *)dst, (char *)ctx->pinned3, 0, bytes, false);
+        return SZHIP_OK;
+    }
     if (bytes < 4 * chunk) {
         HIPCHK(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -184,6 +207,13 @@ int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool t
     const size_t nchunks = (bytes + chunk - 1) / chunk;
     std::atomic<int> failed(0);
     const int device = ctx->device;
+    // the host's end of a chunk: the caller's contiguous array, or the rows of its view
+    auto host_in = [&](void *buf, size_t off, size_t len) {
+        if (hv) host_view_move(*hv, (char *)const_cast<void *>(src), (char *)buf, off, len, true); else memcpy(buf, (const char *)src + off, len);
+    };
+    auto host_out = [&](const void *buf, size_t off, size_t len) {
+        if (hv) host_view_move(*hv, (char *)dst, (char *)const_cast<void *>(buf), off, len, false); else memcpy((char *)dst + off, buf, len);
+    };
     auto worker = [&](int w) {
         if (hipSetDevice(device) != hipSuccess) { failed = 1; return; }
         size_t pend_off[2] = {0, 0}, pend_len[2] = {0, 0};        // device-to-host: the chunk in flight into buffer k
@@ -193,14 +223,14 @@ int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool t
             const size_t off = c * chunk, len = std::min(chunk, bytes - off);
             if (to_device) {
                 if (pend[k] && hipEventSynchronize(ctx->stage_ev[w][k]) != hipSuccess) { failed = 1; return; }   // buffer k is free again
-                memcpy(ctx->stage_buf[w][k], (const char *)src + off, len);
+                host_in(ctx->stage_buf[w][k], off, len);
                 if (hipMemcpyAsync((char *)dst + off, ctx->stage_buf[w][k], len, hipMemcpyHostToDevice, st) != hipSuccess ||
                     hipEventRecord(ctx->stage_ev[w][k], st) != hipSuccess) { failed = 1; return; }
                 pend[k] = true;
             } else {
                 if (pend[k]) {                                     // the chunk that went into buffer k two rounds ago: hand it to the caller
                     if (hipEventSynchronize(ctx->stage_ev[w][k]) != hipSuccess) { failed = 1; return; }
-                    memcpy((char *)dst + pend_off[k], ctx->stage_buf[w][k], pend_len[k]);
+                    host_out(ctx->stage_buf[w][k], pend_off[k], pend_len[k]);
                 }
                 if (hipMemcpyAsync(ctx->stage_buf[w][k], (const char *)src + off, len, hipMemcpyDeviceToHost, st) != hipSuccess ||
                     hipEventRecord(ctx->stage_ev[w][k], st) != hipSuccess) { failed = 1; return; }
@@ -210,7 +240,7 @@ int staged_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, bool t
         for (int q = 0; q < 2; ++q, k ^= 1) {                      // drain, oldest first
             if (!pend[k]) continue;
             if (hipEventSynchronize(ctx->stage_ev[w][k]) != hipSuccess) { failed = 1; return; }
-            if (!to_device) memcpy((char *)dst + pend_off[k], ctx->stage_buf[w][k], pend_len[k]);
+            if (!to_device) host_out(ctx->stage_buf[w][k], pend_off[k], pend_len[k]);
         }
     };
     std::vector<std::thread> th;

@@ -47,9 +47,12 @@ template <class H> unsigned pick_intervals(const H *hist, unsigned max_radius, f
     return p2 < floor_ ? floor_ : p2;
 }
 // the SZ 1.4 interval optimiser (optimize_intervals_float_{1,2,3}D_opt) on the SZ 2.1 sample lattice, radius histogram only: sampled on the device into
-// ctx->hist, the count chosen on the host.  `one_d`: the 1-D lattice (sz_float.c:4413)
+// ctx->hist, the count chosen on the host.  `one_d`: the 1-D lattice (sz_float.c:4413).  `p0` / `p1` (3-D only; 0: the array is contiguous): the element pitches of
+// a view whose sub-box `G` describes -- the same samples through k_sample_view / k_sample_walk_view
 template <class T>
-int sampled_intervals(szhip_ctx *ctx, const szh_geom3 &G, bool one_d, const T *d_in, const szhip_params *prm, T eb, u64 *sm, unsigned *intervals, double *host_ms) {
+int sampled_intervals(szhip_ctx *ctx, const szh_geom3 &G, bool one_d, const T *d_in, const szhip_params *prm, T eb, u64 *sm, unsigned *intervals, double *host_ms,
+                      int64_t p0 = 0, int64_t p1 = 0) {
+    const bool view = p1 != 0 && (p0 != G.d0 || p1 != G.d1);
     hipStream_t st = ctx->stream;
     const unsigned max_radius = prm->max_quant_intervals / 2;
     TRY(ensure(ctx, ctx->hist, (size_t)(max_radius + 8192) * 4 + 64));
@@ -63,12 +66,14 @@ int sampled_intervals(szhip_ctx *ctx, const szh_geom3 &G, bool one_d, const T *d
         hipLaunchKernelGGL((k_sample_1d<T>), dim3(grid), dim3(256), 0, st, d_in, n, prm->sample_distance, (double)eb, max_radius, d_rh);
         HIPCHK(hipGetLastError());
     } else if (G.ndim == 3 && (G.g0.count <= 1 || G.g1.count <= 1)) {      // a degenerate 3-D array: the reference's walk, literally
-        hipLaunchKernelGGL((k_sample_walk<T, false>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)0, max_radius, d_rh, d_fh, sm + SM_WITHIN);
+        if (view) hipLaunchKernelGGL((k_sample_walk_view<T>), dim3(1), dim3(64), 0, st, G, d_in, p0, p1, prm->sample_distance, (double)eb, max_radius, d_rh, sm + SM_WITHIN);
+        else hipLaunchKernelGGL((k_sample_walk<T, false>), dim3(1), dim3(64), 0, st, G, d_in, prm->sample_distance, (double)eb, (T)0, max_radius, d_rh, d_fh, sm + SM_WITHIN);
         HIPCHK(hipGetLastError());
     } else if (nrows > 0) {
         int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-        hipLaunchKernelGGL((k_sample<T, false>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb, (T)0,
-                           max_radius, d_rh, d_fh, sm + SM_WITHIN);
+        if (view) hipLaunchKernelGGL((k_sample_view<T>), dim3(grid), dim3(256), 0, st, G, d_in, p0, p1, nrows, prm->sample_distance, (double)eb, max_radius, d_rh, sm + SM_WITHIN);
+        else hipLaunchKernelGGL((k_sample<T, false>), dim3(grid), dim3(256), 0, st, G, d_in, nrows, prm->sample_distance, (double)eb, (T)0,
+                                max_radius, d_rh, d_fh, sm + SM_WITHIN);
         HIPCHK(hipGetLastError());
     }
     unsigned *h_rh = (unsigned *)ctx->pinned;
