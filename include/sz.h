@@ -243,6 +243,29 @@ unsigned char *SZ_hip_compress_region(int dataType, void *data, size_t *outSize,
                                       size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const size_t start[3], const size_t end[3]);
 int SZ_hip_decompress_into_region(int dataType, unsigned char *bytes, size_t byteLength, void *parent, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1,
                                   const size_t start[3], const size_t end[3]);
+/* An array that is already on the GPU, and a stream that may stay there.  Pointer kinds are taken on trust from the arguments, and the ordering contract is szhip.h's:
+ * whatever produced the array or the stream is synchronised by the caller first; the calls return when their results are complete.  Configuration (SZ_Init, confparams_cpr)
+ * and SZ_hip_last_stats behave as for SZ_compress_args / SZ_decompress on the calling thread.
+ * SZ_hip_compress_device: everything SZ_compress_args does, for an array in DEVICE memory (aligned to its element); the stream comes back as malloc'd host memory, byte for
+ * byte what SZ_compress_args returns for a host copy of the array under the same configuration -- every error-bound mode, SZ 2.1 and withLinearRegression = NO, 1-D to 4-D,
+ * SZ_HIP_MODE=omp, protectValueRange, the constant, <= 20-value and raw-store rules, the lossless stage (on the host, on the finished stream) -- and NULL with the same
+ * message for whatever SZ_compress_args refuses.  The array is never written and never copied to the host: on the input side only scalars cross the bus (the range, the first
+ * value of a constant array, the <= 20 values, the sign bytes of the PW_REL forms); the raw store is a kernel (szhip_store_be).
+ * SZ_hip_compress_device_into: the same stream into the caller's DEVICE buffer d_stream of `capacity` bytes (any alignment), *outSize = its length; nothing outside
+ * [d_stream, d_stream + capacity) is written; bytes of the buffer behind the stream are undefined.  SZ_SCES, or SZ_NSCS with a printed reason: a capacity below the stream's
+ * length (the context stays usable), and any configuration whose szMode is not SZ_BEST_SPEED -- the lossless stage is host code, so a stream that has to pass it is
+ * returned by SZ_hip_compress_device instead.
+ * SZ_hip_decompress_device: everything SZ_decompress reads (SZ 2.1, SZ 1.4, both PW_REL forms, the marked OpenMP container, constant, raw and <= 20-value streams, the
+ * protectValueRange clamp), decoded bit for bit into the caller's DEVICE array d_out (aligned to its element): exactly the array's values are written and nothing else.  The
+ * stream lies on the host (bytes_on_device = 0) or on the device (1, any alignment): of a device stream only its first 256 bytes (the header fields) and the sign bytes of
+ * a PW_REL container come to the host, the payload is read where it lies.  A zstd / gzip-wrapped stream that lies on the device is brought down WHOLE, unwrapped on the host
+ * and decoded from there: that stage is host code.  SZ_SCES, or SZ_NSCS with the reason SZ_decompress prints; on failure the contents of d_out are undefined. */
+unsigned char *SZ_hip_compress_device(int dataType, const void *d_data, size_t *outSize, int errBoundMode, double absErrBound,
+                                      double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1);
+int SZ_hip_compress_device_into(int dataType, const void *d_data, unsigned char *d_stream, size_t capacity, size_t *outSize, int errBoundMode,
+                                double absErrBound, double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1);
+int SZ_hip_decompress_device(int dataType, const unsigned char *bytes, int bytes_on_device, size_t byteLength, void *d_out,
+                             size_t r5, size_t r4, size_t r3, size_t r2, size_t r1);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

@@ -99,11 +99,13 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
  * What it reads from device memory must be complete when the call is made: synchronise the stream that produces it first -- the null stream's
  * implicit ordering does not reach non-blocking streams, and a device-to-device hipMemcpy may return to the host before the copy has finished
  * (profiles/r06_device_input_ordering.txt: a tool that decoded a stream right behind such a copy read a stream whose end had not arrived).
- * Alignment: a pointer to VALUES -- `data` of szhip_minmax, of every compress call and of the prepare calls, `out` of every decompress call -- is aligned to its
+ * Alignment: a pointer to VALUES -- `data` of szhip_minmax, of every compress call and of the prepare calls, `out` of every decompress call, d_src / d_out / d_data of
+ * szhip_store_be / szhip_load_be / szhip_fill / szhip_clamp -- is aligned to its
  * element (4 bytes for SZHIP_F32, 8 for SZHIP_F64), on the host or on the device; any other address is refused with SZHIP_ERR_ARG before anything is launched or
  * written.  More is never required: an array that starts at any element of a larger allocation (a chunk of a buffer, a view that skips a row) is taken, and the
  * library itself picks the kernels that need 16-byte rows only where the address allows them -- same stream, same values.  BYTE pointers -- `stream`, `meta`, a
- * caller's stream buffer (out_on_device = 2), the output arrays of szhip_huff_book -- take any alignment.  Nothing is written in front of an output or behind
+ * caller's stream buffer (out_on_device = 2), the output arrays of szhip_huff_book, `dst` of
+ * szhip_store_be and `src` of szhip_load_be -- take any alignment.  Nothing is written in front of an output or behind
  * its end (r0*r1*r2 values of a decompress call, the capacity of a caller's stream buffer), and an input array is never written.
  * A caller's stream buffer (out_on_device = 2 of szhip_compress / szhip_pool_submit) is written IN PLACE exactly when its address is a multiple of 16 and its
  * capacity is at least the stream's length + 64 (with SZ_HIP_DEV_BOOK=1, where the length is not known before the kernels run: at least the header without the
@@ -245,7 +247,7 @@ int szhip_scatter_view(szhip_ctx *ctx, int dtype, const void *d_packed, size_t r
  *                           408-419, 454-467): radExpo, segment_size, the compressed sign bytes and minLogValue.
  *   szhip_sz14_pwr_locate   (host only) where a PW_REL stream keeps its sign bytes, and its minLogValue;
  *   szhip_decompress_sz14_pwr  the SZ 1.4 inverse on a stream with those fields, then x = exp2(l) (0 below minLogValue), signs applied
- *                           (`signs_host`: n bytes or NULL).
+ *                           (`signs_host`: n bytes or NULL).  Of a device-resident stream only the fixed fields in front of the type array come to the host.
  * The reference's DEFAULT form of mode PW_REL (accelerate_pw_rel_compression = 1, ratio >= 1e-5: the table-driven "MSST19" quantiser,
  * sz_float.c:1824-2725, dispatch :2838, :2890; inverse szd_float.c:1702-2700, szd_float_pwr.c:1425-1528; stream flag 0x08):
  *   szhip_msst_prepare      the scan of computeRangeSize_float_MSST19 (dataCompression.c:121-166: sign bytes from element 1 on, nearZero) and
@@ -302,6 +304,29 @@ typedef struct szhip_book_record {
 } szhip_book_record;
 int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsigned char *out_tree, size_t out_tree_cap,
                     uint64_t *out_code64, uint8_t *out_len8, szhip_book_record *record);
+
+/*
+ * The copy-shaped passes of the drop-in calls for device-resident arrays (include/sz.h: SZ_hip_compress_device, SZ_hip_decompress_device; kernels in
+ * sz_amd/csrc/szh_store.h).  What SZ_compress_args / SZ_decompress do with host loops over the whole array:
+ *   szhip_store_be  the raw store (SZ_compress_args_float_StoreOriData, sz_float.c:526-552): the n values of the device array d_src as big-endian bytes at `dst`
+ *                   -- a device BYTE address of any alignment (dst_on_device = 1), or host memory (0: through the context's stream buffer).  zero_replacement:
+ *                   NULL, or a HOST pointer to one value of the type that is stored in place of every value equal to zero (the MSST19 raw copy, sz_float_pwr.c:2053-2058).
+ *   szhip_load_be   the inverse (szd_float.c:106-118): n big-endian values at the byte address `src` (device, any alignment; or host) into the device array d_out.
+ *   szhip_fill      n copies of *value (a HOST pointer to one value) into d_out: the decode of a constant stream (szd_float.c:96-104).
+ *   szhip_clamp     protectValueRange (szd_float.c:161-176) on the device array d_data, in place: v < vmin -> vmin, v > vmax -> vmax with the reference's
+ *                   comparisons, so a NaN stays; vmin / vmax are narrowed to the data's type.
+ * Alignment as above: d_src, d_out, d_data are pointers to VALUES (aligned to their element, else SZHIP_ERR_ARG before anything is launched), `dst` / `src` are BYTE
+ * pointers.  The n values are cut at the 16-byte boundaries of the output: whole 16-byte pieces move 16 bytes per lane (the input is read 16 bytes at a time where it is
+ * aligned alike, else value by value), the head and tail value by value; a byte address that is not aligned to the element is written / read byte by byte.  Nothing
+ * in front of or behind the n values is written and the input is never written.  The calls return when their result is complete.
+ * szhip_copy: `bytes` bytes between host and device memory on the context's stream (to_device = 1: dst is device memory), complete on return -- the few header bytes
+ * and scalars the drop-in calls move.
+ */
+int szhip_store_be(szhip_ctx *ctx, int dtype, const void *d_src, size_t n, const void *zero_replacement, unsigned char *dst, int dst_on_device);
+int szhip_load_be(szhip_ctx *ctx, int dtype, const unsigned char *src, int src_on_device, size_t n, void *d_out);
+int szhip_fill(szhip_ctx *ctx, int dtype, const void *value, size_t n, void *d_out);
+int szhip_clamp(szhip_ctx *ctx, int dtype, void *d_data, size_t n, double vmin, double vmax);
+int szhip_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, int to_device);
 
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)

@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     SZ_SCES, SZ_NSCS, sz_params, szhip_stats, szhip_params,
     lib, lib_path, build_library, SZError,
     SZ_Init, SZ_Init_Params, SZ_Finalize, SZ_compress, SZ_compress_args, SZ_decompress, SZ_hip_last_stats,
+    SZ_hip_compress_device, SZ_hip_compress_device_into, SZ_hip_decompress_device,
     SZ_hip_decompress_region, SZ_hip_compress_region, SZ_hip_decompress_into_region, sz_slab_compress, sz_slab_decompress, sz_slab_decompress_region,
     conf_params, HipContext, HipPool, make_meta,
 )

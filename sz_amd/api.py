@@ -179,6 +179,22 @@ def _bind(L):
         L.sz_slab_decompress.restype = ctypes.c_void_p
         L.sz_slab_decompress_region.argtypes = [ctypes.c_void_p, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]
         L.sz_slab_decompress_region.restype = ctypes.c_void_p
+    if hasattr(L, "SZ_hip_compress_device"):
+        L.SZ_hip_compress_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [sz] * 5
+        L.SZ_hip_compress_device.restype = ctypes.c_void_p
+        L.SZ_hip_compress_device_into.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, sz, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_double] + [sz] * 5
+        L.SZ_hip_compress_device_into.restype = ctypes.c_int
+        L.SZ_hip_decompress_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, ctypes.c_void_p] + [sz] * 5
+        L.SZ_hip_decompress_device.restype = ctypes.c_int
+        L.szhip_store_be.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.szhip_store_be.restype = ctypes.c_int
+        L.szhip_load_be.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, ctypes.c_void_p]
+        L.szhip_load_be.restype = ctypes.c_int
+        L.szhip_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_void_p]
+        L.szhip_fill.restype = ctypes.c_int
+        L.szhip_clamp.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_double, ctypes.c_double]
+        L.szhip_clamp.restype = ctypes.c_int
     L.szhost_write_meta.argtypes = [ctypes.POINTER(szhost_meta), ctypes.c_ubyte, ctypes.c_char_p]
     L.szhost_write_meta.restype = sz
     L.free.argtypes = [ctypes.c_void_p]
@@ -306,6 +322,44 @@ def SZ_hip_decompress_into_region(stream, parent, lo, hi):
     c_lo, c_hi = _box(lo, hi)
     if lib().SZ_hip_decompress_into_region(dt, buf, len(stream), parent.ctypes.data, *_dims5(parent.shape), c_lo, c_hi) != SZ_SCES:
         raise SZError("SZ_hip_decompress_into_region failed")
+
+
+def SZ_hip_compress_device(ptr, shape, dtype, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
+    """SZ_compress_args for the array of `shape` / `dtype` at the DEVICE address ptr (include/sz.h): the stream as bytes, byte for byte what SZ_compress_args returns
+    for a host copy of the array.  The array is never copied to the host."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    n = ctypes.c_size_t(0)
+    p = lib().SZ_hip_compress_device(dt, ptr, ctypes.byref(n), errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, *_dims5(shape))
+    if not p:
+        raise SZError("SZ_hip_compress_device returned NULL")
+    out = ctypes.string_at(p, n.value)
+    lib().free(p)
+    return out
+
+
+def SZ_hip_compress_device_into(ptr, shape, dtype, out_ptr, cap, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
+    """The same stream into the caller's DEVICE buffer of `cap` bytes at out_ptr (any alignment); returns its length.  Raises when the library refuses: a capacity
+    below the stream's length, or a configuration whose szMode is not SZ_BEST_SPEED (the reason is printed by the library)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    n = ctypes.c_size_t(0)
+    rc = lib().SZ_hip_compress_device_into(dt, ptr, out_ptr, cap, ctypes.byref(n), errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, *_dims5(shape))
+    if rc != SZ_SCES:
+        raise SZError(f"SZ_hip_compress_device_into failed ({rc})")
+    return n.value
+
+
+def SZ_hip_decompress_device(stream_or_ptr, on_device, length, out_ptr, shape, dtype):
+    """SZ_decompress into the DEVICE array at out_ptr (include/sz.h).  The stream: a bytes object (on_device = False) or a device address (on_device = True) of
+    `length` bytes.  Exactly prod(shape) values are written."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    if on_device:
+        src = stream_or_ptr
+    else:
+        keep = ctypes.create_string_buffer(bytes(stream_or_ptr), length)
+        src = ctypes.addressof(keep)
+    rc = lib().SZ_hip_decompress_device(dt, src, 1 if on_device else 0, length, out_ptr, *_dims5(shape))
+    if rc != SZ_SCES:
+        raise SZError(f"SZ_hip_decompress_device failed ({rc})")
 
 
 def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
@@ -593,6 +647,34 @@ class HipContext:
                                       int(pitches[0]), int(pitches[1]))
         if rc:
             self._err(rc, "szhip_scatter_view")
+
+    def store_be(self, src_ptr, n, dtype, dst_ptr, dst_on_device=True, zero_replacement=None):
+        """szhip_store_be: the n values of the device array at src_ptr as big-endian bytes at dst_ptr (a device byte address of any alignment, or host memory);
+        zero_replacement: a value stored in place of every value equal to zero."""
+        T = np.dtype(dtype)
+        z = None if zero_replacement is None else np.array([zero_replacement], dtype=T)
+        rc = lib().szhip_store_be(self._h, 0 if T == np.float32 else 1, src_ptr, n, None if z is None else z.ctypes.data, dst_ptr, int(dst_on_device))
+        if rc:
+            self._err(rc, "szhip_store_be")
+
+    def load_be(self, src_ptr, src_on_device, n, dtype, out_ptr):
+        """szhip_load_be: n big-endian values at the byte address src_ptr (device, any alignment; or host) into the device array at out_ptr."""
+        rc = lib().szhip_load_be(self._h, 0 if np.dtype(dtype) == np.float32 else 1, src_ptr, int(src_on_device), n, out_ptr)
+        if rc:
+            self._err(rc, "szhip_load_be")
+
+    def fill(self, value, n, dtype, out_ptr):
+        """szhip_fill: n copies of `value` into the device array at out_ptr."""
+        v = np.array([value], dtype=np.dtype(dtype))
+        rc = lib().szhip_fill(self._h, 0 if v.dtype == np.float32 else 1, v.ctypes.data, n, out_ptr)
+        if rc:
+            self._err(rc, "szhip_fill")
+
+    def clamp(self, ptr, n, dtype, vmin, vmax):
+        """szhip_clamp: the device array at ptr clamped to [vmin, vmax] in place with the reference's comparisons (a NaN stays)."""
+        rc = lib().szhip_clamp(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ptr, n, float(vmin), float(vmax))
+        if rc:
+            self._err(rc, "szhip_clamp")
 
     def huff_book(self, hist, on_device=False, intervals=None, tree_cap=None):
         """The device's code book of a histogram (szhip_huff_book; k_huff_book alone).  hist: a numpy uint32 array, or a device pointer with `intervals`.

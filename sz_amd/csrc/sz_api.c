@@ -366,6 +366,39 @@ static void set_range(int dataType, double vmin, double vmax, double *valueRange
     } else { *valueRangeSize = vmax - vmin; confparams_cpr->dmin = vmin; confparams_cpr->dmax = vmin + *valueRangeSize; }
 }
 
+/* Where a compress call's array lies and where its stream goes.  The host entry points: {0, NULL, 0} -- a host array, the stream returned as malloc'd host memory.
+ * SZ_hip_compress_device: dev = 1, the array is device memory and is never copied to the host: the range comes from szhip_minmax as always, the first value of a
+ * constant array and the values of a tiny one through szhip_copy, the raw copy through szhip_store_be.  SZ_hip_compress_device_into: d_stream / cap too -- the
+ * stream goes to that DEVICE buffer (the layer's out_on_device = 2, szhip_store_be, or a small upload) and nothing is returned but its length; szMode is
+ * SZ_BEST_SPEED there, so no stream has to pass the host's lossless stage.  d_stream implies dev. */
+typedef struct { int dev; unsigned char *d_stream; size_t cap; } cpr_io;
+static const cpr_io g_host_io = {0, NULL, 0};
+static szhip_ctx *get_ctx(void);
+static void drop_stream(const cpr_io *io, unsigned char *tmp) { if (!io->d_stream) free(tmp); }
+/* a finished host stream `tmp` (owned) to the call's target: handed out, or uploaded into the caller's device buffer */
+static int stream_to_target(const cpr_io *io, unsigned char *tmp, size_t n, unsigned char **newByteData, size_t *outSize, int status)
+{
+    if (!io->d_stream) { *newByteData = tmp; *outSize = n; return status; }
+    szhip_ctx *ctx = get_ctx();
+    int rc = ctx ? SZ_SCES : SZ_NSCS;
+    if (ctx && n > io->cap) { printf("Error: SZ_hip_compress_device_into: the stream takes %zu bytes, the buffer holds %zu.\n", n, io->cap); rc = SZ_NSCS; }
+    else if (ctx && szhip_copy(ctx, io->d_stream, tmp, n, 1) != SZHIP_OK) { printf("Error: szhip_copy failed: %s\n", szhip_last_error(ctx)); rc = SZ_NSCS; }
+    free(tmp);
+    *outSize = rc == SZ_SCES ? n : 0;
+    return rc == SZ_SCES ? status : rc;
+}
+/* a layer call into the caller's device buffer that failed because the stream outgrew the capacity (deliver_stream, szhip_steps.inc): nothing outside the buffer was
+ * written and the context stays usable */
+static int stream_outgrew(const cpr_io *io, szhip_ctx *ctx, int rc)
+{
+    return io->d_stream && rc == SZHIP_ERR_ARG && strstr(szhip_last_error(ctx), "device buffer too small") != NULL;
+}
+static int no_room(const cpr_io *io)
+{
+    printf("Error: SZ_hip_compress_device_into: the stream does not fit the buffer of %zu bytes.\n", io->cap);
+    return SZ_NSCS;
+}
+
 /* SZ_compress_args_float_withinRange, sz_float.c:2728: header + the first value */
 static int constant_stream(int dataType, const szhost_meta *m, const void *oriData, size_t dataLength, unsigned char **newByteData, size_t *outSize)
 {
@@ -383,6 +416,69 @@ static int constant_stream(int dataType, const szhost_meta *m, const void *oriDa
     if (dataType == SZ_FLOAT) szhost_put_f32be(o + 4 + meta_len + 8, ((const float *)oriData)[0]);
     else szhost_put_f64be(o + 4 + meta_len + 8, ((const double *)oriData)[0]);
     *newByteData = o; *outSize = tot;
+    return SZ_SCES;
+}
+
+/* the constant stream to the call's target; of a device array only the first value comes to the host */
+static int constant_out(int dataType, const szhost_meta *m, const void *oriData, size_t dataLength, const cpr_io *io, unsigned char **newByteData, size_t *outSize, int status)
+{
+    double first = 0;                                              /* (room for one value of either type, aligned) */
+    if (io->dev) {
+        szhip_ctx *ctx = get_ctx();
+        if (!ctx || szhip_copy(ctx, &first, oriData, dataType == SZ_FLOAT ? 4 : 8, 0) != SZHIP_OK) return SZ_NSCS;
+        oriData = &first;
+    }
+    unsigned char *o = NULL; size_t n = 0;
+    int crc = constant_stream(dataType, m, oriData, dataLength, &o, &n);
+    if (crc != SZ_SCES) return crc;
+    return stream_to_target(io, o, n, newByteData, outSize, status);
+}
+
+static inline size_t ori_at(size_t i);
+/* SZ_compress_args_float_StoreOriData, sz_float.c:526-552: version, flag byte 80, parameter bytes, the length, every value big-endian.  `zero`: NULL, or the value
+ * stored in place of the values equal to zero (the PW_REL callers).  A host array is copied by the host, value by value; a device array by szhip_store_be -- into
+ * host memory, or straight into the caller's device buffer behind the uploaded header.  *o: the malloc'd stream (host target) or io->d_stream. */
+static int raw_copy(int dataType, const unsigned char *meta, const void *oriData, size_t dataLength, const void *zero, const cpr_io *io, unsigned char **o_out, size_t *tot_out)
+{
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8, meta_len = dataType == SZ_FLOAT ? MetaDataByteLength : MetaDataByteLength_double;
+    const size_t head = 4 + meta_len + 8, tot = 3 + meta_len + 8 + 1 + esz * dataLength;
+    unsigned char hdr[4 + MetaDataByteLength_double + 8];
+    memcpy(hdr, meta, 4 + meta_len);
+    hdr[3] = 80;
+    szhost_put_u64be(hdr + 4 + meta_len, dataLength);
+    if (io->d_stream) {
+        szhip_ctx *ctx = get_ctx();
+        if (!ctx) return SZ_NSCS;
+        if (tot > io->cap) { printf("Error: SZ_hip_compress_device_into: the stream takes %zu bytes, the buffer holds %zu.\n", tot, io->cap); return SZ_NSCS; }
+        if (szhip_copy(ctx, io->d_stream, hdr, head, 1) != SZHIP_OK ||
+            szhip_store_be(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, dataLength, zero, io->d_stream + head, 1) != SZHIP_OK) {
+            printf("Error: szhip_store_be failed: %s\n", szhip_last_error(ctx)); return SZ_NSCS;
+        }
+        *o_out = io->d_stream; *tot_out = tot;
+        return SZ_SCES;
+    }
+    unsigned char *o = (unsigned char *)malloc(tot);
+    if (!o) { printf("Error: out of memory (%zu bytes for the raw copy)\n", tot); return SZ_NSCS; }
+    memcpy(o, hdr, head);
+    unsigned char *q = o + head;
+    if (io->dev) {
+        szhip_ctx *ctx = get_ctx();
+        if (!ctx || szhip_store_be(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, dataLength, zero, q, 0) != SZHIP_OK) {
+            printf("Error: szhip_store_be failed: %s\n", ctx ? szhip_last_error(ctx) : "no device"); free(o); return SZ_NSCS;
+        }
+    } else if (zero) {
+        const float zf = dataType == SZ_FLOAT ? *(const float *)zero : 0.0f;
+        const double zd = dataType == SZ_FLOAT ? 0.0 : *(const double *)zero;
+        for (size_t i = 0; i < dataLength; i++, q += esz) {
+            if (dataType == SZ_FLOAT) { const float v = ((float *)oriData)[ori_at(i)]; szhost_put_f32be(q, v == 0 ? zf : v); }
+            else { const double v = ((double *)oriData)[ori_at(i)]; szhost_put_f64be(q, v == 0 ? zd : v); }
+        }
+    } else {
+        for (size_t i = 0; i < dataLength; i++, q += esz) {
+            if (dataType == SZ_FLOAT) szhost_put_f32be(q, ((float *)oriData)[ori_at(i)]); else szhost_put_f64be(q, ((double *)oriData)[ori_at(i)]);
+        }
+    }
+    *o_out = o; *tot_out = tot;
     return SZ_SCES;
 }
 
@@ -411,6 +507,12 @@ static int finish_lossless(unsigned char *tmp, size_t tmpSize, unsigned char **n
     } else { printf("Error: Wrong setting of confparams_cpr->szMode in the compression.\n"); free(tmp); return SZ_MERR; }
     return status;
 }
+/* ... of a stream that lies in the caller's device buffer (szMode is SZ_BEST_SPEED there): only its length goes out */
+static int finish_stream(const cpr_io *io, unsigned char *tmp, size_t tmpSize, unsigned char **newByteData, size_t *outSize, int status)
+{
+    if (io->d_stream) { *newByteData = NULL; *outSize = tmpSize; return status; }
+    return finish_lossless(tmp, tmpSize, newByteData, outSize, status);
+}
 
 /* ---- compression ---- */
 /* SZ_hip_compress_region: compress_fp reads a sub-box of a larger host array.  t_view = {rows per plane, values per row, pitch0, pitch1} of the sub-box whose first value
@@ -423,15 +525,17 @@ static inline size_t ori_at(size_t i)
     const size_t plane = t_view[0] * t_view[1], k = i / plane, rem = i - k * plane, r = rem / t_view[1];
     return k * t_view[2] + r * t_view[3] + (rem - r * t_view[1]);
 }
-static unsigned char *omp_compress_at(int dataType, const void *data, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size);
+static unsigned char *omp_compress_at(int dataType, const void *data, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size,
+                                      unsigned char mark, const cpr_io *io);
 static int omp_pick_threads(size_t r1, size_t r2, size_t r3);
 #define SZH_OMP_MARK 0x4f         /* stream byte 19 (parameter byte 15, which convertSZParamsToBytes never writes: ByteToolkit.c:874-972) of an OpenMP container that
                                    * SZ_compress_args wrote under SZ_HIP_MODE=omp: how SZ_decompress of THIS library tells it from an SZ 2.1 stream (same flag byte) */
 static int compress_fp(int dataType, int withRegression, unsigned char **newByteData, void *oriData,
                        size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, size_t *outSize,
-                       int errBoundMode, double absErr_Bound, double relBoundRatio, double pwRelBoundRatio)
+                       int errBoundMode, double absErr_Bound, double relBoundRatio, double pwRelBoundRatio, const cpr_io *io)
 {
     const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    const int ood = io->d_stream ? 2 : 0;                          /* the layer's out_on_device */
     const size_t meta_len = dataType == SZ_FLOAT ? MetaDataByteLength : MetaDataByteLength_double;
     confparams_cpr->dataType = dataType;
     confparams_cpr->errorBoundMode = errBoundMode;
@@ -439,6 +543,12 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     *newByteData = NULL;
     size_t dataLength = computeDataLength(r5, r4, r3, r2, r1);
     if (dataLength <= MIN_NUM_OF_ELEMENTS) { /* SZ_skip_compress_float, sz_float.c:37 */
+        if (io->dev) {                                             /* the few values come to the host */
+            unsigned char *few = (unsigned char *)malloc(dataLength * esz != 0 ? dataLength * esz : 1);
+            szhip_ctx *c = get_ctx();
+            if (!few || !c || szhip_copy(c, few, oriData, dataLength * esz, 0) != SZHIP_OK) { free(few); return SZ_NSCS; }
+            return stream_to_target(io, few, dataLength * esz, newByteData, outSize, SZ_SCES);
+        }
         *outSize = dataLength * esz;
         *newByteData = (unsigned char *)malloc(dataLength * esz != 0 ? dataLength * esz : 1);
         if (!t_view) memcpy(*newByteData, oriData, dataLength * esz);
@@ -451,7 +561,8 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     if (t_view) {                                                  /* only the sub-box's rows go to the device */
         int prc = szhip_pack_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, 0, dataLength / (t_view[0] * t_view[1]), t_view[0], t_view[1], t_view[2], t_view[3], &d_in);   /* (the sub-box's own extents: r3 .. r1 may be folded) */
         if (prc != SZHIP_OK) { printf("Error: szhip_pack_view failed (%d): %s\n", prc, szhip_last_error(ctx)); return SZ_NSCS; }
-    } else
+    } else if (io->dev) d_in = oriData;                            /* read where it lies */
+    else
     if (szhip_stage_input(ctx, oriData, dataLength * esz, &d_in) != SZHIP_OK) return SZ_NSCS;
     /* The value range (computeRangeSize_float, sz_float.c:2845).  With an absolute bound on the SZ 2.1 path nothing before the
      * quantiser depends on it -- it only goes into the header and decides the constant-data case -- so it is taken from the library's
@@ -494,10 +605,8 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     szhost_meta m; fill_meta(&m, confparams_cpr, dataType);
     unsigned char meta[4 + MetaDataByteLength_double];
 
-    if (!fuse_range && valueRangeSize <= realPrecision) {
-        int crc = constant_stream(dataType, &m, oriData, dataLength, newByteData, outSize);
-        return crc == SZ_SCES ? status : crc;
-    }
+    if (!fuse_range && valueRangeSize <= realPrecision)
+        return constant_out(dataType, &m, oriData, dataLength, io, newByteData, outSize, status);
 
     int dim = computeDimension(r5, r4, r3, r2, r1);
     if (dim == 5) { printf("Error: doesn't support 5 dimensions for now.\n"); return SZ_DERR; }
@@ -555,31 +664,27 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
          * fixed quantization_intervals overwrites while leaving maxRangeRadius alone (conf.c:193-197) */
         php.max_quant_intervals = exe_params->optQuantMode == 1 ? confparams_cpr->maxRangeRadius * 2 : confparams_cpr->max_quant_intervals;
         php.quantization_intervals = exe_params->optQuantMode == 1 ? 0 : (unsigned)exe_params->intvCapacity;
-        unsigned char *ptmp = NULL; size_t ptmpSize = 0;
-        int crc = szhip_compress_sz14_pwr(ctx, dt, d_log, 1, dim == 4 ? r4 * r3 : r3, r2, r1, rp, lrange, lmedian, &php, meta, 4 + meta_len, &pw, 0,
+        unsigned char *ptmp = io->d_stream; size_t ptmpSize = io->cap;
+        int crc = szhip_compress_sz14_pwr(ctx, dt, d_log, 1, dim == 4 ? r4 * r3 : r3, r2, r1, rp, lrange, lmedian, &php, meta, 4 + meta_len, &pw, ood,
                                           &ptmp, &ptmpSize, &g_last_stats);
         free(blob);
-        if (crc != SZHIP_OK) { printf("Error: szhip_compress_sz14_pwr failed (%d): %s\n", crc, szhip_last_error(ctx)); return SZ_NSCS; }
+        const size_t raw_tot = 3 + meta_len + 8 + 1 + esz * dataLength;
+        /* a stream that outgrew a buffer which holds the raw copy is beyond the raw-store rule below; one that outgrew a smaller buffer fits in neither form */
+        const int outgrew = stream_outgrew(io, ctx, crc);
+        if (outgrew && io->cap < raw_tot) return no_room(io);
+        if (crc != SZHIP_OK && !outgrew) { printf("Error: szhip_compress_sz14_pwr failed (%d): %s\n", crc, szhip_last_error(ctx)); return SZ_NSCS; }
         if (exe_params->optQuantMode == 1) { exe_params->intvCapacity = (int)g_last_stats.intervals; exe_params->intvRadius = exe_params->intvCapacity / 2; }
-        if (ptmpSize > 3 + meta_len + exe_params->SZ_SIZE_TYPE + 1 + esz * dataLength) {     /* sz_float_pwr.c:1971 */
-            size_t tot = 3 + meta_len + 8 + 1 + esz * dataLength;
-            unsigned char *o = (unsigned char *)malloc(tot);
-            if (!o) { printf("Error: out of memory (%zu bytes for the raw copy)\n", tot); free(ptmp); return SZ_NSCS; }
-            memcpy(o, meta, 4 + meta_len);
-            o[3] = 80;
-            szhost_put_u64be(o + 4 + meta_len, dataLength);
-            unsigned char *q = o + 4 + meta_len + 8;
+        if (outgrew || ptmpSize > 3 + meta_len + exe_params->SZ_SIZE_TYPE + 1 + esz * dataLength) {     /* sz_float_pwr.c:1971 */
             /* the reference's MSST19 wrappers store the array whose zeros they have overwritten (sz_float_pwr.c:2053-2058, :2077): the raw copy
              * holds nearZero * (1+ratio)^-3.0001 in their place */
             const float zf = msst19 ? (float)msst_near_zero * (float)pow(1 + pwRelBoundRatio, -3.0001) : 0.0f;
             const double zd = msst19 ? msst_near_zero * pow(1 + pwRelBoundRatio, -3.0001) : 0.0;
-            for (size_t i = 0; i < dataLength; i++, q += esz) {
-                if (dataType == SZ_FLOAT) { const float v = ((float *)oriData)[ori_at(i)]; szhost_put_f32be(q, v == 0 ? zf : v); }
-                else { const double v = ((double *)oriData)[ori_at(i)]; szhost_put_f64be(q, v == 0 ? zd : v); }
-            }
-            free(ptmp); ptmp = o; ptmpSize = tot;
+            unsigned char *o = NULL; size_t tot = 0;
+            int rrc = raw_copy(dataType, meta, oriData, dataLength, dataType == SZ_FLOAT ? (const void *)&zf : (const void *)&zd, io, &o, &tot);
+            if (rrc != SZ_SCES) { drop_stream(io, ptmp); return rrc; }
+            drop_stream(io, ptmp); ptmp = o; ptmpSize = tot;
         }
-        return finish_lossless(ptmp, ptmpSize, newByteData, outSize, status);
+        return finish_stream(io, ptmp, ptmpSize, newByteData, outSize, status);
     }
     /* the SZ 1.4 path (sz_float.c:2938,2978): 2-D and 3-D in this build; a 1-D array takes its container whatever the switch says (:2885-2900) */
     const int sz14 = withRegression == SZ_NO_REGRESSION || dim == 1;
@@ -601,10 +706,10 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
         }
         if (valueRangeSize > realPrecision) {
             size_t osz = 0;
-            unsigned char *o = omp_compress_at(dataType, d_in, 1, r3, r2, r1, realPrecision, &osz);
+            unsigned char *o = omp_compress_at(dataType, d_in, 1, r3, r2, r1, realPrecision, &osz, SZH_OMP_MARK, io);
             if (!o) return SZ_NSCS;
-            o[19] = SZH_OMP_MARK;
-            return finish_lossless(o, osz, newByteData, outSize, status);
+            if (!io->d_stream) o[19] = SZH_OMP_MARK;               /* (a stream in the caller's device buffer carries the mark in its parameter bytes) */
+            return finish_stream(io, o, osz, newByteData, outSize, status);
         }
     }
     unsigned char flags = sz14 ? 0x40 : (0x80 | 0x40);        /* TightDataPointStorageF.c:600-611 / sz_float.c:7396 */
@@ -616,61 +721,67 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     hp.max_quant_intervals = exe_params->optQuantMode == 1 ? confparams_cpr->maxRangeRadius * 2 : confparams_cpr->max_quant_intervals;   /* as above */
     hp.quantization_intervals = exe_params->optQuantMode == 1 ? 0 : (unsigned)exe_params->intvCapacity;
     size_t s0 = dim == 4 ? r4 * r3 : r3;   /* 2-D: r3 == 0 tells the HIP layer so (sz_float.c:2942 passes (r2, r1)) */
-    unsigned char *tmp = NULL; size_t tmpSize = 0;
+    unsigned char *tmp = io->d_stream; size_t tmpSize = io->cap;
     int rc;
     if (sz14) {   /* medianValue = min + valueRangeSize/2 in the data's type (dataCompression.c:117) */
         double median = dataType == SZ_FLOAT ? (double)(float)((float)vmin + (float)valueRangeSize / 2) : vmin + valueRangeSize / 2;
         rc = szhip_compress_sz14(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, d_in, 1, r3, r2, r1, realPrecision, valueRangeSize, median,   /* r3 == 0: 2-D; r3 == r2 == 0: 1-D */
-                                 &hp, meta, 4 + meta_len, 0, &tmp, &tmpSize, &g_last_stats);
+                                 &hp, meta, 4 + meta_len, ood, &tmp, &tmpSize, &g_last_stats);
     } else
         rc = szhip_compress(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, d_in, 1, s0, r2, r1, realPrecision, &hp,
-                            meta, 4 + meta_len, 0, &tmp, &tmpSize, &g_last_stats);
+                            meta, 4 + meta_len, ood, &tmp, &tmpSize, &g_last_stats);
+    const size_t raw_tot = 3 + meta_len + 8 + 1 + esz * dataLength;
+    const int outgrew = stream_outgrew(io, ctx, rc);               /* (as on the PW_REL path above) */
     if (rc != SZHIP_OK && rc != SZHIP_CONSTANT && fuse_range) {
         /* the fused pass failed: a constant array must still come out as the reference's constant stream -- settle that with the plain range scan */
         if (szhip_minmax(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, d_in, 1, dataLength, &vmin, &vmax) == SZHIP_OK) {
             set_range(dataType, vmin, vmax, &valueRangeSize);
             if (valueRangeSize <= realPrecision) {
                 fill_meta(&m, confparams_cpr, dataType);
-                int crc = constant_stream(dataType, &m, oriData, dataLength, newByteData, outSize);
-                return crc == SZ_SCES ? status : crc;
+                return constant_out(dataType, &m, oriData, dataLength, io, newByteData, outSize, status);
             }
         }
     }
-    if (rc != SZHIP_OK && rc != SZHIP_CONSTANT) { printf("Error: szhip_compress failed (%d): %s\n", rc, szhip_last_error(ctx)); return SZ_NSCS; }
-    if (fuse_range) {   /* the range arrived with the stream: record it where the reference's callers look for it, and settle the constant case */
-        set_range(dataType, g_last_stats.vmin, g_last_stats.vmax, &valueRangeSize);
-        fill_meta(&m, confparams_cpr, dataType);
-        szhost_write_meta(&m, flags, meta);
-        if (rc == SZHIP_CONSTANT || valueRangeSize <= realPrecision) {   /* (the HIP layer stops after its fit pass when it sees this: SZHIP_CONSTANT) */
-            free(tmp);
-            int crc = constant_stream(dataType, &m, oriData, dataLength, newByteData, outSize);
-            return crc == SZ_SCES ? status : crc;
+    if (outgrew) {
+        if (io->cap < raw_tot) return no_room(io);
+        if (fuse_range) {                                          /* (the raw copy's header records the range, which did not arrive with a stream) */
+            if (szhip_minmax(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, d_in, 1, dataLength, &vmin, &vmax) != SZHIP_OK) return SZ_NSCS;
+            set_range(dataType, vmin, vmax, &valueRangeSize);
+            fill_meta(&m, confparams_cpr, dataType);
+            szhost_write_meta(&m, flags, meta);
         }
+    } else {
+        if (rc != SZHIP_OK && rc != SZHIP_CONSTANT) { printf("Error: szhip_compress failed (%d): %s\n", rc, szhip_last_error(ctx)); return SZ_NSCS; }
+        if (fuse_range) {   /* the range arrived with the stream: record it where the reference's callers look for it, and settle the constant case */
+            set_range(dataType, g_last_stats.vmin, g_last_stats.vmax, &valueRangeSize);
+            fill_meta(&m, confparams_cpr, dataType);
+            szhost_write_meta(&m, flags, meta);
+            if (rc == SZHIP_CONSTANT || valueRangeSize <= realPrecision) {   /* (the HIP layer stops after its fit pass when it sees this: SZHIP_CONSTANT) */
+                drop_stream(io, tmp);
+                return constant_out(dataType, &m, oriData, dataLength, io, newByteData, outSize, status);
+            }
+        }
+        if (exe_params->optQuantMode == 1) { exe_params->intvCapacity = (int)g_last_stats.intervals; exe_params->intvRadius = exe_params->intvCapacity / 2; } /* updateQuantizationInfo */
     }
-    if (exe_params->optQuantMode == 1) { exe_params->intvCapacity = (int)g_last_stats.intervals; exe_params->intvRadius = exe_params->intvCapacity / 2; } /* updateQuantizationInfo */
 
     /* SZ_compress_args_float_StoreOriData, sz_float.c:526; '>=' on the SZ 2.1 path (:2975) and at the 1-D call site (:2908),
      * '>' on the 2-D/3-D SZ 1.4 path (:1469) */
-    if (tmpSize + (sz14 && dim != 1 ? 0 : 1) > dataLength * esz + 3 + meta_len + exe_params->SZ_SIZE_TYPE + 1) {
-        size_t tot = 3 + meta_len + 8 + 1 + esz * dataLength;
-        unsigned char *o = (unsigned char *)malloc(tot);
-        if (!o) { printf("Error: out of memory (%zu bytes for the raw copy)\n", tot); free(tmp); return SZ_NSCS; }
-        memcpy(o, meta, 4 + meta_len);
-        o[3] = 80;
-        szhost_put_u64be(o + 4 + meta_len, dataLength);
-        unsigned char *q = o + 4 + meta_len + 8;
-        for (size_t i = 0; i < dataLength; i++, q += esz) {
-            if (dataType == SZ_FLOAT) szhost_put_f32be(q, ((float *)oriData)[ori_at(i)]); else szhost_put_f64be(q, ((double *)oriData)[ori_at(i)]);
-        }
-        free(tmp); tmp = o; tmpSize = tot;
+    if (outgrew || tmpSize + (sz14 && dim != 1 ? 0 : 1) > dataLength * esz + 3 + meta_len + exe_params->SZ_SIZE_TYPE + 1) {
+        unsigned char *o = NULL; size_t tot = 0;
+        int rrc = raw_copy(dataType, meta, oriData, dataLength, NULL, io, &o, &tot);
+        drop_stream(io, tmp);
+        if (rrc != SZ_SCES) return rrc;
+        tmp = o; tmpSize = tot;
     }
 
-    return finish_lossless(tmp, tmpSize, newByteData, outSize, status);
+    return finish_stream(io, tmp, tmpSize, newByteData, outSize, status);
 }
 
-unsigned char *SZ_compress_args(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound,
-                                double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+/* SZ_compress_args for an array on the host or on the device, the stream returned or written to the caller's device buffer (cpr_io); *status: compress_fp's */
+static unsigned char *compress_args_io(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound, double relBoundRatio, double pwrBoundRatio,
+                                       size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const cpr_io *io, int *status)
 {
+    *status = SZ_NSCS;
     if (confparams_cpr == NULL) SZ_Init(NULL);
     else if (exe_params == NULL) exe_params = (sz_exedata *)calloc(1, sizeof(sz_exedata));
     if (exe_params->intvCapacity == 0) {
@@ -684,12 +795,49 @@ unsigned char *SZ_compress_args(int dataType, void *data, size_t *outSize, int e
     confparams_cpr->dataType = dataType;
     if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE) {
         unsigned char *newByteData = NULL;
-        compress_fp(dataType, confparams_cpr->withRegression, &newByteData, data, _r[4], _r[3], _r[2], _r[1], _r[0], outSize,
-                    errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio);
+        *status = compress_fp(dataType, confparams_cpr->withRegression, &newByteData, data, _r[4], _r[3], _r[2], _r[1], _r[0], outSize,
+                              errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, io);
         return newByteData;
     }
     printf("Error: the MI355X build handles SZ_FLOAT and SZ_DOUBLE; integer types are outside its scope.\n");
     return NULL;
+}
+
+unsigned char *SZ_compress_args(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound,
+                                double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    int status;
+    return compress_args_io(dataType, data, outSize, errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, r5, r4, r3, r2, r1, &g_host_io, &status);
+}
+
+/* ---- the same for an array that is already on the GPU (include/sz.h) ---- */
+unsigned char *SZ_hip_compress_device(int dataType, const void *d_data, size_t *outSize, int errBoundMode, double absErrBound,
+                                      double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    if (!d_data || !outSize) { printf("Error: SZ_hip_compress_device: null argument.\n"); return NULL; }
+    const cpr_io io = {1, NULL, 0};
+    int status;
+    return compress_args_io(dataType, (void *)d_data, outSize, errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, r5, r4, r3, r2, r1, &io, &status);
+}
+
+int SZ_hip_compress_device_into(int dataType, const void *d_data, unsigned char *d_stream, size_t capacity, size_t *outSize, int errBoundMode,
+                                double absErrBound, double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    if (!d_data || !d_stream || !outSize) { printf("Error: SZ_hip_compress_device_into: null argument.\n"); return SZ_NSCS; }
+    *outSize = 0;
+    if (confparams_cpr == NULL) SZ_Init(NULL);
+    if (confparams_cpr->szMode != SZ_BEST_SPEED) {
+        printf("Error: SZ_hip_compress_device_into writes the stream of szMode = SZ_BEST_SPEED only: the lossless stage of the other modes is host code "
+               "(SZ_hip_compress_device returns such a stream).\n");
+        return SZ_NSCS;
+    }
+    const cpr_io io = {1, d_stream, capacity};
+    int status;
+    size_t n = 0;
+    (void)compress_args_io(dataType, (void *)d_data, &n, errBoundMode, absErrBound, relBoundRatio, pwrBoundRatio, r5, r4, r3, r2, r1, &io, &status);
+    if (status != SZ_SCES) return status;
+    *outSize = n;
+    return SZ_SCES;
 }
 
 int SZ_compress_args2(int dataType, void *data, unsigned char *compressed_bytes, size_t *outSize, int errBoundMode, double absErrBound,
@@ -814,7 +962,7 @@ void *detransposeData(void *data, int dataType, size_t r5, size_t r4, size_t r3,
     return o;
 }
 
-static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data, size_t avail);
+static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data, size_t avail, void *d_out);
 /* the stream behind its lossless stage (zstd or gzip; none: the stream itself): *sz, *szlen, *owned = 1 when *sz was malloc'd here.  0 with a printed reason on failure */
 static int unwrap_lossless(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t dataLength, unsigned char **sz_out, size_t *szlen_out, int *owned_out)
 {
@@ -861,15 +1009,57 @@ static int unwrap_lossless(int dataType, unsigned char *cmpBytes, size_t cmpSize
     return 1;
 }
 
-static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+/* what a device-resident stream brings to the host for the header reads below: its first bytes -- version, flag byte, parameter bytes, the length, the fixed
+ * fields of a PW_REL container, the values of a constant or tiny stream */
+#define DEV_PREFIX 256
+/* SZ_decompress (d_out == NULL: the decoded array is returned as malloc'd host memory), and SZ_hip_decompress_device: the array is decoded into the DEVICE array
+ * d_out (returned on success) -- the raw, constant and clamp steps by szhip_load_be / szhip_fill / szhip_clamp -- from a stream on the host or (bytes_on_device) on
+ * the device.  Of an unwrapped device stream the prefix above and the sign bytes of a PW_REL container come to the host, the payload is read where it lies; one that
+ * the zstd / gzip stage wrapped is brought down whole, since that stage is host code. */
+static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, int bytes_on_device, void *d_out)
 {
     const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
     const size_t meta_len = dataType == SZ_FLOAT ? MetaDataByteLength : MetaDataByteLength_double;
+    const int dtk = dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64;
     size_t dataLength = computeDataLength(r5, r4, r3, r2, r1);
     unsigned char *sz = cmpBytes; size_t szlen = cmpSize; int owned = 0;
+    unsigned char prefix[DEV_PREFIX];
+    unsigned char *whole = NULL;                                   /* a wrapped device stream, brought down */
+    const unsigned char *d_sz = NULL;                              /* the unwrapped stream where it lies on the device */
 
-    if (!unwrap_lossless(dataType, cmpBytes, cmpSize, dataLength, &sz, &szlen, &owned)) return NULL;
+    if (bytes_on_device) {
+        szhip_ctx *ctx = get_ctx();
+        const size_t pl = cmpSize < DEV_PREFIX ? cmpSize : DEV_PREFIX;
+        if (!ctx) return NULL;
+        memset(prefix, 0, sizeof(prefix));
+        if (szhip_copy(ctx, prefix, cmpBytes, pl, 0) != SZHIP_OK) { printf("Error: szhip_copy failed: %s\n", szhip_last_error(ctx)); return NULL; }
+        /* the sniff of unwrap_lossless on the prefix (a zstd frame header has at most 18 bytes) */
+        const size_t cbase = (dataType == SZ_FLOAT ? 8 : 12) + meta_len;
+        int wrapped = 0;
+        if (cmpSize != cbase + 4 && cmpSize != cbase + 8)
+            wrapped = (pl >= 4 && zstd_load() && g_zstd.fcs(prefix, pl) != (unsigned long long)-2) || (pl >= 4 && prefix[0] == 0x28 && prefix[1] == 0xB5 && prefix[2] == 0x2F && prefix[3] == 0xFD) ||
+                      (pl >= 2 && is_zlib_format(prefix[0], prefix[1]));
+        if (wrapped) {
+            whole = (unsigned char *)malloc(cmpSize);
+            if (!whole) { printf("Error: out of memory.\n"); return NULL; }
+            if (szhip_copy(ctx, whole, cmpBytes, cmpSize, 0) != SZHIP_OK) { printf("Error: szhip_copy failed: %s\n", szhip_last_error(ctx)); free(whole); return NULL; }
+            cmpBytes = whole; bytes_on_device = 0;
+        } else {
+            d_sz = cmpBytes; sz = prefix;
+            confparams_dec->losslessCompressor = -1; confparams_dec->szMode = SZ_BEST_SPEED;    /* (what unwrap_lossless records for an unwrapped stream) */
+        }
+    }
+    if (!d_sz && !unwrap_lossless(dataType, cmpBytes, cmpSize, dataLength, &sz, &szlen, &owned)) { free(whole); return NULL; }
+    if (whole) { if (owned) free(whole); else owned = 1; }         /* from here on `sz` is the only host copy to release */
     if (dataLength <= MIN_NUM_OF_ELEMENTS) { /* raw copy written by SZ_skip_compress */
+        if (d_out) {
+            szhip_ctx *ctx = get_ctx();
+            int good = ctx && szlen >= dataLength * esz;           /* (the values of a device stream are in the prefix: 20 x 8 bytes at most) */
+            if (ctx && !good) printf("Error: compressed stream too short.\n");
+            if (good && dataLength && szhip_copy(ctx, d_out, sz, dataLength * esz, 1) != SZHIP_OK) { printf("Error: szhip_copy failed: %s\n", szhip_last_error(ctx)); good = 0; }
+            if (owned) free(sz);
+            return good ? d_out : NULL;
+        }
         void *o = malloc(dataLength * esz != 0 ? dataLength * esz : 1);
         if (!o) { printf("Error: out of memory\n"); if (owned) free(sz); return NULL; }
         memcpy(o, sz, dataLength * esz);
@@ -892,27 +1082,46 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
     confparams_dec->sol_ID = sz[4 + 14];
     const size_t st = exe_params->SZ_SIZE_TYPE;
     const unsigned char *body = sz + 4 + meta_len + st;
-    void *out = malloc(dataLength * esz);
-    hint_huge_pages(out, dataLength * esz);
+    const int ood = d_out ? 1 : 0;                                 /* the layer's out_on_device */
+    const unsigned char *lsz = d_sz ? d_sz : sz;                   /* the stream as the layer takes it, with stream_on_device = (d_sz != NULL) */
+    void *out = d_out ? d_out : malloc(dataLength * esz);
+    if (!d_out) hint_huge_pages(out, dataLength * esz);
     if (!out) { printf("Error: out of memory.\n"); if (owned) free(sz); return NULL; }
     int ok = 1;
     if ((same & 0x80) && !(same & 0x31) && sz[19] == SZH_OMP_MARK && computeDimension(r5, r4, r3, r2, r1) == 3) {
         /* an OpenMP container written by SZ_compress_args of this library under SZ_HIP_MODE=omp (see compress_fp); its body starts behind
          * 4 + MetaDataByteLength bytes for both types (sz_omp.c:221, :733) */
         void *o2 = NULL;
-        free(out);
-        if (szlen >= 4 + (size_t)MetaDataByteLength) omp_decompress(dataType, &o2, r3, r2, r1, sz + 4 + MetaDataByteLength, szlen - 4 - (size_t)MetaDataByteLength);
-        else printf("Error: truncated OpenMP-container stream.\n");
+        if (!d_out) free(out);
+        if (szlen < 4 + (size_t)MetaDataByteLength + 1) printf("Error: truncated OpenMP-container stream.\n");
+        else if (d_sz) {                                           /* the layer walks the tables of a device-resident stream itself (prefixes fetched as it needs them) */
+            szhip_ctx *ctx = get_ctx();
+            const int rc = ctx ? szhip_decompress_omp(ctx, dtk, d_sz + 4 + MetaDataByteLength, 1, szlen - 4 - (size_t)MetaDataByteLength, 0, r3, r2, r1, d_out, 1, &g_last_stats)
+                               : SZHIP_ERR_NODEVICE;
+            if (rc != SZHIP_OK) printf("Error: szhip_decompress_omp failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device");
+            else o2 = d_out;
+        } else omp_decompress(dataType, &o2, r3, r2, r1, sz + 4 + MetaDataByteLength, szlen - 4 - (size_t)MetaDataByteLength, d_out);
         if (owned) free(sz);
         return o2;
     }
     if (same & 0x10) { /* lossless raw copy, big-endian values (szd_float.c:106-118) */
         if (szlen < 4 + meta_len + st + dataLength * esz) ok = 0;
+        else if (d_out) {
+            szhip_ctx *ctx = get_ctx();
+            const int rc = ctx ? szhip_load_be(ctx, dtk, lsz + 4 + meta_len + st, d_sz != NULL, dataLength, d_out) : SZHIP_ERR_NODEVICE;
+            if (rc != SZHIP_OK) { printf("Error: szhip_load_be failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device"); ok = 0; }
+        }
         else for (size_t i = 0; i < dataLength; i++) {
             if (dataType == SZ_FLOAT) ((float *)out)[i] = szhost_get_f32be(body + 4 * i); else ((double *)out)[i] = szhost_get_f64be(body + 8 * i);
         }
     } else if (same & 0x01) { /* constant */
         if (szlen < 4 + meta_len + st + esz) ok = 0;
+        else if (d_out) {
+            szhip_ctx *ctx = get_ctx();
+            const float vf = szhost_get_f32be(body); const double vd = dataType == SZ_DOUBLE ? szhost_get_f64be(body) : 0;
+            const int rc = ctx ? szhip_fill(ctx, dtk, dataType == SZ_FLOAT ? (const void *)&vf : (const void *)&vd, dataLength, d_out) : SZHIP_ERR_NODEVICE;
+            if (rc != SZHIP_OK) { printf("Error: szhip_fill failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device"); ok = 0; }
+        }
         else for (size_t i = 0; i < dataLength; i++) {
             if (dataType == SZ_FLOAT) ((float *)out)[i] = szhost_get_f32be(body); else ((double *)out)[i] = szhost_get_f64be(body);
         }
@@ -926,46 +1135,55 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
             szhip_ctx *ctx = get_ctx();
             const int dt = dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64;
             size_t bo = 0, bs = 0; double thr = 0;
-            unsigned char *signs = NULL;
+            unsigned char *signs = NULL, *blob_host = NULL;
             if (!ctx || szhip_sz14_pwr_locate(dt, sz, szlen, 4 + meta_len + st, &bo, &bs, &thr) != SZHIP_OK) { printf("Error: truncated PW_REL stream.\n"); ok = 0; }
             else if (bs > 0) {                                     /* sz_lossless_decompress(ZSTD_COMPRESSOR, ...) of the sign bytes */
                 signs = (unsigned char *)malloc(dataLength ? dataLength : 1);
                 if (!zstd_load()) { printf("Error: the sign bytes of this PW_REL stream need libzstd.so.1.\n"); ok = 0; }
                 else if (!signs) ok = 0;
-                else {
-                    size_t got = g_zstd.decompress(signs, dataLength, sz + bo, bs);
+                else if (d_sz && (!(blob_host = (unsigned char *)malloc(bs)) || szhip_copy(ctx, blob_host, d_sz + bo, bs, 0) != SZHIP_OK)) {
+                    printf("Error: the sign bytes of this PW_REL stream did not reach the host.\n"); ok = 0;
+                } else {
+                    const unsigned char *blob = d_sz ? blob_host : sz + bo;
+                    size_t got = g_zstd.decompress(signs, dataLength, blob, bs);
                     if (g_zstd.iserr(got) || got != dataLength) {
                         /* the reference's 2-D / 3-D MSST19 wrappers code the sign bytes with the CONFIGURED back end (sz_float_pwr.c:2030, :2068) while its
                          * readers always ask zstd (szd_float_pwr.c:1438), i.e. it cannot read its own gzip-configured streams; zlib is tried here */
                         unsigned long zl = (unsigned long)dataLength;
-                        if (!(zlib_load() && g_zlib.uncompress(signs, &zl, sz + bo, (unsigned long)bs) == 0 && zl == dataLength)) {
+                        if (!(zlib_load() && g_zlib.uncompress(signs, &zl, blob, (unsigned long)bs) == 0 && zl == dataLength)) {
                             printf("Error: the sign bytes of this PW_REL stream do not decode to %zu bytes.\n", dataLength); ok = 0;
                         }
                     }
                 }
             }
             if (ok) {
-                int rc = szhip_decompress_sz14_pwr(ctx, dt, sz, 0, szlen, 4 + meta_len + st, dim == 4 ? r4 * r3 : r3, r2, r1, signs, out, 0, &g_last_stats);
+                int rc = szhip_decompress_sz14_pwr(ctx, dt, lsz, d_sz != NULL, szlen, 4 + meta_len + st, dim == 4 ? r4 * r3 : r3, r2, r1, signs, out, ood, &g_last_stats);
                 if (rc != SZHIP_OK) { printf("Error: szhip_decompress_sz14_pwr failed (%d): %s\n", rc, szhip_last_error(ctx)); ok = 0; }
             }
-            free(signs);
+            free(signs); free(blob_host);
         } else if ((same & (0x20 | 0x02)) || !(dim >= 1 && dim <= 4) || (!(same & 0x80) && dim == 4) || ((same & 0x80) && dim == 1) || st != 8 || confparams_dec->sol_ID != SZ) {
             printf("Error: the MI355X build decodes SZ 2.1 regression-type streams of 2-D/3-D/4-D arrays and SZ 1.4 streams of 1-D/2-D/3-D arrays "
                    "(float/double; point-wise-relative streams in both forms; no random-access form); this stream (flags 0x%02x, dim %d) is not covered yet.\n", same, dim);
             ok = 0;
         } else if (!(same & 0x80)) {   /* SZ 1.4 container: getSnapshotData_float_3D -> decompressDataSeries_float_3D (szd_float.c:146,600) */
             szhip_ctx *ctx = get_ctx();
-            int rc = ctx ? szhip_decompress_sz14(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, sz, 0, szlen, 4 + meta_len + st,
-                                                 r3, r2, r1, out, 0, &g_last_stats) : SZHIP_ERR_NODEVICE;
+            int rc = ctx ? szhip_decompress_sz14(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, lsz, d_sz != NULL, szlen, 4 + meta_len + st,
+                                                 r3, r2, r1, out, ood, &g_last_stats) : SZHIP_ERR_NODEVICE;
             if (rc != SZHIP_OK) { printf("Error: szhip_decompress_sz14 failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device"); ok = 0; }
         } else {
             szhip_ctx *ctx = get_ctx();
             size_t s0 = dim == 4 ? r4 * r3 : r3;
-            int rc = ctx ? szhip_decompress(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, sz, 0, szlen, 4 + meta_len + st,
-                                            s0, r2, r1, out, 0, &g_last_stats) : SZHIP_ERR_NODEVICE;
+            int rc = ctx ? szhip_decompress(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, lsz, d_sz != NULL, szlen, 4 + meta_len + st,
+                                            s0, r2, r1, out, ood, &g_last_stats) : SZHIP_ERR_NODEVICE;
             if (rc != SZHIP_OK) { printf("Error: szhip_decompress failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device"); ok = 0; }
         }
     }
+    if (ok && confparams_dec->protectValueRange && d_out) {        /* the same clamp on the device (k_clamp) */
+        szhip_ctx *ctx = get_ctx();
+        const int rc = ctx ? szhip_clamp(ctx, dtk, d_out, dataLength, dataType == SZ_FLOAT ? (double)confparams_dec->fmin : confparams_dec->dmin,
+                                         dataType == SZ_FLOAT ? (double)confparams_dec->fmax : confparams_dec->dmax) : SZHIP_ERR_NODEVICE;
+        if (rc != SZHIP_OK) { printf("Error: szhip_clamp failed (%d): %s\n", rc, ctx ? szhip_last_error(ctx) : "no device"); ok = 0; }
+    } else
     if (ok && confparams_dec->protectValueRange) { /* szd_float.c:161-176 */
         if (dataType == SZ_FLOAT) {
             float *nd = (float *)out, mn = confparams_dec->fmin, mx = confparams_dec->fmax;
@@ -976,7 +1194,7 @@ static void *decompress_fp(int dataType, unsigned char *cmpBytes, size_t cmpSize
         }
     }
     if (owned) free(sz);
-    if (!ok) { free(out); return NULL; }
+    if (!ok) { if (!d_out) free(out); return NULL; }
     /* updateQuantizationInfo(tdps->intervals) (TightDataPointStorageF.c / szd_float.c): a later compression with fixed
      * quantization_intervals finds what this stream used, as after the reference's decompression */
     if (!(same & (0x10 | 0x01)) && g_last_stats.intervals) { exe_params->intvCapacity = (int)g_last_stats.intervals; exe_params->intvRadius = exe_params->intvCapacity / 2; }
@@ -1088,9 +1306,22 @@ void *SZ_decompress(int dataType, unsigned char *bytes, size_t byteLength, size_
     size_t _r[5];
     filterDimension(r5, r4, r3, r2, r1, _r);
     fresh_dec_state();
-    if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE) return decompress_fp(dataType, bytes, byteLength, _r[4], _r[3], _r[2], _r[1], _r[0]);
+    if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE) return decompress_fp(dataType, bytes, byteLength, _r[4], _r[3], _r[2], _r[1], _r[0], 0, NULL);
     printf("Error: the MI355X build handles SZ_FLOAT and SZ_DOUBLE; integer types are outside its scope.\n");
     return NULL;
+}
+
+int SZ_hip_decompress_device(int dataType, const unsigned char *bytes, int bytes_on_device, size_t byteLength, void *d_out,
+                             size_t r5, size_t r4, size_t r3, size_t r2, size_t r1)
+{
+    if (!bytes || !d_out) { printf("Error: SZ_hip_decompress_device: null argument.\n"); return SZ_NSCS; }
+    size_t _r[5];
+    filterDimension(r5, r4, r3, r2, r1, _r);
+    fresh_dec_state();
+    if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE)
+        return decompress_fp(dataType, (unsigned char *)bytes, byteLength, _r[4], _r[3], _r[2], _r[1], _r[0], bytes_on_device, d_out) ? SZ_SCES : SZ_NSCS;
+    printf("Error: the MI355X build handles SZ_FLOAT and SZ_DOUBLE; integer types are outside its scope.\n");
+    return SZ_NSCS;
 }
 
 size_t SZ_decompress_args(int dataType, unsigned char *bytes, size_t byteLength, void *decompressed_array,
@@ -1161,7 +1392,7 @@ unsigned char *SZ_compress_customize_threadsafe(const char *cmprName, void *user
         filterDimension(r5, r4, r3, r2, r1, _r);
         if (dataType == SZ_FLOAT || dataType == SZ_DOUBLE)
             compress_fp(dataType, SZ_WITH_LINEAR_REGRESSION, &result, data, _r[4], _r[3], _r[2], _r[1], _r[0], outSize,
-                        para->errorBoundMode, para->absErrBound, para->relBoundRatio, para->pw_relBoundRatio);
+                        para->errorBoundMode, para->absErrBound, para->relBoundRatio, para->pw_relBoundRatio, &g_host_io);
         *status = result ? SZ_SCES : SZ_NSCS;
     } else *status = SZ_NSCS;
     return result;
@@ -1218,8 +1449,10 @@ static int omp_pick_threads(size_t r1, size_t r2, size_t r3)
     return 0;
 }
 static unsigned char *omp_compress(int dataType, const void *oriData, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size)
-{ return omp_compress_at(dataType, oriData, 0, r1, r2, r3, realPrecision, comp_size); }
-static unsigned char *omp_compress_at(int dataType, const void *oriData, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size)
+{ return omp_compress_at(dataType, oriData, 0, r1, r2, r3, realPrecision, comp_size, 0, &g_host_io); }
+/* `mark` (0: none): written into parameter byte 15 in front of the call, for a stream that stays on the device; `io`: where the stream goes */
+static unsigned char *omp_compress_at(int dataType, const void *oriData, int on_device, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size,
+                                      unsigned char mark, const cpr_io *io)
 {
     if (comp_size) *comp_size = 0;
     if (!oriData || !comp_size) return NULL;
@@ -1241,13 +1474,15 @@ static unsigned char *omp_compress_at(int dataType, const void *oriData, int on_
     if (confparams_cpr->randomAccess) flags |= 0x02;
     if (confparams_cpr->protectValueRange) flags |= 0x04;
     szhost_write_meta(&m, flags, meta);
+    if (mark && io->d_stream) meta[19] = mark;
     szhip_params hp; memset(&hp, 0, sizeof(hp));
     hp.sample_distance = confparams_cpr->sampleDistance; hp.pred_threshold = confparams_cpr->predThreshold;
     hp.max_quant_intervals = exe_params->optQuantMode == 1 ? confparams_cpr->maxRangeRadius * 2 : confparams_cpr->max_quant_intervals;
     hp.quantization_intervals = exe_params->optQuantMode == 1 ? 0 : (unsigned)exe_params->intvCapacity;
-    unsigned char *out = NULL; size_t n = 0;
+    unsigned char *out = io->d_stream; size_t n = io->cap;
     const int rc = szhip_compress_omp(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, on_device, r1, r2, r3, realPrecision, threads, &hp,
-                                      meta, 4 + meta_len, 0, &out, &n, &g_last_stats);
+                                      meta, 4 + meta_len, io->d_stream ? 2 : 0, &out, &n, &g_last_stats);
+    if (stream_outgrew(io, ctx, rc)) { (void)no_room(io); return NULL; }
     if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp failed (%d): %s\n", rc, szhip_last_error(ctx)); return NULL; }
     *comp_size = n;
     return out;
@@ -1256,7 +1491,8 @@ static unsigned char *omp_compress_at(int dataType, const void *oriData, int on_
  * `avail`: the bytes there are behind that pointer -- SZ_decompress knows (a crafted frame must not send the table walk below out of the buffer:
  * every offset is checked against it before it is read); the reference-signature entry points have no length argument and pass SIZE_MAX:
  * there the extent is read off the stream's own tables, as the reference does */
-static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data, size_t avail)
+/* d_out (NULL: a malloc'd host array goes out through *data): the caller's DEVICE array, decoded into and handed back through *data */
+static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data, size_t avail, void *d_out)
 {
     if (!data) return;
     *data = NULL;
@@ -1293,10 +1529,10 @@ static void omp_decompress(int dataType, void **data, size_t r1, size_t r2, size
     off += nb * 8;
     if (pay == (size_t)-1 || pay > avail - off) { printf("Error: truncated OpenMP-container stream.\n"); return; }
     const size_t total = off + pay;
-    void *out = malloc(r1 * r2 * r3 * esz ? r1 * r2 * r3 * esz : 1);
+    void *out = d_out ? d_out : malloc(r1 * r2 * r3 * esz ? r1 * r2 * r3 * esz : 1);
     if (!out) return;
-    const int rc = szhip_decompress_omp(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, comp_data, 0, total, 0, r1, r2, r3, out, 0, &g_last_stats);
-    if (rc != SZHIP_OK) { printf("Error: szhip_decompress_omp failed (%d): %s\n", rc, szhip_last_error(ctx)); free(out); return; }
+    const int rc = szhip_decompress_omp(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, comp_data, 0, total, 0, r1, r2, r3, out, d_out ? 1 : 0, &g_last_stats);
+    if (rc != SZHIP_OK) { printf("Error: szhip_decompress_omp failed (%d): %s\n", rc, szhip_last_error(ctx)); if (!d_out) free(out); return; }
     *data = out;
 }
 unsigned char *SZ_compress_float_3D_MDQ_openmp(float *oriData, size_t r1, size_t r2, size_t r3, float realPrecision, size_t *comp_size)
@@ -1304,9 +1540,9 @@ unsigned char *SZ_compress_float_3D_MDQ_openmp(float *oriData, size_t r1, size_t
 unsigned char *SZ_compress_double_3D_MDQ_openmp(double *oriData, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size)
 { return omp_compress(SZ_DOUBLE, oriData, r1, r2, r3, realPrecision, comp_size); }
 void decompressDataSeries_float_3D_openmp(float **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data)
-{ omp_decompress(SZ_FLOAT, (void **)data, r1, r2, r3, comp_data, (size_t)-1); }
+{ omp_decompress(SZ_FLOAT, (void **)data, r1, r2, r3, comp_data, (size_t)-1, NULL); }
 void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data)
-{ omp_decompress(SZ_DOUBLE, (void **)data, r1, r2, r3, comp_data, (size_t)-1); }
+{ omp_decompress(SZ_DOUBLE, (void **)data, r1, r2, r3, comp_data, (size_t)-1, NULL); }
 
 /* the rest of sz/include/sz_omp.h and sz.h's thread helpers, so that callers written for an OpenMP build link unchanged:
  * sz_set_num_threads (sz_omp.c:49-53) sets the box count as omp_set_num_threads does for an OpenMP build; the 1-D / 2-D entry points

@@ -624,14 +624,23 @@ int szhip_sz14_pwr_locate(int dtype, const unsigned char *stream, size_t stream_
 int szhip_decompress_sz14_pwr(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
                               size_t r0, size_t r1, size_t r2, const unsigned char *signs_host, void *out, int out_on_device, szhip_stats *stats)
 {
-    if (!ctx || !stream || !out || body_off >= stream_len || stream_on_device) return SZHIP_ERR_ARG;        // the header is read on the host
+    if (!ctx || !stream || !out || body_off >= stream_len) return SZHIP_ERR_ARG;
     if (!dims_3d_2d_1d(r0, r1, r2)) return SZHIP_ERR_ARG;
     TRY(check_alignment_set_device(ctx, dtype, out));
+    // the fixed fields in front of the type array are read on the host: of a device-resident stream they are fetched, the rest stays where it is
+    unsigned char head[160]; const unsigned char *hs = stream;
+    if (stream_on_device) {
+        const size_t want = std::min<size_t>(stream_len, body_off + 80);
+        if (want > sizeof(head)) return SZHIP_ERR_ARG;
+        HIPCHK(hipMemcpyAsync(head, stream, want, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        hs = head;
+    }
     size_t bo, bs; double thr;
-    if (szhip_sz14_pwr_locate(dtype, stream, stream_len, body_off, &bo, &bs, &thr) != SZHIP_OK) return SZHIP_ERR_STREAM;
-    const bool msst = (stream[3] & 0x08) != 0;                   // TightDataPointStorageF.c:81
+    if (szhip_sz14_pwr_locate(dtype, hs, stream_len, body_off, &bo, &bs, &thr) != SZHIP_OK) return SZHIP_ERR_STREAM;
+    const bool msst = (hs[3] & 0x08) != 0;                       // TightDataPointStorageF.c:81
     return drained_on_failure(ctx, with_ticket_fallback(ctx, [&]() {
-               return BY_DTYPE(dtype, decompress14_pwr_impl, ctx, stream, 0, stream_len, body_off, r0, r1, r2, signs_host, thr, msst, out, out_on_device, stats); }));
+               return BY_DTYPE(dtype, decompress14_pwr_impl, ctx, stream, stream_on_device ? 1 : 0, stream_len, body_off, r0, r1, r2, signs_host, thr, msst, out, out_on_device, stats); }));
 }
 
 int szhip_decompress(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -676,6 +685,82 @@ int szhip_huff_book(szhip_ctx *ctx, const void *hist, unsigned intervals, unsign
     HIPCHK(hipMemcpyAsync(record, ctx->book_rec.p, sizeof(*record), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return SZHIP_OK;
+}
+
+// ---- the copy-shaped passes of the drop-in calls for device-resident arrays (szhip.h; kernels: szh_store.h)
+static unsigned store_grid(size_t n, int dtype)       // a lane per 16-byte piece, grid-stride beyond 2048 workgroups
+{
+    const size_t pieces = n / (dtype == SZHIP_F32 ? 4 : 2) + 1;
+    return (unsigned)std::min<size_t>((pieces + 255) / 256, 2048);
+}
+static bool store_count_ok(size_t n) { return n >= 1 && n < ((size_t)1 << 59); }
+
+int szhip_store_be(szhip_ctx *ctx, int dtype, const void *d_src, size_t n, const void *zero_replacement, unsigned char *dst, int dst_on_device)
+{
+    if (!ctx || !d_src || !dst || !store_count_ok(n) || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, d_src));
+    const size_t bytes = n * (dtype == SZHIP_F32 ? 4 : 8);
+    unsigned char *d_dst = dst;
+    if (!dst_on_device) { TRY(ensure(ctx, ctx->stream_buf, bytes)); d_dst = (unsigned char *)ctx->stream_buf.p; }
+    if (dtype == SZHIP_F32) {
+        float r = 0; if (zero_replacement) memcpy(&r, zero_replacement, 4);
+        hipLaunchKernelGGL((k_store_be<float>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (const float *)d_src, d_dst, (int64_t)n, zero_replacement ? 1 : 0, r);
+    } else {
+        double r = 0; if (zero_replacement) memcpy(&r, zero_replacement, 8);
+        hipLaunchKernelGGL((k_store_be<double>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (const double *)d_src, d_dst, (int64_t)n, zero_replacement ? 1 : 0, r);
+    }
+    HIPCHK(hipGetLastError());
+    if (!dst_on_device) return synced_on_failure(ctx, staged_copy(ctx, dst, d_dst, bytes, false));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+
+int szhip_load_be(szhip_ctx *ctx, int dtype, const unsigned char *src, int src_on_device, size_t n, void *d_out)
+{
+    if (!ctx || !src || !d_out || !store_count_ok(n) || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, d_out));
+    const size_t bytes = n * (dtype == SZHIP_F32 ? 4 : 8);
+    const unsigned char *d_src = src;
+    if (!src_on_device) {
+        TRY(ensure(ctx, ctx->stream_buf, bytes));
+        TRY(synced_on_failure(ctx, staged_copy(ctx, ctx->stream_buf.p, src, bytes, true)));
+        d_src = (const unsigned char *)ctx->stream_buf.p;
+    }
+    if (dtype == SZHIP_F32) hipLaunchKernelGGL((k_load_be<float>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, d_src, (float *)d_out, (int64_t)n);
+    else hipLaunchKernelGGL((k_load_be<double>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, d_src, (double *)d_out, (int64_t)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+
+int szhip_fill(szhip_ctx *ctx, int dtype, const void *value, size_t n, void *d_out)
+{
+    if (!ctx || !value || !d_out || !store_count_ok(n) || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, d_out));
+    if (dtype == SZHIP_F32) { float v; memcpy(&v, value, 4); hipLaunchKernelGGL((k_fill<float>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (float *)d_out, (int64_t)n, v); }
+    else { double v; memcpy(&v, value, 8); hipLaunchKernelGGL((k_fill<double>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (double *)d_out, (int64_t)n, v); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+
+int szhip_clamp(szhip_ctx *ctx, int dtype, void *d_data, size_t n, double vmin, double vmax)
+{
+    if (!ctx || !d_data || !store_count_ok(n) || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, d_data));
+    if (dtype == SZHIP_F32) hipLaunchKernelGGL((k_clamp<float>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (float *)d_data, (int64_t)n, (float)vmin, (float)vmax);
+    else hipLaunchKernelGGL((k_clamp<double>), dim3(store_grid(n, dtype)), dim3(256), 0, ctx->stream, (double *)d_data, (int64_t)n, vmin, vmax);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SZHIP_OK;
+}
+
+int szhip_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, int to_device)
+{
+    if (!ctx || !dst || !src) return SZHIP_ERR_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    if (bytes == 0) return SZHIP_OK;
+    return synced_on_failure(ctx, staged_copy(ctx, dst, src, bytes, to_device != 0));
 }
 
 int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes)

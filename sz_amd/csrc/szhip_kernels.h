@@ -1763,3 +1763,4 @@ __global__ void k_probe_touch(unsigned long long *p) { *p = 1; }
 #include "szh_book.h"
 #include "szh_segenc.h"
 #include "szh_fittile.h"
+#include "szh_store.h"
