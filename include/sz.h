@@ -224,6 +224,19 @@ unsigned char *SZ_compress_float_3D_MDQ_openmp(float *oriData, size_t r1, size_t
 unsigned char *SZ_compress_double_3D_MDQ_openmp(double *oriData, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size);
 void decompressDataSeries_float_3D_openmp(float **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data);
 void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data);
+/* Many small arrays of ONE shape r1 x r2 x r3 and type in one call (szhip_compress_omp_batch / szhip_decompress_omp_batch of szhip.h: one set of kernel launches over
+ * the boxes of all arrays instead of one blocking call per array).  data[i]: the arrays, on the host or -- data_on_device -- on the device; realPrecision[i]: the
+ * absolute bound of array i.  streams[i] comes back as a malloc'd stream (caller frees) of comp_sizes[i] bytes, byte for byte what
+ * SZ_compress_{float,double}_3D_MDQ_openmp returns for array i under the same configuration: the same parameter bytes of confparams_cpr, the same box count
+ * (sz_set_num_threads / SZ_HIP_OMP_THREADS, else picked from the shape), the body behind 4 + MetaDataByteLength bytes.  The inverse takes comp_data[i] at the stream's
+ * FIRST byte, as returned (it skips the parameter bytes itself), comp_sizes[i] bytes long, and writes array i to out[i] (host, or device with out_on_device).
+ * Both return SZ_SCES, or SZ_NSCS with a printed reason; when any array fails every returned stream is freed and its pointer nulled.
+ * Out of scope: error-bound modes other than an absolute bound per array, SZ_HIP_MODE=omp through SZ_compress_args, the lossless stage (the streams are what the
+ * `*_openmp` entry points write: never wrapped). */
+int SZ_hip_compress_openmp_batch(int dataType, int count, const void *const *data, int data_on_device, const double *realPrecision,
+                                 size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes);
+int SZ_hip_decompress_openmp_batch(int dataType, int count, unsigned char *const *comp_data, const size_t *comp_sizes, void *const *out, int out_on_device,
+                                   size_t r1, size_t r2, size_t r3);
 /* A sub-box of a 3-D array out of its stream: start / end per dimension in the order r3, r2, r1 (slowest first), end exclusive.  Returns a malloc'd array of
  * (end[0]-start[0]) x (end[1]-start[1]) x (end[2]-start[2]) values (caller frees), bit for bit that part of what SZ_decompress returns; NULL with a printed
  * reason otherwise.  Reads what this library's SZ_decompress recognises as an OpenMP container: the streams SZ_compress_args writes for 3-D arrays under

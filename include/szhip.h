@@ -236,6 +236,52 @@ int szhip_pack_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_dev
 int szhip_scatter_view(szhip_ctx *ctx, int dtype, const void *d_packed, size_t r0, size_t r1, size_t r2, void *out, int out_on_device, size_t pitch0, size_t pitch1);
 
 /*
+ * MANY SMALL ARRAYS of one shape in one call (OpenMP container).  A single call's cost for a small array is almost entirely fixed -- host
+ * synchronisations, launch gaps, small copies, kernels that cannot fill the chip with 8 - 27 boxes.  A batch call runs the container's kernels ONCE over the boxes of all
+ * `count` arrays (the array is the grid's second dimension; a box finds its array's base pointer, bound, interval count, code table and stream position through a
+ * per-array table), builds `count` code books on the host between two synchronisations, and so makes a number of synchronisations, launches and copies that does not
+ * grow with `count` (one sweep launch per form, below).  The shape r0 x r1 x r2, dtype, thread_num, params, meta_len and the pointer kinds are common; everything else
+ * is per item.  No stream changes:
+ *   - blob[offset_i, offset_i + size_i) is byte for byte what szhip_compress_omp returns for array i alone with the same eb, meta, params and thread_num; the
+ *     interval optimiser (params->quantization_intervals == 0) runs per array, so the arrays of a batch may have different interval counts, trees and header lengths.
+ *     Offsets increase with i and are multiples of 64; bytes between streams are undefined.  *blob: out_on_device 0: malloc'd host memory owned by the caller (free());
+ *     1: device memory owned by the context (valid until its next batch compress call); 2 (a caller's buffer): SZHIP_ERR_UNSUP.
+ *   - the batched decode writes into items[i].out bit for bit what szhip_decompress_omp writes for stream i, and nothing else.  Inputs are never written.
+ * Alignment as above: values to their element, streams and meta any; the 16-byte forms are picked PER ARRAY from its address, so the arrays of a batch may take
+ * different sweep forms (items[i].quant_kernel 3 / 4 / 5): they are grouped by form, one sweep launch per form; stats->quant_kernel_launches counts the sweep launches
+ * of the shared part (at most 3; the single calls of fallback items are not in it).
+ * Fallback: an array the shared launches do not cover runs through the single call from inside the batch call (identical by construction), its stream goes into the
+ * blob / its values into `out`, items[i].batched = 0, the rest of the batch stays batched.  Compress: more than 1024 intervals, a longest code word above 32 bits, a box
+ * of a number of points that is no multiple of 8 (then the whole batch), an extent of 1 in dim 0 or dim 1 (the whole batch).  Decompress: a one-symbol book, a stream
+ * that misses the look-up-table decoder's conditions (box points no multiple of 8; payload + tables beyond a workgroup's LDS), a thread_num other than the batch's first.
+ * Errors: the call returns the first non-zero items[i].rc, else SZHIP_OK.  A decompress item that fails (SZHIP_ERR_STREAM: found on the host in its header and tables,
+ * or on the device in its payloads and verbatim-value counts, counted per array) does not disturb the others: items with rc == SZHIP_OK are fully and correctly decoded, a
+ * failed item's output array is undefined.  Refused with SZHIP_ERR_ARG before anything is launched or written: count < 1, a null item pointer (data / meta; stream /
+ * out), a misaligned value pointer, a bound that is not positive.
+ * Limits (SZHIP_ERR_UNSUP beyond them): count <= 65535, count x boxes <= 2^22, count x r0 x r1 x r2 < 2^32 values; the single call's restrictions on the shape.
+ * Host arrays (data_on_device = 0) are staged one behind the other into the context's input buffer with ONE copy when they total at most 64 MiB, else array by array.
+ * stats: n_elements / n_blocks / n_unpred / out_bytes are sums over the batch, the times those of the shared launches.
+ */
+typedef struct szhip_batch_item {
+    /* in  */ const void *data;             /* compress: the array; decompress: unused */
+              void *out;                    /* decompress: where the array goes */
+              double eb;                    /* compress: absolute bound of THIS array */
+              const unsigned char *meta;    /* compress: meta_len bytes in front of THIS stream */
+              const unsigned char *stream;  /* decompress: the stream's first byte ... */
+              size_t stream_len, body_off;  /* ... its length, the offset of its thread_num field */
+    /* out */ size_t offset, size;          /* compress: the stream's place in the blob */
+              int rc;                       /* SZHIP_* of this item */
+              unsigned intervals;
+              uint64_t n_unpred;
+              int quant_kernel;             /* 3 / 4 / 5 as in szhip_stats */
+              int batched;                  /* 1: ran in the shared launches; 0: the single call ran for it */
+} szhip_batch_item;
+int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
+                             const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats);
+int szhip_decompress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
+                               int out_on_device, szhip_stats *stats);
+
+/*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of
  * sz/src/sz_float_pwr.c:1791-1975 / sz_double_pwr.c:1781-1965 (dispatch sz_float.c:2888-2996) and their inverses
  * szd_float_pwr.c:1353-1422.  Three steps, the sign bytes being compressed on the host (zstd) in between:
@@ -331,7 +377,7 @@ int szhip_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, int to_
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)
  *        4 code histogram (u32) 5 per-column zero counts (u32) 6 per-column unpredictable offsets (u64)
- *        7 unpredictable values (T) 8 stream buffer 12 the input buffer (szhip_stage_input, szhip_pack_view) */
+ *        7 unpredictable values (T) 8 stream buffer 12 the input buffer (szhip_stage_input, szhip_pack_view) 13 the blob of szhip_compress_omp_batch */
 int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes);
 
 #ifdef __cplusplus

@@ -54,6 +54,13 @@ class szhip_stats(ctypes.Structure):  # include/szhip.h
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class szhip_batch_item(ctypes.Structure):  # include/szhip.h: one array of szhip_compress_omp_batch / szhip_decompress_omp_batch
+    _fields_ = [("data", ctypes.c_void_p), ("out", ctypes.c_void_p), ("eb", ctypes.c_double), ("meta", ctypes.c_void_p), ("stream", ctypes.c_void_p),
+                ("stream_len", ctypes.c_size_t), ("body_off", ctypes.c_size_t),
+                ("offset", ctypes.c_size_t), ("size", ctypes.c_size_t), ("rc", ctypes.c_int), ("intervals", ctypes.c_uint), ("n_unpred", ctypes.c_uint64),
+                ("quant_kernel", ctypes.c_int), ("batched", ctypes.c_int)]
+
+
 class szhip_book_record(ctypes.Structure):  # include/szhip.h
     _fields_ = [("n_nodes", ctypes.c_uint32), ("tree_bytes", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("status", ctypes.c_uint32),
                 ("total_bits", ctypes.c_uint64), ("total_unpred", ctypes.c_uint64)]
@@ -160,6 +167,20 @@ def _bind(L):
         L.szhip_pack_view.restype = ctypes.c_int
         L.szhip_scatter_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, sz, sz, ctypes.c_void_p, ctypes.c_int, sz, sz]
         L.szhip_scatter_view.restype = ctypes.c_int
+    if hasattr(L, "szhip_compress_omp_batch"):
+        L.szhip_compress_omp_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.c_int, ctypes.c_int, sz, sz, sz, ctypes.c_int,
+                                               ctypes.POINTER(szhip_params), sz, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(szhip_stats)]
+        L.szhip_compress_omp_batch.restype = ctypes.c_int
+        L.szhip_decompress_omp_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.c_int, ctypes.c_int, sz, sz, sz, ctypes.c_int,
+                                                 ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_batch.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_compress_openmp_batch"):
+        L.SZ_hip_compress_openmp_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double), sz, sz, sz,
+                                                   ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]
+        L.SZ_hip_compress_openmp_batch.restype = ctypes.c_int
+        L.SZ_hip_decompress_openmp_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_void_p),
+                                                     ctypes.c_int, sz, sz, sz]
+        L.SZ_hip_decompress_openmp_batch.restype = ctypes.c_int
     if hasattr(L, "SZ_hip_compress_region"):
         L.SZ_hip_compress_region.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [sz] * 5 + \
                                             [ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -360,6 +381,36 @@ def SZ_hip_decompress_device(stream_or_ptr, on_device, length, out_ptr, shape, d
     rc = lib().SZ_hip_decompress_device(dt, src, 1 if on_device else 0, length, out_ptr, *_dims5(shape))
     if rc != SZ_SCES:
         raise SZError(f"SZ_hip_decompress_device failed ({rc})")
+
+
+def SZ_hip_compress_openmp_batch(ptrs, on_device, shape, dtype, bounds):
+    """include/sz.h: `len(ptrs)` arrays of one 3-D `shape` / `dtype` at the addresses ptrs (host, or device with on_device) into OpenMP-container streams, array i with
+    the absolute bound bounds[i]: a list of bytes objects, stream i byte for byte what SZ_compress_{float,double}_3D_MDQ_openmp returns for array i."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(ptrs)
+    c_ptrs = (ctypes.c_void_p * count)(*ptrs)
+    c_eb = (ctypes.c_double * count)(*bounds)
+    streams, sizes = (ctypes.c_void_p * count)(), (ctypes.c_size_t * count)()
+    rc = lib().SZ_hip_compress_openmp_batch(dt, count, c_ptrs, 1 if on_device else 0, c_eb, shape[0], shape[1], shape[2], streams, sizes)
+    if rc != SZ_SCES:
+        raise SZError(f"SZ_hip_compress_openmp_batch failed ({rc})")
+    out = [ctypes.string_at(streams[i], sizes[i]) for i in range(count)]
+    for i in range(count):
+        lib().free(streams[i])
+    return out
+
+
+def SZ_hip_decompress_openmp_batch(streams, out_ptrs, out_on_device, shape, dtype):
+    """include/sz.h: the inverse -- streams[i] (bytes, as returned: the parameter bytes in front) into the array at out_ptrs[i] (host, or device with out_on_device)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(streams)
+    keep = [ctypes.create_string_buffer(bytes(s), len(s)) for s in streams]
+    c_streams = (ctypes.c_void_p * count)(*[ctypes.addressof(k) for k in keep])
+    c_sizes = (ctypes.c_size_t * count)(*[len(s) for s in streams])
+    c_out = (ctypes.c_void_p * count)(*out_ptrs)
+    rc = lib().SZ_hip_decompress_openmp_batch(dt, count, c_streams, c_sizes, c_out, 1 if out_on_device else 0, shape[0], shape[1], shape[2])
+    if rc != SZ_SCES:
+        raise SZError(f"SZ_hip_decompress_openmp_batch failed ({rc})")
 
 
 def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
@@ -593,6 +644,41 @@ class HipContext:
         if rc:
             self._err(rc, "szhip_decompress_omp")
         return st
+
+    def compress_omp_batch(self, ptrs, on_device, shape3, dtype, bounds, thread_num, metas, params=None, out_on_device=False, raise_on_error=True):
+        """szhip_compress_omp_batch: len(ptrs) arrays of one shape3 / dtype in one call, array i with the absolute bound bounds[i] and the parameter bytes metas[i] (all of
+        one length).  Returns (rc, blob, blob_size, items, stats): blob a bytes object, or the context's device pointer with out_on_device; items[i].offset / .size place
+        stream i in it, items[i].rc / .intervals / .n_unpred / .quant_kernel / .batched say how it went.  rc: the first non-zero items[i].rc."""
+        count = len(ptrs)
+        items = (szhip_batch_item * max(count, 1))()
+        keep = [ctypes.create_string_buffer(bytes(m), len(m)) for m in metas]
+        for i in range(count):
+            items[i].data, items[i].eb, items[i].meta = ptrs[i], bounds[i], ctypes.addressof(keep[i]) if metas[i] is not None else None
+        p = params or szhip_params(100, 0.99, 65536, 0)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(0), szhip_stats()
+        rc = lib().szhip_compress_omp_batch(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, count, int(on_device), shape3[0], shape3[1], shape3[2], thread_num,
+                                            ctypes.byref(p), len(metas[0]) if count else 0, int(out_on_device), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_compress_omp_batch")
+        if out_on_device or not out.value:
+            return rc, out.value, n.value, items, st
+        b = ctypes.string_at(out.value, n.value)
+        lib().free(out)
+        return rc, b, n.value, items, st
+
+    def decompress_omp_batch(self, streams, stream_on_device, body_off, shape3, dtype, out_ptrs, out_on_device, raise_on_error=True):
+        """szhip_decompress_omp_batch: streams[i] = (address, length) of an OpenMP-container stream (host, or device with stream_on_device) into the array at out_ptrs[i].
+        Returns (rc, items, stats); an item whose rc is non-zero failed alone."""
+        count = len(streams)
+        items = (szhip_batch_item * max(count, 1))()
+        for i in range(count):
+            items[i].stream, items[i].stream_len, items[i].body_off, items[i].out = streams[i][0], streams[i][1], body_off, out_ptrs[i]
+        st = szhip_stats()
+        rc = lib().szhip_decompress_omp_batch(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, count, int(stream_on_device), shape3[0], shape3[1], shape3[2],
+                                              int(out_on_device), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_decompress_omp_batch")
+        return rc, items, st
 
     def decompress_omp_region(self, stream_ptr, stream_on_device, stream_len, body_off, shape3, dtype, lo, hi, out_ptr, out_on_device):
         """The sub-box [lo, hi) (per dimension, dim 0 slowest, hi exclusive) of an OpenMP-container stream (szhip_decompress_omp_region): only the boxes that

@@ -1448,6 +1448,20 @@ static int omp_pick_threads(size_t r1, size_t r2, size_t r3)
     }
     return 0;
 }
+/* what every OpenMP-container stream of the present configuration starts with and is made with: the version, flag and parameter bytes of confparams_cpr, the HIP layer's parameters */
+static void omp_meta_params(unsigned char *meta, szhip_params *hp)
+{
+    const int meta_type = confparams_cpr->dataType == SZ_DOUBLE ? SZ_DOUBLE : SZ_FLOAT;
+    szhost_meta m; fill_meta(&m, confparams_cpr, meta_type);
+    unsigned char flags = 0x80 | (exe_params->SZ_SIZE_TYPE == 8 ? 0x40 : 0);
+    if (confparams_cpr->randomAccess) flags |= 0x02;
+    if (confparams_cpr->protectValueRange) flags |= 0x04;
+    szhost_write_meta(&m, flags, meta);
+    memset(hp, 0, sizeof(*hp));
+    hp->sample_distance = confparams_cpr->sampleDistance; hp->pred_threshold = confparams_cpr->predThreshold;
+    hp->max_quant_intervals = exe_params->optQuantMode == 1 ? confparams_cpr->maxRangeRadius * 2 : confparams_cpr->max_quant_intervals;
+    hp->quantization_intervals = exe_params->optQuantMode == 1 ? 0 : (unsigned)exe_params->intvCapacity;
+}
 static unsigned char *omp_compress(int dataType, const void *oriData, size_t r1, size_t r2, size_t r3, double realPrecision, size_t *comp_size)
 { return omp_compress_at(dataType, oriData, 0, r1, r2, r3, realPrecision, comp_size, 0, &g_host_io); }
 /* `mark` (0: none): written into parameter byte 15 in front of the call, for a stream that stays on the device; `io`: where the stream goes */
@@ -1466,19 +1480,11 @@ static unsigned char *omp_compress_at(int dataType, const void *oriData, int on_
     /* The body begins at byte 3 + 1 + MetaDataByteLength = 32 for BOTH types (sz_omp.c:221, :733): with confparams_cpr->dataType == SZ_DOUBLE
      * initRandomAccessBytes writes 36 parameter bytes and the body then overwrites the last eight of them; callers pass
      * comp + 4 + MetaDataByteLength to the decompressor either way (example/sz_openmp.c) */
-    const int meta_type = confparams_cpr->dataType == SZ_DOUBLE ? SZ_DOUBLE : SZ_FLOAT;
     const size_t meta_len = MetaDataByteLength;
-    szhost_meta m; fill_meta(&m, confparams_cpr, meta_type);
     unsigned char meta[4 + MetaDataByteLength_double];
-    unsigned char flags = 0x80 | (exe_params->SZ_SIZE_TYPE == 8 ? 0x40 : 0);
-    if (confparams_cpr->randomAccess) flags |= 0x02;
-    if (confparams_cpr->protectValueRange) flags |= 0x04;
-    szhost_write_meta(&m, flags, meta);
+    szhip_params hp;
+    omp_meta_params(meta, &hp);
     if (mark && io->d_stream) meta[19] = mark;
-    szhip_params hp; memset(&hp, 0, sizeof(hp));
-    hp.sample_distance = confparams_cpr->sampleDistance; hp.pred_threshold = confparams_cpr->predThreshold;
-    hp.max_quant_intervals = exe_params->optQuantMode == 1 ? confparams_cpr->maxRangeRadius * 2 : confparams_cpr->max_quant_intervals;
-    hp.quantization_intervals = exe_params->optQuantMode == 1 ? 0 : (unsigned)exe_params->intvCapacity;
     unsigned char *out = io->d_stream; size_t n = io->cap;
     const int rc = szhip_compress_omp(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, oriData, on_device, r1, r2, r3, realPrecision, threads, &hp,
                                       meta, 4 + meta_len, io->d_stream ? 2 : 0, &out, &n, &g_last_stats);
@@ -1543,6 +1549,56 @@ void decompressDataSeries_float_3D_openmp(float **data, size_t r1, size_t r2, si
 { omp_decompress(SZ_FLOAT, (void **)data, r1, r2, r3, comp_data, (size_t)-1, NULL); }
 void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, size_t r3, unsigned char *comp_data)
 { omp_decompress(SZ_DOUBLE, (void **)data, r1, r2, r3, comp_data, (size_t)-1, NULL); }
+
+/* ---- many small arrays of one shape (include/sz.h): the two calls above over `count` arrays, through szhip_compress_omp_batch / szhip_decompress_omp_batch */
+int SZ_hip_compress_openmp_batch(int dataType, int count, const void *const *data, int data_on_device, const double *realPrecision,
+                                 size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes)
+{
+    if (streams) for (int i = 0; i < count; ++i) streams[i] = NULL;
+    if (count < 1 || !data || !realPrecision || !streams || !comp_sizes || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: SZ_hip_compress_openmp_batch: bad arguments.\n"); return SZ_NSCS; }
+    if (confparams_cpr == NULL) SZ_Init(NULL);
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const int threads = omp_pick_threads(r1, r2, r3);
+    g_omp_last_threads = threads;
+    if (threads <= 0) { printf("Error: no power-of-two box grid divides %zu x %zu x %zu into boxes the MI355X build takes; set SZ_HIP_OMP_THREADS.\n", r1, r2, r3); return SZ_NSCS; }
+    unsigned char meta[4 + MetaDataByteLength_double];
+    szhip_params hp;
+    omp_meta_params(meta, &hp);
+    szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
+    if (!items) return SZ_NSCS;
+    for (int i = 0; i < count; ++i) { items[i].data = data[i]; items[i].eb = dataType == SZ_FLOAT ? (double)(float)realPrecision[i] : realPrecision[i]; items[i].meta = meta; }
+    unsigned char *blob = NULL; size_t blob_size = 0;
+    int rc = szhip_compress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, count, data_on_device, r1, r2, r3, threads, &hp,
+                                      4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &g_last_stats);
+    if (rc != SZHIP_OK) printf("Error: szhip_compress_omp_batch failed (%d): %s\n", rc, szhip_last_error(ctx));
+    for (int i = 0; i < count && rc == SZHIP_OK; ++i) {
+        streams[i] = (unsigned char *)malloc(items[i].size ? items[i].size : 1);
+        if (!streams[i]) { rc = SZHIP_ERR_INTERNAL; break; }
+        memcpy(streams[i], blob + items[i].offset, items[i].size);
+        comp_sizes[i] = items[i].size;
+    }
+    if (rc != SZHIP_OK) for (int i = 0; i < count; ++i) { free(streams[i]); streams[i] = NULL; comp_sizes[i] = 0; }
+    free(blob); free(items);
+    return rc == SZHIP_OK ? SZ_SCES : SZ_NSCS;
+}
+int SZ_hip_decompress_openmp_batch(int dataType, int count, unsigned char *const *comp_data, const size_t *comp_sizes, void *const *out, int out_on_device,
+                                   size_t r1, size_t r2, size_t r3)
+{
+    if (count < 1 || !comp_data || !comp_sizes || !out || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: SZ_hip_decompress_openmp_batch: bad arguments.\n"); return SZ_NSCS; }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
+    if (!items) return SZ_NSCS;
+    for (int i = 0; i < count; ++i) { items[i].stream = comp_data[i]; items[i].stream_len = comp_sizes[i]; items[i].body_off = 4 + (size_t)MetaDataByteLength; items[i].out = out[i]; }
+    const int rc = szhip_decompress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, count, 0, r1, r2, r3, out_on_device, &g_last_stats);
+    if (rc != SZHIP_OK) {
+        int bad = 0; while (bad < count - 1 && items[bad].rc == SZHIP_OK) ++bad;
+        printf("Error: szhip_decompress_omp_batch failed (%d; first at stream %d): %s\n", rc, bad, szhip_last_error(ctx));
+    }
+    free(items);
+    return rc == SZHIP_OK ? SZ_SCES : SZ_NSCS;
+}
 
 /* the rest of sz/include/sz_omp.h and sz.h's thread helpers, so that callers written for an OpenMP build link unchanged:
  * sz_set_num_threads (sz_omp.c:49-53) sets the box count as omp_set_num_threads does for an OpenMP build; the 1-D / 2-D entry points

@@ -45,10 +45,11 @@ __device__ __forceinline__ const void *szh_omp_box_origin_bytes(const szh_omp_ge
 // DEC = false: data -> codes (0 = the value is kept verbatim), the count of such values per box, the box's first value
 // DEC = true : codes + the box's verbatim values (in the box's row-major order, uoff[b] .. uoff[b + 1]) + its first value -> data;
 //              `ucount` is then ONE counter of boxes whose codes and table entry disagree
+// (the kernels of this file are thin __global__ wrappers around `*_body` functions: szh_ompbatch.h launches the same bodies over the boxes of many arrays)
 template <class T, bool DEC, bool VEC>
-__global__ __launch_bounds__(1024) void k_omp_box(szh_omp_geom g, const T *__restrict__ data, T *__restrict__ out, T eb, T recip, int intervals,
-                                                  uint16_t *__restrict__ codes, unsigned *__restrict__ ucount, u64 *__restrict__ ucount64, T *__restrict__ first,
-                                                  const T *__restrict__ unpred, const u64 *__restrict__ uoff)
+__device__ __forceinline__ void omp_box_body(szh_omp_geom g, const T *__restrict__ data, T *__restrict__ out, T eb, T recip, int intervals,
+                                             uint16_t *__restrict__ codes, unsigned *__restrict__ ucount, u64 *__restrict__ ucount64, T *__restrict__ first,
+                                             const T *__restrict__ unpred, const u64 *__restrict__ uoff)
 {
     SZH_DYN_SMEM(smem);
     T *ring = reinterpret_cast<T *>(smem);                  // [4][c0 * pitch]
@@ -225,6 +226,13 @@ __global__ __launch_bounds__(1024) void k_omp_box(szh_omp_geom g, const T *__res
         if (tid == 0) { ucount[b] = s_un; ucount64[b] = s_un; first[b] = first_v; }
     }
 }
+template <class T, bool DEC, bool VEC>
+__global__ __launch_bounds__(1024) void k_omp_box(szh_omp_geom g, const T *__restrict__ data, T *__restrict__ out, T eb, T recip, int intervals,
+                                                  uint16_t *__restrict__ codes, unsigned *__restrict__ ucount, u64 *__restrict__ ucount64, T *__restrict__ first,
+                                                  const T *__restrict__ unpred, const u64 *__restrict__ uoff)
+{
+    omp_box_body<T, DEC, VEC>(g, data, out, eb, recip, intervals, codes, ucount, ucount64, first, unpred, uoff);
+}
 
 // ---- Huffman packing with one byte-aligned payload per box (sz_omp.c:300-330: `encode` per box into its own buffer, then memcpy)
 __device__ __forceinline__ void omp_load8(const uint16_t *__restrict__ cb, int p0, int bel, bool aligned, uint16_t (&c)[8])
@@ -321,8 +329,8 @@ __global__ __launch_bounds__(256) void k_omp_hdec(int bel, const unsigned char *
 //   k_omp_hdec_lut   a workgroup per box, the payload staged in LDS, decoded with the multi-symbol look-up table of k_hdec_* (hdec_run_lut)
 // =====================================================================================================================
 // ucount / ucount64 (or null): the box's count of verbatim values = its bin 0 (when the sweep did not count them, k_omp_col<.., COUNT = false>)
-__global__ __launch_bounds__(256) void k_omp_hist_box(int bel, const uint16_t *__restrict__ codes, unsigned nbins, int rshift, unsigned *__restrict__ hist_box, unsigned *hist,
-                                                      unsigned *ucount, u64 *ucount64, int nb, int per_wg)
+__device__ __forceinline__ void omp_hist_box_body(int bel, const uint16_t *__restrict__ codes, unsigned nbins, int rshift, unsigned *__restrict__ hist_box, unsigned *hist,
+                                                  unsigned *ucount, u64 *ucount64, int nb, int per_wg)
 {
     SZH_DYN_SMEM(smem);
     unsigned *sh = reinterpret_cast<unsigned *>(smem);
@@ -362,6 +370,11 @@ __global__ __launch_bounds__(256) void k_omp_hist_box(int bel, const uint16_t *_
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void k_omp_hist_box(int bel, const uint16_t *__restrict__ codes, unsigned nbins, int rshift, unsigned *__restrict__ hist_box, unsigned *hist,
+                                                      unsigned *ucount, u64 *ucount64, int nb, int per_wg)
+{
+    omp_hist_box_body(bel, codes, nbins, rshift, hist_box, hist, ucount, ucount64, nb, per_wg);
 }
 // bytes of box b = its bits rounded up (Huffman.c encode: the last byte is padded with zero bits); from the box's histogram ...
 __global__ __launch_bounds__(256) void k_omp_box_bits_h(int nb, unsigned nbins, const unsigned *__restrict__ hist_box, const uint8_t *__restrict__ len, u64 *box_bytes)
@@ -485,8 +498,8 @@ __global__ __launch_bounds__(256) void k_omp_encode_box(szh_omp_geom g, const T 
 // the payloads and the verbatim values of every box begin (two scans), the totals.  Before: k_omp_box_bits_h + two three-launch scans +
 // their gaps, ~50 us for 4096 boxes.
 // have_bytes: box_bytes is already there (k_omp_box_bits_p, many boxes: one workgroup reading every box's histogram took 0.22 ms for 32 768 boxes)
-__global__ __launch_bounds__(1024) void k_omp_layout(int nb, unsigned nbins, const unsigned *__restrict__ hist_box, const u64 *__restrict__ packed, const u64 *__restrict__ ucount64,
-                                                     u64 *box_bytes, u64 *box_off, u64 *uoff, u64 *total_bytes, u64 *total_unpred, int have_bytes)
+__device__ __forceinline__ void omp_layout_body(int nb, unsigned nbins, const unsigned *__restrict__ hist_box, const u64 *__restrict__ packed, const u64 *__restrict__ ucount64,
+                                                u64 *box_bytes, u64 *box_off, u64 *uoff, u64 *total_bytes, u64 *total_unpred, int have_bytes)
 {
     __shared__ u64 sa[16], sb[16];
     __shared__ unsigned char llen[2048];
@@ -520,6 +533,11 @@ __global__ __launch_bounds__(1024) void k_omp_layout(int nb, unsigned nbins, con
     }
     if (tid == 0) { *total_bytes = carry_b; *total_unpred = carry_u; uoff[nb] = carry_u; }
 }
+__global__ __launch_bounds__(1024) void k_omp_layout(int nb, unsigned nbins, const unsigned *__restrict__ hist_box, const u64 *__restrict__ packed, const u64 *__restrict__ ucount64,
+                                                     u64 *box_bytes, u64 *box_off, u64 *uoff, u64 *total_bytes, u64 *total_unpred, int have_bytes)
+{
+    omp_layout_body(nb, nbins, hist_box, packed, ucount64, box_bytes, box_off, uoff, total_bytes, total_unpred, have_bytes);
+}
 
 // Third form (round 4): the two above spend ~50 instructions per code -- eight codes a thread, every one of them an LDS atomic, a block scan
 // and three barriers per 2048 codes.  Here a thread takes 32 CONSECUTIVE codes of a round of 8192 and packs them one after the other
@@ -548,10 +566,10 @@ __device__ __forceinline__ int64_t omp_point_off(const szh_omp_geom &g, int64_t 
 }
 __device__ __forceinline__ void omp_put_bytes(unsigned char *dst, const void *src, int n) { const unsigned char *q = (const unsigned char *)src; for (int i = 0; i < n; ++i) dst[i] = q[i]; }
 template <class T>
-__global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T *__restrict__ data, const uint16_t *__restrict__ codes, const u64 *__restrict__ packed,
-                                                         unsigned nbins, unsigned maxlen, const u64 *__restrict__ box_off, const u64 *__restrict__ box_bytes,
-                                                         const u64 *__restrict__ uoff, const unsigned *__restrict__ ucount, u64 bit0, unsigned *out32,
-                                                         T *__restrict__ unpred, unsigned *bad, szh_omp_tables tb)
+__device__ __forceinline__ void omp_encode_box3_body(szh_omp_geom g, const T *__restrict__ data, const uint16_t *__restrict__ codes, const u64 *__restrict__ packed,
+                                                     unsigned nbins, unsigned maxlen, const u64 *__restrict__ box_off, const u64 *__restrict__ box_bytes,
+                                                     const u64 *__restrict__ uoff, const unsigned *__restrict__ ucount, u64 bit0, unsigned *out32,
+                                                     T *__restrict__ unpred, unsigned *bad, szh_omp_tables tb)
 {
     SZH_DYN_SMEM(smem);
     __shared__ u64 sh[8];
@@ -689,13 +707,21 @@ __global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T
     }
     if (tid == 0 && (((done_bits + 7) >> 3) != box_bytes[b] || done_zero != (u64)ucount[b])) atomicAdd(bad, 1u);
 }
+template <class T>
+__global__ __launch_bounds__(256) void k_omp_encode_box3(szh_omp_geom g, const T *__restrict__ data, const uint16_t *__restrict__ codes, const u64 *__restrict__ packed,
+                                                         unsigned nbins, unsigned maxlen, const u64 *__restrict__ box_off, const u64 *__restrict__ box_bytes,
+                                                         const u64 *__restrict__ uoff, const unsigned *__restrict__ ucount, u64 bit0, unsigned *out32,
+                                                         T *__restrict__ unpred, unsigned *bad, szh_omp_tables tb)
+{
+    omp_encode_box3_body<T>(g, data, codes, packed, nbins, maxlen, box_off, box_bytes, uoff, ucount, bit0, out32, unpred, bad, tb);
+}
 
 // ---- decoding with the look-up table of k_hdec_* (szhip_kernels.h: hdec_run_lut, SZH_LUT_BITS bits and up to four symbols a look-up).
 // A workgroup per box; dynamic LDS: [the payload: byte-swapped words, swizzled (SZH_HDEC_SWZ), `stage_bytes` of them + slack]
 // [the look-up table SZH_LUT_BYTES][the node table when tab_lds].  The box's 256 stretches find their starts as in k_omp_hdec.
-__global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned char *__restrict__ payload, unsigned bytes_before, const u64 *__restrict__ box_off,
-                                                      const u64 *__restrict__ box_bytes, const unsigned *__restrict__ table, int n_nodes, int tab_lds,
-                                                      const uint4 *__restrict__ lut, unsigned stage_bytes, uint16_t *__restrict__ codes, unsigned *__restrict__ bad)
+__device__ __forceinline__ void omp_hdec_lut_body(int bel, const unsigned char *__restrict__ payload, unsigned bytes_before, const u64 *__restrict__ box_off,
+                                                  const u64 *__restrict__ box_bytes, const unsigned *__restrict__ table, int n_nodes, int tab_lds,
+                                                  const uint4 *__restrict__ lut, unsigned stage_bytes, uint16_t *__restrict__ codes, unsigned *__restrict__ bad)
 {
     SZH_DYN_SMEM(smem);
     __shared__ unsigned s_start[257], s_flag[2];
@@ -754,6 +780,12 @@ __global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned ch
     int64_t oend = wr ? (int64_t)o + cnt : (int64_t)o;
     if (oend > bel) oend = bel;
     hdec_run_lut<true>(l, total, ltab, table, lut4, wr ? start : 0u, wr ? limit : 0u, &e, out, (int64_t)o, oend, wr);
+}
+__global__ __launch_bounds__(256) void k_omp_hdec_lut(int bel, const unsigned char *__restrict__ payload, unsigned bytes_before, const u64 *__restrict__ box_off,
+                                                      const u64 *__restrict__ box_bytes, const unsigned *__restrict__ table, int n_nodes, int tab_lds,
+                                                      const uint4 *__restrict__ lut, unsigned stage_bytes, uint16_t *__restrict__ codes, unsigned *__restrict__ bad)
+{
+    omp_hdec_lut_body(bel, payload, bytes_before, box_off, box_bytes, table, n_nodes, tab_lds, lut, stage_bytes, codes, bad);
 }
 
 // =====================================================================================================================

@@ -1,0 +1,128 @@
+// szh_ompbatch.h -- the OpenMP container (szh_omp.h, szh_ompcol.h) over the boxes of MANY same-shape arrays in one launch
+// (szhip_compress_omp_batch / szhip_decompress_omp_batch, include/szhip.h).
+// Every kernel of the container is indexed by box number and its boxes are independent, so a batch is the same kernels with the array as the grid's second
+// dimension: blockIdx.x counts what it counts in the single call (boxes, pairs of boxes, groups of boxes), blockIdx.y picks the array.  What differs from array to
+// array -- base pointer, bound, interval count, code table, the places of its tables and of its stream -- is ONE record per array in a device table; a workgroup
+// reads its record once through list[blockIdx.y] (the record is uniform per workgroup: plain loads through a const __restrict__ pointer, scalar on the GPU) and runs
+// the `*_body` function the single call's kernel runs, with the record's values where that kernel has its arguments.  Nothing of a body is repeated here.
+// `list`: the arrays a launch covers (all batched ones; those of one sweep form; those with verbatim values), so that one table serves every launch of the call.
+#pragma once
+
+struct szh_ompb_rec {
+    const void *data; void *out;               // the array (compress: read; decompress: written)
+    double eb, recip;                          // the bound and 1 / bound, both already rounded to the array's type
+    unsigned intervals; int rshift;            // interval count; k_omp_hist_box: log2 of the lane-private copies of its bins
+    uint16_t *codes;                           // nb * bel codes
+    unsigned *ucount; u64 *ucount64; void *first;      // per box: count of verbatim values, first value
+    int count_in_hist, maxlen;                 // compress: the histogram pass fills ucount (the column sweep leaves the counting out); longest code word
+    unsigned *hist_box, *hist;                 // compress: nb * intervals bins, intervals bins
+    unsigned *radius_hist;                     // compress: the interval optimiser's radius histogram of this array
+    u64 *box_bytes, *box_off, *uoff;           // per box: payload bytes, payload offset, rank of its first verbatim value (nb + 1 entries)
+    u64 *totals;                               // {payload bytes, verbatim values, boxes in error, samples within the bound}: this array's SM_SCRATCH / SM_TOTAL_UNPRED / SM_ERR / SM_WITHIN
+    const u64 *packed;                         // compress: the code table `code << 8 | len`
+    unsigned char *stream; const unsigned char *hdr; unsigned hdr_len, pad_;     // compress: where its stream is built (4-byte aligned, zeroed); its header bytes
+    u64 off_ucount, off_first, off_unpred, off_sizes, off_pay;                   // compress: the stream's tables
+    void *unpred;                              // the array's verbatim values at an aligned address (compress: written; decompress: read)
+    const unsigned char *payload; unsigned bytes_before; int n_nodes, tab_lds, pad2_;     // decompress: its payloads, what k_omp_hdec_lut takes per stream
+    const unsigned *table; uint4 *lut;         // decompress: the node table, the look-up table built from it
+    unsigned *vflags;                          // decompress, column form: nb * fw flag words (k_omp_scatter)
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_sample(szh_geom3 G, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, int64_t nrows, int sd, unsigned max_radius)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    sample_body<T, false>(G, (const T *)r.data, nrows, sd, r.eb, (T)0, max_radius, r.radius_hist, nullptr, r.totals + 3);
+}
+
+template <class T> __device__ __forceinline__ void ompb_sweep_args(const szh_omp_geom &g, const szh_ompb_rec &r, bool dec, int fw, szh_oc::sweep_args<T> &a)
+{
+    a.g = g; a.data = dec ? nullptr : (const T *)r.data; a.out = dec ? (T *)r.out : nullptr;
+    a.eb = (T)r.eb; a.recip = (T)r.recip; a.intervals = (int)r.intervals; a.codes = r.codes;
+    a.ucount = dec ? (unsigned *)(r.totals + 2) : r.ucount; a.ucount64 = dec ? nullptr : r.ucount64; a.first = (T *)r.first;
+    a.uoff = dec ? r.uoff : nullptr; a.vflags = dec ? r.vflags : nullptr; a.fw = dec ? fw : 0;
+}
+// two boxes of the SAME array per wavefront (the box count of an array is even: omp_col_applies).  The sweep itself is szh_oc::sweep; these are the dozen lines of
+// k_omp_col around it once more (k_omp_col stays as it is, to the letter: its register allocation is what two wavefronts per SIMD hang on)
+template <class T, int C1, int C2, bool DEC, bool COUNT>
+__global__ __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) void k_ompb_col(szh_omp_geom g, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, int fw)
+{
+    typedef szh_oc::shape<T, C1, C2> S;
+    __shared__ __attribute__((aligned(16))) unsigned char ring_raw[S::RS * S::PITCH];
+    __shared__ unsigned flags_raw[DEC ? S::NB * OC_FLAG_WORDS : 1];
+    OC_LDS unsigned char *ring = (OC_LDS unsigned char *)ring_raw;
+    OC_LDS unsigned *fl = (OC_LDS unsigned *)flags_raw;
+    szh_oc::sweep_args<T> a;
+    ompb_sweep_args<T>(g, recs[list[blockIdx.y]], DEC, fw, a);
+    if (!DEC) { szh_oc::sweep<T, C1, C2, szh_oc::M_CMP, COUNT> s(ring, fl, a); s.run(); }
+    else {
+        const int b0 = (int)blockIdx.x * S::NB;
+        const bool verb = a.uoff[b0 + S::NB] != a.uoff[b0];          // (uniform)
+        if (verb) { szh_oc::sweep<T, C1, C2, szh_oc::M_DECV> s(ring, fl, a); s.run(); }
+        else { szh_oc::sweep<T, C1, C2, szh_oc::M_DEC> s(ring, fl, a); s.run(); }
+    }
+}
+template <class T, bool DEC, bool VEC>
+__global__ __launch_bounds__(1024) void k_ompb_box(szh_omp_geom g, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    omp_box_body<T, DEC, VEC>(g, DEC ? nullptr : (const T *)r.data, DEC ? (T *)r.out : nullptr, (T)r.eb, (T)r.recip, (int)r.intervals, r.codes,
+                              DEC ? (unsigned *)(r.totals + 2) : r.ucount, DEC ? nullptr : r.ucount64, (T *)r.first, DEC ? (const T *)r.unpred : nullptr, DEC ? r.uoff : nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_ompb_hist_box(int bel, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, int nb, int per_wg)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    omp_hist_box_body(bel, r.codes, r.intervals, r.rshift, r.hist_box, r.hist, r.count_in_hist ? r.ucount : nullptr, r.count_in_hist ? r.ucount64 : nullptr, nb, per_wg);
+}
+// one workgroup per array: every box its size and its place inside its OWN stream, the array's totals
+__global__ __launch_bounds__(1024) void k_ompb_layout(int nb, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    omp_layout_body(nb, r.intervals, r.hist_box, r.packed, r.ucount64, r.box_bytes, r.box_off, r.uoff, r.totals, r.totals + 1, 0);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_encode_box3(szh_omp_geom g, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    szh_omp_tables tb;
+    tb.stream = r.stream; tb.hdr = r.hdr; tb.hdr_len = r.hdr_len;
+    tb.off_ucount = r.off_ucount; tb.off_first = r.off_first; tb.off_unpred = r.off_unpred; tb.off_sizes = r.off_sizes; tb.first = r.first;
+    omp_encode_box3_body<T>(g, (const T *)r.data, r.codes, r.packed, r.intervals, (unsigned)r.maxlen, r.box_off, r.box_bytes, r.uoff, r.ucount, r.off_pay * 8,
+                            (unsigned *)r.stream, (T *)r.unpred, (unsigned *)(r.totals + 2), tb);
+}
+
+__global__ __launch_bounds__(256) void k_ompb_build_lut(const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    hdec_build_lut_body(r.table, r.lut);
+}
+__global__ __launch_bounds__(256) void k_ompb_hdec_lut(int bel, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, unsigned stage_bytes)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    omp_hdec_lut_body(bel, r.payload, r.bytes_before, r.box_off, r.box_bytes, r.table, r.n_nodes, r.tab_lds, r.lut, stage_bytes, r.codes, (unsigned *)(r.totals + 2));
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_scatter(szh_omp_geom g, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, int fw)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    omp_scatter_body<T>(g, r.codes, r.uoff, (const T *)r.unpred, (T *)r.out, (unsigned *)(r.totals + 2), r.vflags, fw);
+}
+
+// Pieces of byte arrays that lie anywhere (the caller's streams, the tables inside them) to places in ONE destination buffer, a workgroup per span
+// {source address, destination offset, bytes}: 16 bytes per lane where source and destination are aligned alike, else byte by byte (as k_omp_gather)
+__global__ __launch_bounds__(256) void k_ompb_fetch(unsigned char *__restrict__ dst, const u64 *__restrict__ spans)
+{
+    const u64 *sp = spans + 3 * (u64)blockIdx.x;
+    const unsigned char *s = reinterpret_cast<const unsigned char *>((uintptr_t)sp[0]);
+    unsigned char *d = dst + sp[1];
+    const u64 n = sp[2], tid = threadIdx.x;
+    if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0) {
+        u64 head = (16u - (unsigned)((uintptr_t)s & 15u)) & 15u;
+        if (head > n) head = n;
+        const u64 n16 = (n - head) / 16, tail = head + n16 * 16;
+        if (tid < head) d[tid] = s[tid];
+        for (u64 i = tid; i < n16; i += 256) reinterpret_cast<uint4 *>(d + head)[i] = reinterpret_cast<const uint4 *>(s + head)[i];
+        if (tail + tid < n) d[tail + tid] = s[tail + tid];            // (fewer than 16 bytes)
+    } else for (u64 i = tid; i < n; i += 256) d[i] = s[i];
+}

@@ -431,8 +431,8 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) void k_omp_col(szh_oc
 // `vflags` (or null): per box `fw` words (zeroed by the caller), bit g = rows [g RPL, (g + 1) RPL) of the box, RPL = 16 / sizeof(T), hold a verbatim
 // value -- the only rows of `out` the sweep has to read
 template <class T>
-__global__ __launch_bounds__(256) void k_omp_scatter(szh_omp_geom g, const uint16_t *__restrict__ codes, const u64 *__restrict__ uoff,
-                                                     const T *__restrict__ unpred, T *__restrict__ out, unsigned *bad, unsigned *vflags, int fw)
+__device__ __forceinline__ void omp_scatter_body(szh_omp_geom g, const uint16_t *__restrict__ codes, const u64 *__restrict__ uoff,
+                                                 const T *__restrict__ unpred, T *__restrict__ out, unsigned *bad, unsigned *vflags, int fw)
 {
     __shared__ u64 sh[8];
     __shared__ unsigned lflags[OC_FLAG_WORDS];
@@ -465,4 +465,10 @@ __global__ __launch_bounds__(256) void k_omp_scatter(szh_omp_geom g, const uint1
     }
     if (flags) { __syncthreads(); for (int i = threadIdx.x; i < fw; i += 256) vflags[(int64_t)b * fw + i] = lflags[i]; }
     if (threadIdx.x == 0 && done != cap) atomicAdd(bad, 1u);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_omp_scatter(szh_omp_geom g, const uint16_t *__restrict__ codes, const u64 *__restrict__ uoff,
+                                                     const T *__restrict__ unpred, T *__restrict__ out, unsigned *bad, unsigned *vflags, int fw)
+{
+    omp_scatter_body<T>(g, codes, uoff, unpred, out, bad, vflags, fw);
 }

@@ -146,7 +146,8 @@ struct szhip_ctx {
     // workspaces (grow-only)
     DevBuf lor_bits, reg_flags, reg_rank, coef_compact, in, out, codes_nat, codes_blk, coef, blk_lor, faceI, faceJ, rb_down, rb_right, rb_vals, pt_flags, feed_word, progress, order, small, hist, col_zeros, col_zeros64,
         seg_bits, seg_zeros, seg_bitoff, seg_zoff, seg_hist, seg_tab, col_off, partial, samples, unpred, stream_buf, chunk_bits, chunk_off, code_tab, len_tab, dec_tab,
-        starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe, book_tree, book_rec, book_stage;
+        starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe, book_tree, book_rec, book_stage,
+        batch_rec, batch_blob;               // szhip_*_omp_batch: the per-array table; the blob of streams (the single calls inside a batch use stream_buf)
     void *pinned = nullptr; size_t pinned_cap = 0;
     void *pinned2 = nullptr; size_t pinned2_cap = 0;   // target of the second stream's copies (indicator bits, regression-block count)
     // bulk copies between the caller's pageable arrays and the device: SZH_STAGE_T host threads, two pinned buffers + events each
@@ -182,6 +183,7 @@ namespace {
 #include "szhip_sz14.inc"    // SZ 1.4 container, MSST19
 #include "szhip_pwr.inc"     // point-wise relative bounds
 #include "szhip_omp.inc"     // the reference's OpenMP container
+#include "szhip_ompbatch.inc" // ... over many same-shape arrays in one call
 
 } // namespace
 
@@ -288,7 +290,7 @@ void szhip_destroy(szhip_ctx *ctx)
                       &ctx->order, &ctx->small, &ctx->hist, &ctx->col_zeros, &ctx->col_zeros64, &ctx->seg_bits, &ctx->seg_zeros, &ctx->seg_bitoff, &ctx->seg_zoff, &ctx->seg_hist, &ctx->seg_tab, &ctx->col_off, &ctx->partial,
                       &ctx->samples, &ctx->unpred, &ctx->stream_buf, &ctx->chunk_bits, &ctx->chunk_off, &ctx->code_tab,
                       &ctx->len_tab, &ctx->dec_tab, &ctx->starts, &ctx->ends, &ctx->counts, &ctx->offs, &ctx->dirty, &ctx->zcnt, &ctx->zpos,
-                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe, &ctx->book_tree, &ctx->book_rec, &ctx->book_stage};
+                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe, &ctx->book_tree, &ctx->book_rec, &ctx->book_stage, &ctx->batch_rec, &ctx->batch_blob};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->pinned2) hipHostFree(ctx->pinned2);
@@ -490,6 +492,48 @@ int szhip_decompress_omp(szhip_ctx *ctx, int dtype, const unsigned char *stream,
     TRY(check_alignment_set_device(ctx, dtype, out));
     return synced_on_failure(ctx,
                BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, 0, 0, stats));
+}
+
+// the refusals of a batch call, before anything is launched or written: SZHIP_ERR_ARG
+static int batch_args(szhip_ctx *ctx, int dtype, const szhip_batch_item *items, int count, size_t r0, size_t r1, size_t r2, bool compress)
+{
+    if (!ctx || !items || count < 1 || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    for (int i = 0; i < count; ++i) {
+        const szhip_batch_item &it = items[i];
+        const void *values = compress ? it.data : (const void *)it.out;
+        if (!values || (compress ? !it.meta || !(it.eb > 0) || !((dtype == SZHIP_F32 ? (double)(float)it.eb : it.eb) > 0) : !it.stream || it.body_off >= it.stream_len)) {
+            snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: a null pointer, a bound that is not positive or an empty stream", i);
+            return SZHIP_ERR_ARG;
+        }
+        if (((uintptr_t)values & (dtype == SZHIP_F32 ? 3u : 7u)) != 0) {
+            snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: pointer %p is not aligned to its %d-byte elements", i, values, dtype == SZHIP_F32 ? 4 : 8);
+            return SZHIP_ERR_ARG;
+        }
+    }
+    return SZHIP_OK;
+}
+
+int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
+                             const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+{
+    if (!params || !blob || !blob_size || thread_num < 1) return SZHIP_ERR_ARG;
+    TRY(batch_args(ctx, dtype, items, count, r0, r1, r2, true));
+    if (out_on_device != 0 && out_on_device != 1) { snprintf(ctx->err, sizeof(ctx->err), "a batch writes into a host blob (0) or the context's device blob (1)"); return SZHIP_ERR_UNSUP; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) { items[i].offset = items[i].size = 0; items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
+    *blob = nullptr; *blob_size = 0;
+    return synced_on_failure(ctx,
+               BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, r0, r1, r2, thread_num, params, meta_len, out_on_device, blob, blob_size, stats));
+}
+
+int szhip_decompress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
+                               int out_on_device, szhip_stats *stats)
+{
+    TRY(batch_args(ctx, dtype, items, count, r0, r1, r2, false));
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) { items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
+    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, r0, r1, r2, out_on_device, stats));
 }
 
 int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -768,7 +812,7 @@ int szhip_debug_fetch(szhip_ctx *ctx, int which, void *dst, size_t bytes)
     if (!ctx || !dst) return SZHIP_ERR_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     DevBuf *bufs[] = {&ctx->coef, &ctx->blk_lor, &ctx->codes_nat, &ctx->codes_blk, &ctx->hist, &ctx->col_zeros, &ctx->col_off,
-                      &ctx->unpred, &ctx->stream_buf, &ctx->rb_down, &ctx->rb_right, &ctx->small, &ctx->in};
+                      &ctx->unpred, &ctx->stream_buf, &ctx->rb_down, &ctx->rb_right, &ctx->small, &ctx->in, &ctx->batch_blob};
     if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0]))) return SZHIP_ERR_ARG;
     if (!bufs[which]->p || bufs[which]->cap < bytes) return SZHIP_ERR_ARG;
     HIPCHK(hipStreamSynchronize(ctx->stream));

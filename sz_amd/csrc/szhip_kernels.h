@@ -373,8 +373,8 @@ __global__ __launch_bounds__(256) void k_gather_mean(const T *__restrict__ data,
 // instead of 48.  (Round 4 tried one thread per SAMPLE instead of per row: slower -- 0.23 ms against 0.10-0.16 -- the pass is bound by
 // the 64-byte sectors its scattered reads touch, ~0.35 GB at 512^3, not by the five dependent rounds of a row.)
 template <class T, bool FREQ>
-__global__ __launch_bounds__(256) void k_sample(szh_geom3 G, const T *__restrict__ data, int64_t nrows, int sd, double ebD, T mean,
-                                                unsigned max_radius, unsigned *radius_hist, unsigned *freq_hist, u64 *within)
+__device__ __forceinline__ void sample_body(szh_geom3 G, const T *__restrict__ data, int64_t nrows, int sd, double ebD, T mean,
+                                            unsigned max_radius, unsigned *radius_hist, unsigned *freq_hist, u64 *within)
 {
     __shared__ unsigned sh_r[SZH_LDS_RADIUS_BINS];
     __shared__ unsigned sh_f[FREQ ? 8192 : 1];
@@ -405,6 +405,12 @@ __global__ __launch_bounds__(256) void k_sample(szh_geom3 G, const T *__restrict
     __syncthreads();
     for (int i = threadIdx.x; i < SZH_LDS_RADIUS_BINS; i += 256) if (sh_r[i]) atomicAdd(&radius_hist[i], sh_r[i]);
     if (FREQ) for (int i = threadIdx.x; i < 8192; i += 256) if (sh_f[i]) atomicAdd(&freq_hist[i], sh_f[i]);
+}
+template <class T, bool FREQ>
+__global__ __launch_bounds__(256) void k_sample(szh_geom3 G, const T *__restrict__ data, int64_t nrows, int sd, double ebD, T mean,
+                                                unsigned max_radius, unsigned *radius_hist, unsigned *freq_hist, u64 *within)
+{
+    sample_body<T, FREQ>(G, data, nrows, sd, ebD, mean, max_radius, radius_hist, freq_hist, within);
 }
 // The same samples for a DEGENERATE 3-D array (an extent of 1 in dim 0 or dim 1): the reference's walk (sz_float.c:4644-4702 and the
 // optimiser of the SZ 2.1 path) does not see rows and planes, it advances ONE position through the flat array -- with r2 = 1 its row counter
@@ -1306,7 +1312,7 @@ __device__ __forceinline__ unsigned hdec_w32(const SZH_LDS unsigned *l, unsigned
 #define SZH_LUT_BITS 10
 #define SZH_LUT_SIZE (1 << SZH_LUT_BITS)
 #define SZH_LUT_BYTES (SZH_LUT_SIZE * 16 + SZH_LUT_SIZE * 4)      /* uint4 entries, then the w words */
-__global__ __launch_bounds__(256) void k_hdec_build_lut(const unsigned *__restrict__ table, uint4 *lut)
+__device__ __forceinline__ void hdec_build_lut_body(const unsigned *__restrict__ table, uint4 *lut)
 {
     const unsigned idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= SZH_LUT_SIZE) return;
@@ -1324,6 +1330,7 @@ __global__ __launch_bounds__(256) void k_hdec_build_lut(const unsigned *__restri
     lut[idx] = e;
     reinterpret_cast<unsigned *>(lut + SZH_LUT_SIZE)[idx] = e.w;
 }
+__global__ __launch_bounds__(256) void k_hdec_build_lut(const unsigned *__restrict__ table, uint4 *lut) { hdec_build_lut_body(table, lut); }
 // decodes from LOCAL bit `pos` to the first codeword boundary at or after `limit` (never past `total`, the stream's end in local
 // bits); *endpos = that boundary; returns the number of symbols.
 // WRITE: the thread's symbols are the run out[o, oend), assembled as aligned groups of 8 in two 64-bit registers (lo: slots 0-3,
@@ -1759,6 +1766,7 @@ __global__ void k_probe_touch(unsigned long long *p) { *p = 1; }
 #include "szh_msst.h"
 #include "szh_omp.h"
 #include "szh_ompcol.h"
+#include "szh_ompbatch.h"
 #include "szh_beam.h"
 #include "szh_book.h"
 #include "szh_segenc.h"

@@ -1,0 +1,606 @@
+// szhip_ompbatch.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace, behind szhip_omp.inc): the OpenMP container over many
+// same-shape arrays in one call (include/szhip.h: szhip_compress_omp_batch, szhip_decompress_omp_batch; kernels: szh_ompbatch.h; DESIGN section 4.5.3).
+// The steps are those of omp_call / omp_dec, each ONE launch with the array as the grid's second dimension; what a step of the single call keeps in members is here a
+// per-array record (szh_ompb_rec) in a device table that is uploaded whole whenever the host has learnt something new about the arrays (the interval counts, the books).
+// An array the shared launches do not cover goes through compress_omp_impl / decompress_omp_impl from inside the call.
+// =====================================================================================================================
+static int omp_form(const szh_omp_geom &g, const void *base, size_t elem, size_t r1, size_t r2)
+{
+    if (omp_col_applies(g, base, r2 * elem, r1 * r2 * elem)) return 3;
+    return g.vec && ((uintptr_t)base & 15u) == 0 ? 4 : 5;
+}
+static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+static size_t up64(size_t v) { return (v + 63) / 64 * 64; }
+static int ompb_limits(szhip_ctx *ctx, int count, size_t nb, size_t n)
+{
+    if (count > 65535 || (size_t)count * nb > ((size_t)1 << 22) || (size_t)count * n >= ((size_t)1 << 32))
+        FAIL(SZHIP_ERR_UNSUP, "OpenMP-container batch: %d arrays of %zu boxes and %zu values (at most 65535 arrays, 2^22 boxes and 2^32 - 1 values in all)", count, nb, n);
+    return SZHIP_OK;
+}
+// the device table of a batch in ctx->batch_rec: [totals: 4 u64 per array][records][LISTS lists of `count` array numbers][what a version of the table adds behind]
+enum { OMPB_L_ALL = 0, OMPB_L_F3, OMPB_L_F4, OMPB_L_F5, OMPB_L_ENT, OMPB_L_PACK, OMPB_LISTS };
+struct ompb_table {
+    szhip_ctx *ctx; int count;
+    std::vector<szh_ompb_rec> rec; std::vector<int> list[OMPB_LISTS];
+    size_t o_rec, o_list, o_extra;
+    std::vector<unsigned char> image[3];                    // the host copies of the uploads (one per version: a pageable source stays untouched until the next synchronisation)
+    ompb_table(szhip_ctx *c, int n) : ctx(c), count(n), rec((size_t)n)
+    {
+        memset(rec.data(), 0, rec.size() * sizeof(szh_ompb_rec));
+        o_rec = up64((size_t)n * 32); o_list = o_rec + (size_t)n * sizeof(szh_ompb_rec); o_extra = up64(o_list + (size_t)OMPB_LISTS * n * 4);
+    }
+    int reserve(size_t extra) { return ensure(ctx, ctx->batch_rec, o_extra + extra + 64); }
+    unsigned char *dev() const { return (unsigned char *)ctx->batch_rec.p; }
+    u64 *totals(int i) const { return (u64 *)dev() + 4 * (size_t)i; }
+    const szh_ompb_rec *d_rec() const { return (const szh_ompb_rec *)(dev() + o_rec); }
+    const int *d_list(int which) const { return (const int *)(dev() + o_list) + (size_t)which * count; }
+    int clear_totals() { HIPCHK(hipMemsetAsync(dev(), 0, (size_t)count * 32, ctx->stream)); return SZHIP_OK; }
+    // records, lists and `extra` (placed at o_extra) to the device
+    int upload(int version, const std::vector<unsigned char> &extra)
+    {
+        std::vector<unsigned char> &im = image[version];
+        im.assign(o_extra - o_rec + extra.size(), 0);
+        memcpy(im.data(), rec.data(), rec.size() * sizeof(szh_ompb_rec));
+        for (int l = 0; l < OMPB_LISTS; ++l) if (!list[l].empty()) memcpy(im.data() + (o_list - o_rec) + (size_t)l * count * 4, list[l].data(), list[l].size() * 4);
+        if (!extra.empty()) memcpy(im.data() + (o_extra - o_rec), extra.data(), extra.size());
+        HIPCHK(hipMemcpyAsync(dev() + o_rec, im.data(), im.size(), hipMemcpyHostToDevice, ctx->stream));
+        return SZHIP_OK;
+    }
+};
+
+template <class T>
+int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
+                            const szhip_params *prm, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+{
+    call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
+    szh_omp_geom g;
+    TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+    const size_t n = r0 * r1 * r2, nb = (size_t)g.nb;
+    TRY(ompb_limits(ctx, count, nb, n));
+    S.n_elements = (uint64_t)count * n; S.n_blocks = (uint64_t)count * nb;
+    enum { BATCH, EARLY, LATE, FAILED };
+    std::vector<int> state((size_t)count, BATCH);
+    // an array that misses box_hist's conditions whatever its intervals, or whose samples the walk of k_sample_walk takes: every array through the single call
+    const bool shared = g.bel % 8 == 0 && r0 > 1 && r1 > 1;
+    if (!shared) state.assign((size_t)count, EARLY);
+    // ---- 1. host arrays one behind the other into the context's input buffer
+    const size_t in_stride = up16(n * sizeof(T));
+    std::vector<const T *> d_in((size_t)count);
+    if (data_on_device) for (int i = 0; i < count; ++i) d_in[i] = (const T *)items[i].data;
+    else {
+        TRY(ensure(ctx, ctx->in, (size_t)count * in_stride));
+        for (int i = 0; i < count; ++i) d_in[i] = (const T *)((const char *)ctx->in.p + (size_t)i * in_stride);
+        if ((size_t)count * in_stride <= ((size_t)64 << 20)) {
+            TRY(ensure_pinned3(ctx, (size_t)count * in_stride));
+            for (int i = 0; i < count; ++i) memcpy((char *)ctx->pinned3 + (size_t)i * in_stride, items[i].data, n * sizeof(T));
+            HIPCHK(hipMemcpyAsync(ctx->in.p, ctx->pinned3, (size_t)count * in_stride, hipMemcpyHostToDevice, st));
+        } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)ctx->in.p + (size_t)i * in_stride, items[i].data, n * sizeof(T), true));
+    }
+    // the single call for array i, from the device copy of it: its stream on the host until the blob is laid out
+    std::vector<std::vector<unsigned char>> fb((size_t)count);
+    auto single = [&](int i) {
+        unsigned char *p = nullptr; size_t len = 0; szhip_stats s1;
+        memset(&s1, 0, sizeof(s1));
+        const int rc = compress_omp_impl<T>(ctx, d_in[i], 1, r0, r1, r2, r1 * r2, r2, items[i].eb, thread_num, prm, items[i].meta, meta_len, 0, &p, &len, &s1);
+        items[i].rc = rc; items[i].batched = 0;
+        if (rc == SZHIP_OK) {
+            fb[i].assign(p, p + len); free(p);
+            items[i].intervals = s1.intervals; items[i].n_unpred = s1.n_unpred; items[i].quant_kernel = s1.quant_kernel;
+        } else { hipStreamSynchronize(st); state[i] = FAILED; }
+    };
+    // ---- the per-array tables of the shared launches
+    const unsigned max_radius = prm->max_quant_intervals / 2;
+    const bool optimise = prm->quantization_intervals == 0;
+    ompb_table tab(ctx, count);
+    uint16_t *d_codes = nullptr; unsigned *d_hist = nullptr;
+    if (shared) {
+        TRY(tab.reserve(0));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
+        TRY(ensure(ctx, ctx->zcnt, (size_t)count * nb * 4)); TRY(ensure(ctx, ctx->samples, (size_t)count * nb * sizeof(T)));
+        TRY(ensure(ctx, ctx->col_zeros64, (size_t)count * nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)count * (nb + 1) * 8));
+        TRY(ensure(ctx, ctx->reg_flags, (size_t)count * nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)count * nb * 8));
+        TRY(ensure(ctx, ctx->hist, std::max((size_t)count * std::max<size_t>(optimise ? max_radius : 0, 1024), (size_t)65536 + 8192) * 4 + 8192 * 4 + 64));      // (never less than a single call asks for: none of them inside this call may move it)
+        d_codes = (uint16_t *)ctx->codes_nat.p; d_hist = (unsigned *)ctx->hist.p;
+    }
+    auto fill_static = [&]() {                               // (again after every tab.reserve: the totals move with the table)
+        for (int i = 0; i < count; ++i) {
+            szh_ompb_rec &r = tab.rec[i];
+            const T ebT = (T)items[i].eb;
+            r.data = d_in[i]; r.eb = (double)ebT; r.recip = (double)(T)(1 / ebT);
+            r.codes = d_codes + (size_t)i * n;
+            r.ucount = (unsigned *)ctx->zcnt.p + (size_t)i * nb; r.ucount64 = (u64 *)ctx->col_zeros64.p + (size_t)i * nb; r.first = (T *)ctx->samples.p + (size_t)i * nb;
+            r.box_bytes = (u64 *)ctx->reg_flags.p + (size_t)i * nb; r.box_off = (u64 *)ctx->reg_rank.p + (size_t)i * nb; r.uoff = (u64 *)ctx->col_off.p + (size_t)i * (nb + 1);
+            r.totals = tab.totals(i);
+        }
+    };
+    // ---- 2. the interval optimiser: one sampling launch, one read-back, pick_intervals per array
+    std::vector<unsigned> iv((size_t)count, prm->quantization_intervals);
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    if (shared && optimise) {
+        const szh_geom3 G = szh_make_geom3((int)r0, (int)r1, (int)r2);
+        const int64_t nrows = szh_sample_row_limit(G, prm->sample_distance);
+        TRY(ensure_pinned(ctx, (size_t)count * max_radius * 4 + 64));
+        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)count * max_radius * 4, st));
+        TRY(tab.clear_totals());
+        fill_static();
+        tab.list[OMPB_L_ALL].resize((size_t)count);
+        for (int i = 0; i < count; ++i) { tab.rec[i].radius_hist = d_hist + (size_t)i * max_radius; tab.list[OMPB_L_ALL][i] = i; }
+        TRY(tab.upload(0, {}));
+        if (nrows > 0) {
+            const int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
+            hipLaunchKernelGGL((k_ompb_sample<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), nrows, prm->sample_distance, max_radius);
+            HIPCHK(hipGetLastError());
+        }
+        const unsigned *h_rh = (const unsigned *)ctx->pinned;
+        HIPCHK(hipMemcpyAsync(ctx->pinned, d_hist, (size_t)count * max_radius * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double h0 = now_ms();
+        for (int i = 0; i < count; ++i) iv[i] = pick_intervals(h_rh + (size_t)i * max_radius, max_radius, prm->pred_threshold, 32u);
+        cb.host_ms += now_ms() - h0;
+    }
+    HIPCHK(hipEventRecord(ctx->ev[1], st));
+    if (shared && optimise) { HIPCHK(hipEventSynchronize(ctx->ev[1])); float ms = 0; hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_prequant = ms; }
+    // ---- who stays in the shared launches (box_hist of the single call), in which sweep form; the others run now, while nothing of the batch is on the device yet
+    std::vector<size_t> o_hb((size_t)count, 0);
+    size_t hb_bytes = 0, hist_lds = 16;
+    for (int i = 0; i < count; ++i) {
+        if (state[i] == BATCH && (iv[i] > 65536 || iv[i] < 4)) {
+            state[i] = FAILED; items[i].rc = SZHIP_ERR_UNSUP;
+            snprintf(ctx->err, sizeof(ctx->err), "quantization interval count %u outside [4,65536]", iv[i]);
+        }
+        if (state[i] == BATCH && (iv[i] > 1024 || nb * iv[i] * 4 > ((size_t)64 << 20))) state[i] = EARLY;
+        if (state[i] == EARLY) { single(i); continue; }
+        if (state[i] != BATCH) continue;
+        const int form = omp_form(g, d_in[i], sizeof(T), r1, r2);
+        items[i].intervals = iv[i]; items[i].quant_kernel = form; items[i].batched = 1;
+        tab.list[form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
+        tab.list[OMPB_L_ENT].push_back(i);
+        int rshift = 0;
+        while ((iv[i] << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)iv[i] << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
+        szh_ompb_rec &r = tab.rec[i];
+        r.intervals = iv[i]; r.rshift = rshift; r.count_in_hist = form == 3 ? 1 : 0;
+        hist_lds = std::max(hist_lds, ((size_t)iv[i] << rshift) * 4);
+        o_hb[i] = hb_bytes; hb_bytes += nb * iv[i] * 4;
+    }
+    const int n_ent = (int)tab.list[OMPB_L_ENT].size();
+    if (shared) { d_codes = (uint16_t *)ctx->codes_nat.p; d_hist = (unsigned *)ctx->hist.p; }
+    std::vector<std::vector<unsigned char>> hdr((size_t)count);
+    std::vector<std::vector<u64>> packed((size_t)count);
+    std::vector<u64> E((size_t)count, 0), total_bits((size_t)count, 0);
+    std::vector<size_t> off_pay((size_t)count, 0), cap_len((size_t)count, 0);
+    size_t lds3_max = 16;
+    if (n_ent > 0) {
+        // ---- 3. the sweeps, one launch per form
+        TRY(ensure(ctx, ctx->chunk_bits, hb_bytes));
+        TRY(tab.clear_totals());
+        HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)count * 1024 * 4, st));
+        fill_static();
+        for (int i : tab.list[OMPB_L_ENT]) { tab.rec[i].hist_box = (unsigned *)((char *)ctx->chunk_bits.p + o_hb[i]); tab.rec[i].hist = d_hist + (size_t)i * 1024; }
+        TRY(tab.upload(1, {}));
+        HIPCHK(hipEventRecord(ctx->ev[2], st));
+        const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size();
+        const int rows = g.c0 * g.c1;
+        const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
+        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3), 0);
+        if (n4) hipLaunchKernelGGL((k_ompb_box<T, false, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F4));
+        if (n5) hipLaunchKernelGGL((k_ompb_box<T, false, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[3], st));
+        S.quant_kernel_launches += (n3 ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
+        // ---- 4. the boxes' histograms and every array's own: one launch, one read-back
+        const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
+        hipLaunchKernelGGL(k_ompb_hist_box, dim3((unsigned)((nb + hist_per_wg - 1) / hist_per_wg), (unsigned)n_ent), dim3(256), hist_lds, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT),
+                           (int)nb, hist_per_wg);
+        HIPCHK(hipGetLastError());
+        TRY(ensure_pinned(ctx, (size_t)count * 1024 * 4 + 64));
+        HIPCHK(hipMemcpyAsync(ctx->pinned, d_hist, (size_t)count * 1024 * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // ---- 5. the books, the headers (hist_and_book of the single call, per array)
+        const double h0 = now_ms();
+        const unsigned *h_hist = (const unsigned *)ctx->pinned;
+        for (int i : tab.list[OMPB_L_ENT]) {
+            std::vector<u64> tab_code; std::vector<uint8_t> tab_len; unsigned maxlen = 0;
+            const unsigned *hh = h_hist + (size_t)i * 1024;
+            E[i] = hh[0]; items[i].n_unpred = E[i];
+            const huff_ptr hf = host_book(hh, iv[i], tab_code, tab_len, &maxlen);
+            if (!hf) { state[i] = FAILED; items[i].rc = SZHIP_ERR_INTERNAL; snprintf(ctx->err, sizeof(ctx->err), "Huffman build failed"); continue; }
+            const size_t tree_bytes = szhost_huff_tree_size(hf.get());
+            total_bits[i] = hf->total_bits;
+            const size_t hdr_len = meta_len + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes;
+            szh_ompb_rec &r = tab.rec[i];
+            r.hdr_len = (unsigned)hdr_len; r.maxlen = (int)maxlen;
+            r.off_ucount = hdr_len; r.off_first = r.off_ucount + nb * 4; r.off_unpred = r.off_first + nb * sizeof(T);
+            r.off_sizes = r.off_unpred + (size_t)E[i] * sizeof(T); r.off_pay = r.off_sizes + nb * 8;
+            off_pay[i] = (size_t)r.off_pay;
+            cap_len[i] = off_pay[i] + (size_t)((total_bits[i] + 7) / 8) + nb;
+            const size_t lds3 = (size_t)iv[i] * 8 + ((size_t)SZH_OMP_R3 * maxlen / 32 + 4) * 4 + 16;
+            if (!(maxlen <= 32 && lds3 <= 60 * 1024)) { state[i] = LATE; items[i].batched = 0; continue; }      // (pack_general: the single call, once the batch is through)
+            lds3_max = std::max(lds3_max, lds3);
+            hdr[i].assign(hdr_len, 0);
+            unsigned char *q = hdr[i].data();
+            memcpy(q, items[i].meta, meta_len); q += meta_len;
+            szhost_put_u32be(q, (uint32_t)g.nb); q += 4;
+            if (sizeof(T) == 8) szhost_put_f64be(q, (double)(T)items[i].eb); else szhost_put_f32be(q, (float)items[i].eb);
+            q += sizeof(T);
+            szhost_put_u32be(q, iv[i]); q += 4;
+            szhost_put_u32be(q, (uint32_t)tree_bytes); q += 4;
+            szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;
+            szhost_huff_tree_write(hf.get(), q);
+            packed[i].resize(iv[i]);
+            for (unsigned s2 = 0; s2 < iv[i]; ++s2) packed[i][s2] = ((tab_code[s2] & (tab_len[s2] >= 64 ? ~0ull : (1ull << tab_len[s2]) - 1)) << 8) | tab_len[s2];
+            tab.list[OMPB_L_PACK].push_back(i);
+        }
+        cb.host_ms += now_ms() - h0;
+    }
+    // ---- the blob: every stream at a multiple of 64, in item order.  A stream of the shared launches and one that is still to come take their bound (+ 64: the
+    // packers' last words), a finished one its length
+    size_t pos = 0;
+    for (int i = 0; i < count; ++i) {
+        items[i].offset = pos;
+        const size_t slot = state[i] == EARLY ? fb[i].size() : state[i] == FAILED ? 0 : cap_len[i] + 64;
+        pos = up64(pos + slot);
+    }
+    TRY(ensure(ctx, ctx->batch_blob, pos + 64));
+    unsigned char *d_blob = (unsigned char *)ctx->batch_blob.p;
+    const int n_pack = (int)tab.list[OMPB_L_PACK].size();
+    const u64 *h_tot = nullptr;
+    if (n_pack > 0) {
+        // ---- 6. one upload: the table again, with every header and packed code table and the spans of the verbatim values behind it
+        size_t un_bytes = 0, ex = 0;
+        std::vector<size_t> o_un((size_t)count, 0), o_hdr((size_t)count, 0);
+        int n_spans = 0;
+        for (int i : tab.list[OMPB_L_PACK]) {
+            o_un[i] = un_bytes; un_bytes += up16((size_t)E[i] * sizeof(T));
+            o_hdr[i] = ex; ex += (hdr[i].size() + 7) / 8 * 8 + (size_t)iv[i] * 8;
+            if (E[i] > 0) ++n_spans;
+        }
+        const size_t o_spans = ex;
+        ex += (size_t)n_spans * 24;
+        TRY(ensure(ctx, ctx->unpred, un_bytes + 16));
+        TRY(tab.reserve(ex));
+        fill_static();
+        std::vector<unsigned char> extra(ex, 0);
+        u64 *sp = (u64 *)(extra.data() + o_spans);
+        for (int i : tab.list[OMPB_L_PACK]) {
+            szh_ompb_rec &r = tab.rec[i];
+            const size_t hdr_pad = (hdr[i].size() + 7) / 8 * 8;
+            memcpy(extra.data() + o_hdr[i], hdr[i].data(), hdr[i].size());
+            memcpy(extra.data() + o_hdr[i] + hdr_pad, packed[i].data(), (size_t)iv[i] * 8);
+            r.hdr = tab.dev() + tab.o_extra + o_hdr[i]; r.packed = (const u64 *)(r.hdr + hdr_pad);
+            r.stream = d_blob + items[i].offset;
+            r.unpred = (char *)ctx->unpred.p + o_un[i];
+            if (E[i] > 0) { *sp++ = (u64)(uintptr_t)r.unpred; *sp++ = (u64)(items[i].offset + r.off_unpred); *sp++ = (u64)E[i] * sizeof(T); }
+        }
+        TRY(tab.clear_totals());
+        HIPCHK(hipMemsetAsync(d_blob, 0, pos + 64, st));
+        TRY(tab.upload(2, extra));
+        // ---- 7. / 8. every box its size and place inside its own stream; every stream's tables and payloads
+        hipLaunchKernelGGL(k_ompb_layout, dim3(1, (unsigned)n_pack), dim3(1024), 0, st, (int)nb, tab.d_rec(), tab.d_list(OMPB_L_PACK));
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_pack), dim3(256), lds3_max, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACK));
+        HIPCHK(hipGetLastError());
+        if (n_spans) {
+            hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)n_spans), dim3(256), 0, st, d_blob, (const u64 *)(tab.dev() + tab.o_extra + o_spans));
+            HIPCHK(hipGetLastError());
+        }
+        // ---- 9. the arrays' totals: the device's counts against the books' (check_and_deliver of the single call, per array)
+        HIPCHK(hipEventRecord(ctx->ev[4], st));
+        TRY(ensure_pinned(ctx, (size_t)count * 32));
+        HIPCHK(hipMemcpyAsync(ctx->pinned, tab.dev(), (size_t)count * 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        h_tot = (const u64 *)ctx->pinned;
+        float ms = 0;
+        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
+        hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]); S.ms_entropy = ms;
+        for (int i : tab.list[OMPB_L_PACK]) {
+            const u64 *t = h_tot + 4 * (size_t)i;
+            const u64 bytes = (total_bits[i] + 7) / 8;
+            if (t[1] != E[i] || (unsigned)t[2] != 0 || t[0] < bytes || t[0] > bytes + (u64)nb || off_pay[i] + (size_t)t[0] > cap_len[i]) {
+                state[i] = FAILED; items[i].rc = SZHIP_ERR_INTERNAL;
+                snprintf(ctx->err, sizeof(ctx->err), "OpenMP container: entropy stage mismatch in array %d of the batch", i);
+                continue;
+            }
+            items[i].size = off_pay[i] + (size_t)t[0];
+        }
+    } else HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < count; ++i) if (state[i] == LATE) single(i);
+    // ---- the blob to the caller; the streams of the single calls into their places
+    unsigned char *h_blob = nullptr;
+    if (!out_on_device) {
+        h_blob = (unsigned char *)malloc(pos ? pos : 1);
+        if (!h_blob) FAIL(SZHIP_ERR_INTERNAL, "out of host memory");
+        if (n_pack > 0) { const int rc = staged_copy(ctx, h_blob, d_blob, pos, false); if (rc != SZHIP_OK) { free(h_blob); return rc; } }
+    }
+    bool copied = false;
+    for (int i = 0; i < count; ++i) {
+        if ((state[i] != EARLY && state[i] != LATE) || items[i].rc != SZHIP_OK) continue;
+        if (state[i] == LATE && fb[i].size() > cap_len[i] + 64) { items[i].rc = SZHIP_ERR_INTERNAL; continue; }      // (the single call packs the same book: never)
+        items[i].size = fb[i].size();
+        if (h_blob) memcpy(h_blob + items[i].offset, fb[i].data(), fb[i].size());
+        else { HIPCHK(hipMemcpyAsync(d_blob + items[i].offset, fb[i].data(), fb[i].size(), hipMemcpyHostToDevice, st)); copied = true; }
+    }
+    if (copied) HIPCHK(hipStreamSynchronize(st));
+    *blob = h_blob ? h_blob : d_blob; *blob_size = pos;
+    int rc_all = SZHIP_OK;
+    for (int i = 0; i < count; ++i) {
+        if (items[i].rc != SZHIP_OK) { items[i].size = 0; if (rc_all == SZHIP_OK) rc_all = items[i].rc; continue; }
+        S.n_unpred += items[i].n_unpred; S.out_bytes += items[i].size;
+    }
+    S.ms_host = cb.host_ms; S.ms_total = now_ms() - cb.t_begin;
+    if (stats) *stats = S;
+    return rc_all;
+}
+
+// ---- the inverse.  What read_header of the single call finds in a stream, per stream
+template <class T>
+struct ompb_stream {
+    int thread_num = 0; T eb = 0; unsigned intervals = 0; size_t tree_bytes = 0; int node_count = 0;
+    size_t fixed = 0, off_ucount = 0, off_first = 0, off_unpred = 0, off_sizes = 0, off_pay = 0, pos = 0;      // (`pos`: where the stream's copy lies in the context's buffer)
+    u64 E = 0, max_box = 0;
+    dec_table D;
+    std::vector<u64> uoff, bbytes, boff;
+    std::vector<unsigned char> hbuf;                          // a device-resident stream: its first bytes on the host, as far as the rounds have fetched them
+    size_t have = 0;
+};
+
+template <class T>
+int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2, int out_on_device, szhip_stats *stats)
+{
+    call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
+    const size_t n = r0 * r1 * r2;
+    enum { BATCH, SINGLE, FAILED };
+    std::vector<int> state((size_t)count, BATCH);
+    std::vector<ompb_stream<T>> ps((size_t)count);
+    auto fail = [&](int i, const char *why) {
+        state[i] = FAILED; items[i].rc = SZHIP_ERR_STREAM;
+        snprintf(ctx->err, sizeof(ctx->err), "stream %d of the batch: %s", i, why);
+    };
+    // ---- the streams into the context's buffer, each where its address modulo 16 puts it, 64 zero bytes behind each (the bit readers may look past an end)
+    size_t total = 0;
+    for (int i = 0; i < count; ++i) {
+        total = up16(total) + ((uintptr_t)items[i].stream & 15u);
+        ps[i].pos = total; total += items[i].stream_len + 64;
+    }
+    TRY(ensure(ctx, ctx->stream_buf, total + 64));
+    unsigned char *d_streams = (unsigned char *)ctx->stream_buf.p;
+    TRY(ensure(ctx, ctx->batch_rec, 64));
+    HIPCHK(hipMemsetAsync(d_streams, 0, total + 64, st));
+    // pieces of the callers' device streams to the host, one round: spans up, one k_ompb_fetch into the context's staging array, one copy down
+    std::vector<u64> spans;
+    auto fetch_round = [&](const std::vector<size_t> &want) -> int {           // want[i]: bytes of stream i the host needs (0: none, the stream has failed)
+        if (!stream_on_device) return SZHIP_OK;
+        spans.clear();
+        size_t bytes = 0;
+        std::vector<size_t> at((size_t)count, 0);
+        for (int i = 0; i < count; ++i) {
+            if (state[i] == FAILED || want[i] <= ps[i].have) continue;
+            at[i] = bytes;
+            spans.push_back((u64)(uintptr_t)(items[i].stream + ps[i].have)); spans.push_back((u64)bytes); spans.push_back((u64)(want[i] - ps[i].have));
+            bytes += want[i] - ps[i].have;
+        }
+        if (spans.empty()) return SZHIP_OK;
+        const size_t o_data = up16(spans.size() * 8);
+        TRY(ensure(ctx, ctx->seg_hist, o_data + bytes + 64));
+        TRY(ensure_pinned(ctx, bytes + 64));
+        unsigned char *d = (unsigned char *)ctx->seg_hist.p;
+        HIPCHK(hipMemcpyAsync(d, spans.data(), spans.size() * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)(spans.size() / 3)), dim3(256), 0, st, d + o_data, (const u64 *)d);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctx->pinned, d + o_data, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < count; ++i) {
+            if (state[i] == FAILED || want[i] <= ps[i].have) continue;
+            ps[i].hbuf.resize(want[i]);
+            memcpy(ps[i].hbuf.data() + ps[i].have, (const unsigned char *)ctx->pinned + at[i], want[i] - ps[i].have);
+            ps[i].have = want[i];
+        }
+        return SZHIP_OK;
+    };
+    auto hs = [&](int i) { return stream_on_device ? (const unsigned char *)ps[i].hbuf.data() : items[i].stream; };
+    if (stream_on_device) {
+        std::vector<u64> all;
+        for (int i = 0; i < count; ++i) { all.push_back((u64)(uintptr_t)items[i].stream); all.push_back((u64)ps[i].pos); all.push_back((u64)items[i].stream_len); }
+        TRY(ensure(ctx, ctx->seg_zoff, all.size() * 8));
+        HIPCHK(hipMemcpyAsync(ctx->seg_zoff.p, all.data(), all.size() * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)count), dim3(256), 0, st, d_streams, (const u64 *)ctx->seg_zoff.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));                        // (`all` is a pageable source)
+    } else if (total <= ((size_t)64 << 20)) {
+        TRY(ensure_pinned3(ctx, total + 64));
+        memset(ctx->pinned3, 0, total);
+        for (int i = 0; i < count; ++i) memcpy((unsigned char *)ctx->pinned3 + ps[i].pos, items[i].stream, items[i].stream_len);
+        HIPCHK(hipMemcpyAsync(d_streams, ctx->pinned3, total, hipMemcpyHostToDevice, st));
+    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, d_streams + ps[i].pos, items[i].stream, items[i].stream_len, true));
+    HIPCHK(hipEventRecord(ctx->ev[0], st));
+    // ---- 1. / 2. headers, trees and per-box tables of all streams: three rounds of fetches at most, the walks of read_header per stream
+    const double h0 = now_ms();
+    std::vector<size_t> want((size_t)count, 0);
+    for (int i = 0; i < count; ++i) {
+        ps[i].fixed = items[i].body_off + 4 + sizeof(T) + 12;
+        if (ps[i].fixed > items[i].stream_len) fail(i, "truncated stream"); else want[i] = ps[i].fixed;
+    }
+    TRY(fetch_round(want));
+    szh_omp_geom g; bool have_g = false; int batch_threads = 0;
+    for (int i = 0; i < count; ++i) {
+        if (state[i] == FAILED) { want[i] = 0; continue; }
+        ompb_stream<T> &p = ps[i];
+        const unsigned char *q = hs(i) + items[i].body_off;
+        p.thread_num = (int)szhost_get_u32be(q); q += 4;
+        p.eb = sizeof(T) == 8 ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
+        p.intervals = szhost_get_u32be(q); q += 4;
+        p.tree_bytes = szhost_get_u32be(q); q += 4;
+        p.node_count = (int)szhost_get_u32be(q);
+        if (p.intervals < 4 || p.intervals > 65536 || !(p.eb > 0)) { fail(i, "bad OpenMP-container header"); want[i] = 0; continue; }
+        if (p.node_count <= 0 || p.tree_bytes > items[i].stream_len || szhost_huff_serial_size(p.node_count) > p.tree_bytes) { fail(i, "truncated stream"); want[i] = 0; continue; }
+        if (!have_g) {
+            szh_omp_geom gi;
+            if (p.thread_num >= 1 && omp_box_grid(ctx, p.thread_num, r0, r1, r2, &gi) == SZHIP_OK && gi.nb == p.thread_num) { g = gi; have_g = true; batch_threads = p.thread_num; }
+        }
+        if (!have_g || p.thread_num != batch_threads) { state[i] = SINGLE; want[i] = 0; continue; }      // (another grid, or none: the single call says what is wrong with it)
+        p.off_ucount = p.fixed + p.tree_bytes; p.off_first = p.off_ucount + (size_t)g.nb * 4; p.off_unpred = p.off_first + (size_t)g.nb * sizeof(T);
+        if (p.off_unpred > items[i].stream_len) { fail(i, "truncated stream"); want[i] = 0; continue; }
+        want[i] = p.off_unpred;
+    }
+    TRY(fetch_round(want));
+    for (int i = 0; i < count; ++i) {
+        if (state[i] != BATCH) { want[i] = 0; continue; }
+        ompb_stream<T> &p = ps[i];
+        if (!read_tree(hs(i) + p.fixed, p.node_count, p.intervals, p.D)) { fail(i, "bad Huffman tree"); want[i] = 0; continue; }
+        p.uoff.assign((size_t)g.nb + 1, 0);
+        bool ok = true;
+        for (int b = 0; b < g.nb; ++b) { uint32_t c; memcpy(&c, hs(i) + p.off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)g.bel) { ok = false; break; } p.uoff[b + 1] = p.uoff[b] + c; }
+        if (!ok) { fail(i, "bad verbatim-value count"); want[i] = 0; continue; }
+        p.E = p.uoff[g.nb];
+        p.off_sizes = p.off_unpred + (size_t)p.E * sizeof(T); p.off_pay = p.off_sizes + (size_t)g.nb * 8;
+        if (p.off_pay > items[i].stream_len) { fail(i, "truncated stream"); want[i] = 0; continue; }
+        want[i] = p.off_pay;
+    }
+    if (stream_on_device) {                                    // (the third round wants the box sizes only: not the verbatim values in front of them)
+        for (int i = 0; i < count; ++i) if (state[i] == BATCH) { ps[i].hbuf.resize(ps[i].off_sizes); ps[i].have = ps[i].off_sizes; }
+    }
+    TRY(fetch_round(want));
+    size_t stage_max = 0, tab_max = 0;
+    for (int i = 0; i < count; ++i) {
+        if (state[i] != BATCH) continue;
+        ompb_stream<T> &p = ps[i];
+        p.bbytes.resize((size_t)g.nb); p.boff.resize((size_t)g.nb);
+        memcpy(p.bbytes.data(), hs(i) + p.off_sizes, (size_t)g.nb * 8);
+        u64 acc = 0; bool ok = true;
+        for (int b = 0; b < g.nb; ++b) { p.boff[b] = acc; if (p.bbytes[b] > items[i].stream_len || p.bbytes[b] >= ((u64)1 << 28)) { ok = false; break; } acc += p.bbytes[b]; p.max_box = std::max(p.max_box, p.bbytes[b]); }
+        if (!ok) { fail(i, "bad payload size"); continue; }
+        if (p.off_pay + acc > items[i].stream_len) { fail(i, "truncated stream"); continue; }
+        // the look-up-table decoder's conditions (omp_dec::huffman_decode), for this stream alone
+        const unsigned stage_bytes = (unsigned)((p.max_box + 30 + 15) / 16 * 16 + 16);
+        const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
+        const int tab_lds = (size_t)p.D.n_nodes * 8 <= 13 * 1024;
+        const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds ? ((size_t)p.D.n_nodes * 8 + 15) / 16 * 16 : 0);
+        if (!(p.D.single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024)) { state[i] = SINGLE; continue; }
+        stage_max = std::max<size_t>(stage_max, stage_bytes);
+        if (tab_lds) tab_max = std::max(tab_max, ((size_t)p.D.n_nodes * 8 + 15) / 16 * 16);
+    }
+    // one launch has one LDS size: the largest payload's stage, the look-up table, the largest node table that goes to LDS -- or none of them there, if that is too much
+    const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_max + 16) / 4) * 4 + 15) / 16 * 16;
+    bool tabs_in_lds = true;
+    if (stage_lds + SZH_LUT_BYTES + tab_max > 64 * 1024) { tabs_in_lds = false; tab_max = 0; }
+    const size_t lds_lut = stage_lds + SZH_LUT_BYTES + tab_max;
+    if (lds_lut > 64 * 1024) for (int i = 0; i < count; ++i) if (state[i] == BATCH) state[i] = SINGLE;
+    cb.host_ms += now_ms() - h0;
+    // ---- the arrays of the shared launches: their places, forms, records
+    ompb_table tab(ctx, count);
+    const size_t out_stride = up16(n * sizeof(T));
+    if (!out_on_device) TRY(ensure(ctx, ctx->out, (size_t)count * out_stride));
+    size_t ex = 0, un_bytes = 0;
+    std::vector<size_t> o_ex((size_t)count, 0), o_un((size_t)count, 0);
+    int fw = 0;
+    const size_t nb = have_g ? (size_t)g.nb : 0;
+    if (have_g) { TRY(ompb_limits(ctx, count, nb, n)); fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32; if (fw > OC_FLAG_WORDS) fw = 0; }
+    const size_t first_bytes = up16((size_t)count * nb * sizeof(T));
+    for (int i = 0; i < count; ++i) {
+        if (state[i] != BATCH) continue;
+        ompb_stream<T> &p = ps[i];
+        tab.list[OMPB_L_ENT].push_back(i);
+        o_ex[i] = ex;
+        ex += up64(p.D.dtab.size() * 4) + SZH_LUT_BYTES + 64 + up16(nb * 8) * 2 + up16((nb + 1) * 8);
+        o_un[i] = first_bytes + un_bytes; un_bytes += up16((size_t)p.E * sizeof(T));
+        S.n_unpred += p.E; items[i].intervals = p.intervals; items[i].n_unpred = p.E; items[i].batched = 1;
+    }
+    const int n_ent = (int)tab.list[OMPB_L_ENT].size();
+    S.n_elements = (uint64_t)count * n; S.n_blocks = (uint64_t)count * nb;
+    const u64 *h_tot = nullptr;
+    if (n_ent > 0) {
+        const size_t o_spans = ex;
+        ex += (size_t)n_ent * 2 * 24;
+        TRY(tab.reserve(ex));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
+        TRY(ensure(ctx, ctx->unpred, first_bytes + un_bytes + 16));
+        bool any_flags = false;
+        if (fw > 0) TRY(ensure(ctx, ctx->chunk_bits, (size_t)count * nb * fw * 4));
+        std::vector<unsigned char> extra(ex, 0);
+        u64 *sp = (u64 *)(extra.data() + o_spans);
+        int n_spans = 0;
+        unsigned char *d_un = (unsigned char *)ctx->unpred.p;
+        for (int i : tab.list[OMPB_L_ENT]) {
+            ompb_stream<T> &p = ps[i];
+            szh_ompb_rec &r = tab.rec[i];
+            unsigned char *dx = tab.dev() + tab.o_extra + o_ex[i], *hx = extra.data() + o_ex[i];
+            size_t o = 0;
+            memcpy(hx, p.D.dtab.data(), p.D.dtab.size() * 4); r.table = (const unsigned *)dx; o = up64(p.D.dtab.size() * 4);
+            r.lut = (uint4 *)(dx + o); o += SZH_LUT_BYTES + 64;
+            memcpy(hx + o, p.bbytes.data(), nb * 8); r.box_bytes = (u64 *)(dx + o); o += up16(nb * 8);
+            memcpy(hx + o, p.boff.data(), nb * 8); r.box_off = (u64 *)(dx + o); o += up16(nb * 8);
+            memcpy(hx + o, p.uoff.data(), (nb + 1) * 8); r.uoff = (u64 *)(dx + o);
+            r.out = out_on_device ? items[i].out : (void *)((char *)ctx->out.p + (size_t)i * out_stride);
+            r.eb = (double)p.eb; r.recip = (double)(T)(1 / p.eb); r.intervals = p.intervals;
+            r.codes = (uint16_t *)ctx->codes_nat.p + (size_t)i * n;
+            r.first = d_un + (size_t)i * nb * sizeof(T); r.unpred = d_un + o_un[i];
+            r.totals = tab.totals(i);
+            r.payload = d_streams + p.pos + p.off_pay; r.bytes_before = (unsigned)std::min<size_t>(p.pos + p.off_pay, 0x7fffffffu);
+            r.n_nodes = p.D.n_nodes; r.tab_lds = tabs_in_lds && (size_t)p.D.n_nodes * 8 <= 13 * 1024 ? 1 : 0;
+            const int form = omp_form(g, r.out, sizeof(T), r1, r2);
+            items[i].quant_kernel = form;
+            tab.list[form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
+            if (form == 3 && p.E > 0) {
+                tab.list[OMPB_L_PACK].push_back(i);               // (here: the arrays k_omp_scatter runs for)
+                if (fw > 0) { r.vflags = (unsigned *)ctx->chunk_bits.p + (size_t)i * nb * fw; any_flags = true; }
+            }
+            // the first values and the verbatim values to aligned addresses (omp_dec::decode_boxes copies them out of the stream one by one)
+            *sp++ = (u64)(uintptr_t)(d_streams + p.pos + p.off_first); *sp++ = (u64)((size_t)i * nb * sizeof(T)); *sp++ = (u64)(nb * sizeof(T)); ++n_spans;
+            if (p.E > 0) { *sp++ = (u64)(uintptr_t)(d_streams + p.pos + p.off_unpred); *sp++ = (u64)o_un[i]; *sp++ = (u64)p.E * sizeof(T); ++n_spans; }
+        }
+        // ---- 3. one upload; 4. / 5. the look-up tables, the Huffman decode
+        TRY(tab.clear_totals());
+        if (any_flags) HIPCHK(hipMemsetAsync(ctx->chunk_bits.p, 0, (size_t)count * nb * fw * 4, st));
+        TRY(tab.upload(0, extra));
+        hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)n_spans), dim3(256), 0, st, d_un, (const u64 *)(tab.dev() + tab.o_extra + o_spans));
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ompb_build_lut, dim3(SZH_LUT_SIZE / 256, (unsigned)n_ent), dim3(256), 0, st, tab.d_rec(), tab.d_list(OMPB_L_ENT));
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ompb_hdec_lut, dim3((unsigned)nb, (unsigned)n_ent), dim3(256), lds_lut, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT), (unsigned)stage_max);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        // ---- 6. the verbatim values of the column-form arrays to their places, one sweep launch per form
+        HIPCHK(hipEventRecord(ctx->ev[2], st));
+        const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size(), ns = (int)tab.list[OMPB_L_PACK].size();
+        const int rows = g.c0 * g.c1;
+        const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
+        if (ns) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)ns), dim3(256), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACK), fw);
+        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3), fw);
+        if (n4) hipLaunchKernelGGL((k_ompb_box<T, true, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F4));
+        if (n5) hipLaunchKernelGGL((k_ompb_box<T, true, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[3], st));
+        S.quant_kernel_launches += (n3 ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
+        // ---- 7. the arrays' error counts
+        TRY(ensure_pinned(ctx, (size_t)count * 32));
+        HIPCHK(hipMemcpyAsync(ctx->pinned, tab.dev(), (size_t)count * 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        h_tot = (const u64 *)ctx->pinned;
+        float ms = 0;
+        hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); S.ms_entropy = ms;
+        hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
+        for (int i : tab.list[OMPB_L_ENT]) if ((unsigned)h_tot[4 * (size_t)i + 2] != 0) fail(i, "boxes whose payload or verbatim-value count does not fit their codes");
+        if (!out_on_device) {                                 // the decoded arrays to the callers' host arrays: one copy down, then those of the streams that decoded
+            std::vector<unsigned char> tmp((size_t)count * out_stride);
+            TRY(staged_copy(ctx, tmp.data(), ctx->out.p, tmp.size(), false));
+            for (int i : tab.list[OMPB_L_ENT]) if (state[i] == BATCH) memcpy(items[i].out, tmp.data() + (size_t)i * out_stride, n * sizeof(T));
+        }
+    } else HIPCHK(hipStreamSynchronize(st));
+    // ---- the streams the shared launches do not cover: the single call
+    for (int i = 0; i < count; ++i) {
+        if (state[i] != SINGLE) continue;
+        szhip_stats s1; memset(&s1, 0, sizeof(s1));
+        const int rc = decompress_omp_impl<T>(ctx, items[i].stream, stream_on_device, items[i].stream_len, items[i].body_off, r0, r1, r2, items[i].out, out_on_device, 0, 0, &s1);
+        items[i].rc = rc; items[i].batched = 0;
+        if (rc != SZHIP_OK) { hipStreamSynchronize(st); continue; }
+        items[i].intervals = s1.intervals; items[i].n_unpred = s1.n_unpred; items[i].quant_kernel = s1.quant_kernel;
+        S.n_unpred += s1.n_unpred;
+    }
+    int rc_all = SZHIP_OK;
+    for (int i = 0; i < count; ++i) if (items[i].rc != SZHIP_OK && rc_all == SZHIP_OK) rc_all = items[i].rc;
+    S.out_bytes = (uint64_t)count * n * sizeof(T);
+    S.ms_host = cb.host_ms; S.ms_total = now_ms() - cb.t_begin;
+    if (stats) *stats = S;
+    return rc_all;
+}
