@@ -279,6 +279,19 @@ int SZ_hip_compress_device_into(int dataType, const void *d_data, unsigned char 
                                 double absErrBound, double relBoundRatio, double pwrBoundRatio, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1);
 int SZ_hip_decompress_device(int dataType, const unsigned char *bytes, int bytes_on_device, size_t byteLength, void *d_out,
                              size_t r5, size_t r4, size_t r3, size_t r2, size_t r1);
+/* An array against its decoded copy: the reference's `-a` report (example/sz.c:549-620) and the bound checks, computed on the device in one read of the two arrays
+ * (szhip_compare of szhip.h, which describes every field of struct szhip_quality; NaN points are excluded and counted).  SZ_hip_compare: two HOST arrays of
+ * r5 x ... x r1 values (unused dimensions 0); SZ_hip_compare_device: two DEVICE arrays, aligned to their element, complete when the call is made; neither is written.
+ * absBound / pwRelBound: the bounds the n_over_* counts are taken against, negative for "not asked"; flags: SZHIP_Q_CORR for the correlation (acEff), which costs a
+ * second read.  SZ_SCES, or SZ_NSCS with a printed reason (a null pointer, no points, a misaligned pointer), *out untouched.
+ * SZ_hip_print_quality prints the lines of that report in the reference's formats; cmp_bytes: the stream's length for the compressionRatio line (0: no such line);
+ * the acEff line appears when the correlation was asked for. */
+struct szhip_quality;
+int SZ_hip_compare(int dataType, const void *ori, const void *dec, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound, double pwRelBound,
+                   int flags, struct szhip_quality *out);
+int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound,
+                          double pwRelBound, int flags, struct szhip_quality *out);
+void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int is_double);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

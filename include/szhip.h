@@ -374,6 +374,48 @@ int szhip_fill(szhip_ctx *ctx, int dtype, const void *value, size_t n, void *d_o
 int szhip_clamp(szhip_ctx *ctx, int dtype, void *d_data, size_t n, double vmin, double vmax);
 int szhip_copy(szhip_ctx *ctx, void *dst, const void *src, size_t bytes, int to_device);
 
+/*
+ * AN ARRAY AGAINST ITS DECODED COPY, where both lie: the reference's `sz -a` report (example/sz.c:549-620 float, :735-805 double) and the bound checks a caller of an
+ * error-bounded compressor makes next, as ONE read of the two arrays (kernels in sz_amd/csrc/szh_quality.h).  `ori` and `dec` are device or host
+ * pointers, each on its own (a host array is staged into a buffer of the context, a host view row by row), aligned to their element and to nothing more; neither is
+ * written.  szhip_compare takes two contiguous arrays of n values; szhip_compare_view two boxes of r0 x r1 x r2 values (r0 >= 1), each with its own element pitches in
+ * the meaning of the VIEWS above.  Points are numbered row-major within the box, 0 .. n - 1.
+ * Per point e = |dec - ori| is formed in the data's type (`float err = fabs(data[i] - ori_data[i])`); everything after that runs in double on exactly converted values.
+ * A point whose ori, dec or e is a NaN is EXCLUDED (+inf against +inf too: the difference is a NaN): it is counted in n_excluded, in n_excluded_diff as well when the
+ * two bit patterns differ, and takes part in nothing else.  Over the points that take part:
+ *   vmin, vmax           of ori;  range = vmax - vmin, for SZHIP_F32 the float difference
+ *   max_abs_err          and max_abs_idx, the SMALLEST number of a point that attains it
+ *   max_pw_rel_err       max e / |ori| over ori != 0 (a double division; inf / inf is a NaN and counts for nothing, as `if (maxpw_relerr < relerr)` has it)
+ *   n_zero_changed       points with ori == 0 and dec != 0 (a point-wise relative bound leaves zeros alone)
+ *   n_over_abs           points with e > abs_bound;  n_over_pwr: points with ori != 0 and e / |ori| > pw_rel_bound;  n_over_both: points in both sets;
+ *                        first_over_idx: the smallest number of a point in either.  A negative bound is "not asked": its counts are 0.  ABS_OR_PW_REL is violated at
+ *                        n_over_both points, ABS_AND_PW_REL at n_over_abs + n_over_pwr - n_over_both.
+ *   sum_ori, sum_dec, sum_dec_sq, sum_err_sq   double sums of ori, dec, dec * dec, e * e
+ *   cov, var_ori, var_dec   only with SZHIP_Q_CORR (else 0): the centred SUMS sum (ori - m1)(dec - m2), sum (ori - m1)^2, sum (dec - m2)^2 of sz.c:595-597 around
+ *                        m1 = sum_ori / N, m2 = sum_dec / N -- a SECOND read of both arrays (the one-pass form cancels on a field whose mean dwarfs its spread)
+ *   mse = sum_err_sq / N, psnr = 20 log10(range) - 10 log10(mse), nrmse = sqrt(mse) / range, norm_err = sqrt(sum_err_sq),
+ *   ac_eff = (cov / N) / sqrt(var_ori / N) / sqrt(var_dec / N), a NaN without SZHIP_Q_CORR          N = n - n_excluded, the points that take part
+ * max_abs_idx / first_over_idx are UINT64_MAX when there is no such point; when every point is excluded vmin and vmax are NaNs and max_abs_err is 0.
+ * DETERMINISTIC: which values are added in which order depends on the point count alone -- not on addresses, pitches or timing (no floating-point atomics): two calls
+ * on the same input return the same bytes, and a view returns what the call returns on contiguous copies of the two boxes, sums included.
+ * SZHIP_ERR_ARG before anything is launched, *q untouched: a null pointer, n == 0 or an empty box, n >= 2^40, pitch1 < r2, pitch0 < r1 * pitch1, a misaligned pointer.
+ */
+typedef struct szhip_quality {
+    uint64_t n, n_excluded, n_excluded_diff, n_zero_changed;
+    uint64_t n_over_abs, n_over_pwr, n_over_both;
+    uint64_t max_abs_idx, first_over_idx;   /* UINT64_MAX when there is none */
+    double   vmin, vmax, max_abs_err, max_pw_rel_err;
+    double   sum_ori, sum_dec, sum_dec_sq, sum_err_sq;
+    double   cov, var_ori, var_dec;         /* centred SUMS; 0 without SZHIP_Q_CORR */
+    double   range, mse, psnr, nrmse, norm_err, ac_eff;
+} szhip_quality;
+#define SZHIP_Q_CORR 1u
+int szhip_compare(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device, const void *dec, int dec_on_device, size_t n,
+                  double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *q);
+int szhip_compare_view(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device, size_t o_pitch0, size_t o_pitch1,
+                       const void *dec, int dec_on_device, size_t d_pitch0, size_t d_pitch1, size_t r0, size_t r1, size_t r2,
+                       double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *q);
+
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)
  *        4 code histogram (u32) 5 per-column zero counts (u32) 6 per-column unpredictable offsets (u64)

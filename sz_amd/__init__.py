@@ -15,4 +15,5 @@ from .api import (  # noqa: F401
     SZ_hip_compress_device, SZ_hip_compress_device_into, SZ_hip_decompress_device,
     SZ_hip_decompress_region, SZ_hip_compress_region, SZ_hip_decompress_into_region, sz_slab_compress, sz_slab_decompress, sz_slab_decompress_region,
     conf_params, HipContext, HipPool, make_meta,
+    szhip_quality, Quality, SZHIP_Q_CORR, NO_INDEX, SZ_hip_compare, SZ_hip_compare_device, SZ_hip_print_quality,
 )

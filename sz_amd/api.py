@@ -1,5 +1,6 @@
 """ctypes mirror of include/sz.h and include/szhip.h (sz_amd/csrc/libszhip.so)."""
 import ctypes
+import dataclasses
 import os
 import subprocess
 
@@ -64,6 +65,23 @@ class szhip_batch_item(ctypes.Structure):  # include/szhip.h: one array of szhip
 class szhip_book_record(ctypes.Structure):  # include/szhip.h
     _fields_ = [("n_nodes", ctypes.c_uint32), ("tree_bytes", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("status", ctypes.c_uint32),
                 ("total_bits", ctypes.c_uint64), ("total_unpred", ctypes.c_uint64)]
+
+
+class szhip_quality(ctypes.Structure):  # include/szhip.h: what szhip_compare / szhip_compare_view fill
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "n_excluded", "n_excluded_diff", "n_zero_changed", "n_over_abs", "n_over_pwr", "n_over_both",
+                                               "max_abs_idx", "first_over_idx")] + \
+               [(k, ctypes.c_double) for k in ("vmin", "vmax", "max_abs_err", "max_pw_rel_err", "sum_ori", "sum_dec", "sum_dec_sq", "sum_err_sq",
+                                               "cov", "var_ori", "var_dec", "range", "mse", "psnr", "nrmse", "norm_err", "ac_eff")]
+
+
+SZHIP_Q_CORR = 1
+NO_INDEX = 2 ** 64 - 1              # max_abs_idx / first_over_idx when there is no such point
+# the fields of szhip_quality as Python numbers, and the struct's bytes (`raw`: two calls on the same input give the same bytes)
+Quality = dataclasses.make_dataclass("Quality", [(k, int if t is ctypes.c_uint64 else float) for k, t in szhip_quality._fields_] + [("raw", bytes)], frozen=True)
+
+
+def _quality(q):
+    return Quality(**{k: getattr(q, k) for k, _ in szhip_quality._fields_}, raw=bytes(q))
 
 
 class szhost_meta(ctypes.Structure):  # sz_amd/csrc/szhost.h
@@ -216,6 +234,17 @@ def _bind(L):
         L.szhip_fill.restype = ctypes.c_int
         L.szhip_clamp.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_double, ctypes.c_double]
         L.szhip_clamp.restype = ctypes.c_int
+    if hasattr(L, "szhip_compare"):
+        L.szhip_compare.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_uint, ctypes.POINTER(szhip_quality)]
+        L.szhip_compare.restype = ctypes.c_int
+        L.szhip_compare_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, sz, sz, ctypes.c_void_p, ctypes.c_int, sz, sz, sz, sz, sz,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_uint, ctypes.POINTER(szhip_quality)]
+        L.szhip_compare_view.restype = ctypes.c_int
+        for f in (L.SZ_hip_compare, L.SZ_hip_compare_device):
+            f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [sz] * 5 + [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(szhip_quality)]
+            f.restype = ctypes.c_int
+        L.SZ_hip_print_quality.argtypes = [ctypes.POINTER(szhip_quality), sz, ctypes.c_int]; L.SZ_hip_print_quality.restype = None
     L.szhost_write_meta.argtypes = [ctypes.POINTER(szhost_meta), ctypes.c_ubyte, ctypes.c_char_p]
     L.szhost_write_meta.restype = sz
     L.free.argtypes = [ctypes.c_void_p]
@@ -381,6 +410,31 @@ def SZ_hip_decompress_device(stream_or_ptr, on_device, length, out_ptr, shape, d
     rc = lib().SZ_hip_decompress_device(dt, src, 1 if on_device else 0, length, out_ptr, *_dims5(shape))
     if rc != SZ_SCES:
         raise SZError(f"SZ_hip_decompress_device failed ({rc})")
+
+
+def SZ_hip_compare(ori, dec, absBound=-1.0, pwRelBound=-1.0, corr=False):
+    """include/sz.h: the numpy array `ori` against its decoded copy `dec` (same shape and dtype), compared on the device: a Quality."""
+    ori, dec = np.ascontiguousarray(ori), np.ascontiguousarray(dec)
+    if ori.shape != dec.shape or ori.dtype != dec.dtype:
+        raise SZError("SZ_hip_compare: two arrays of one shape and dtype")
+    q = szhip_quality()
+    if lib().SZ_hip_compare(_dtype_code(ori), ori.ctypes.data, dec.ctypes.data, *_dims5(ori.shape), absBound, pwRelBound, SZHIP_Q_CORR if corr else 0, ctypes.byref(q)) != SZ_SCES:
+        raise SZError("SZ_hip_compare failed")
+    return _quality(q)
+
+
+def SZ_hip_compare_device(ori_ptr, dec_ptr, shape, dtype, absBound=-1.0, pwRelBound=-1.0, corr=False):
+    """include/sz.h: the same for two arrays of `shape` / `dtype` at DEVICE addresses; neither is copied to the host."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    q = szhip_quality()
+    if lib().SZ_hip_compare_device(dt, ori_ptr, dec_ptr, *_dims5(shape), absBound, pwRelBound, SZHIP_Q_CORR if corr else 0, ctypes.byref(q)) != SZ_SCES:
+        raise SZError("SZ_hip_compare_device failed")
+    return _quality(q)
+
+
+def SZ_hip_print_quality(q, cmp_bytes=0, is_double=False):
+    """include/sz.h: the lines of the reference's `-a` report for a Quality, on the process's stdout."""
+    lib().SZ_hip_print_quality(ctypes.byref(szhip_quality.from_buffer_copy(q.raw)), cmp_bytes, int(is_double))
 
 
 def SZ_hip_compress_openmp_batch(ptrs, on_device, shape, dtype, bounds):
@@ -733,6 +787,29 @@ class HipContext:
                                       int(pitches[0]), int(pitches[1]))
         if rc:
             self._err(rc, "szhip_scatter_view")
+
+    def compare(self, ori_ptr, dec_ptr, on_device, n, dtype, abs_bound=-1.0, pw_rel_bound=-1.0, corr=False):
+        """szhip_compare: the n values at ori_ptr against the n at dec_ptr (on_device: one flag for both, or a pair), in one read of the two arrays on the device;
+        corr: the correlation too, a second read.  Returns a Quality (include/szhip.h describes the fields); neither array is written."""
+        od, dd = on_device if isinstance(on_device, (tuple, list)) else (on_device, on_device)
+        q = szhip_quality()
+        rc = lib().szhip_compare(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ori_ptr, int(od), dec_ptr, int(dd), n, float(abs_bound), float(pw_rel_bound),
+                                 SZHIP_Q_CORR if corr else 0, ctypes.byref(q))
+        if rc:
+            self._err(rc, "szhip_compare")
+        return _quality(q)
+
+    def compare_view(self, ori_ptr, ori_pitches, dec_ptr, dec_pitches, on_device, shape3, dtype, abs_bound=-1.0, pw_rel_bound=-1.0, corr=False):
+        """szhip_compare_view: two boxes of shape3 values, each inside a larger array with its own (pitch0, pitch1) in elements.  The Quality of compare on contiguous
+        copies of the two boxes, sums included."""
+        od, dd = on_device if isinstance(on_device, (tuple, list)) else (on_device, on_device)
+        q = szhip_quality()
+        rc = lib().szhip_compare_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, ori_ptr, int(od), int(ori_pitches[0]), int(ori_pitches[1]),
+                                      dec_ptr, int(dd), int(dec_pitches[0]), int(dec_pitches[1]), shape3[0], shape3[1], shape3[2], float(abs_bound),
+                                      float(pw_rel_bound), SZHIP_Q_CORR if corr else 0, ctypes.byref(q))
+        if rc:
+            self._err(rc, "szhip_compare_view")
+        return _quality(q)
 
     def store_be(self, src_ptr, n, dtype, dst_ptr, dst_on_device=True, zero_replacement=None):
         """szhip_store_be: the n values of the device array at src_ptr as big-endian bytes at dst_ptr (a device byte address of any alignment, or host memory);

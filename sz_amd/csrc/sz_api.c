@@ -1600,6 +1600,45 @@ int SZ_hip_decompress_openmp_batch(int dataType, int count, unsigned char *const
     return rc == SZHIP_OK ? SZ_SCES : SZ_NSCS;
 }
 
+/* ---- an array against its decoded copy (sz.h): szhip_compare on the calling thread's context */
+static int compare_fp(int dataType, const void *ori, const void *dec, int dev, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound, double pwRelBound,
+                      int flags, struct szhip_quality *out)
+{
+    const char *who = dev ? "SZ_hip_compare_device" : "SZ_hip_compare";
+    if (!ori || !dec || !out) { printf("Error: %s: null argument.\n", who); return SZ_NSCS; }
+    if (dataType != SZ_FLOAT && dataType != SZ_DOUBLE) { printf("Error: %s: float and double arrays only.\n", who); return SZ_NSCS; }
+    const size_t n = computeDataLength(r5, r4, r3, r2, r1);
+    if (n == 0) { printf("Error: %s: no points (r1 = 0).\n", who); return SZ_NSCS; }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const int rc = szhip_compare(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, ori, dev, dec, dev, n, absBound, pwRelBound, (unsigned)flags, out);
+    if (rc != SZHIP_OK) { printf("Error: szhip_compare failed (%d): %s\n", rc, rc == SZHIP_ERR_ARG ? "a pointer that is not aligned to its element, or too many points" : szhip_last_error(ctx)); return SZ_NSCS; }
+    return SZ_SCES;
+}
+int SZ_hip_compare(int dataType, const void *ori, const void *dec, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound, double pwRelBound,
+                   int flags, struct szhip_quality *out)
+{
+    return compare_fp(dataType, ori, dec, 0, r5, r4, r3, r2, r1, absBound, pwRelBound, flags, out);
+}
+int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound,
+                          double pwRelBound, int flags, struct szhip_quality *out)
+{
+    return compare_fp(dataType, d_ori, d_dec, 1, r5, r4, r3, r2, r1, absBound, pwRelBound, flags, out);
+}
+/* example/sz.c:613-620 */
+void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int is_double)
+{
+    if (!q) return;
+    printf("Min=%.20G, Max=%.20G, range=%.20G\n", q->vmin, q->vmax, q->range);
+    printf("Max absolute error = %.10f\n", q->max_abs_err);
+    printf("Max relative error = %f\n", q->max_abs_err / q->range);
+    printf("Max pw relative error = %f\n", q->max_pw_rel_err);
+    printf("PSNR = %f, NRMSE= %.20G\n", q->psnr, q->nrmse);
+    printf("normError = %f, normErr_norm = %f\n", q->norm_err, q->norm_err / sqrt(q->sum_dec_sq));
+    if (q->ac_eff == q->ac_eff) printf("acEff=%f\n", q->ac_eff);
+    if (cmp_bytes) printf("compressionRatio=%f\n", 1.0 * (double)(q->n * (is_double ? 8 : 4)) / (double)cmp_bytes);
+}
+
 /* the rest of sz/include/sz_omp.h and sz.h's thread helpers, so that callers written for an OpenMP build link unchanged:
  * sz_set_num_threads (sz_omp.c:49-53) sets the box count as omp_set_num_threads does for an OpenMP build; the 1-D / 2-D entry points
  * are stubs in the reference itself (sz_omp.c:56-61, :360-364, :570-576, :866-870) and stay stubs here */

@@ -21,6 +21,7 @@
 #include "../../include/szhip.h"
 #include "szhost.h"
 #include "szhip_kernels.h"
+#include "szh_quality.h"
 
 namespace {
 
@@ -147,7 +148,8 @@ struct szhip_ctx {
     DevBuf lor_bits, reg_flags, reg_rank, coef_compact, in, out, codes_nat, codes_blk, coef, blk_lor, faceI, faceJ, rb_down, rb_right, rb_vals, pt_flags, feed_word, progress, order, small, hist, col_zeros, col_zeros64,
         seg_bits, seg_zeros, seg_bitoff, seg_zoff, seg_hist, seg_tab, col_off, partial, samples, unpred, stream_buf, chunk_bits, chunk_off, code_tab, len_tab, dec_tab,
         starts, ends, counts, offs, dirty, zcnt, zpos, pwr_log, pwr_signs, pwr_small, coef_dec, msst_ptab, msst_cells, msst_rec, msst_pe, book_tree, book_rec, book_stage,
-        batch_rec, batch_blob;               // szhip_*_omp_batch: the per-array table; the blob of streams (the single calls inside a batch use stream_buf)
+        batch_rec, batch_blob,               // szhip_*_omp_batch: the per-array table; the blob of streams (the single calls inside a batch use stream_buf)
+        in2, quality;                        // szhip_compare: the second host array of the pair; the workgroups' partial results
     void *pinned = nullptr; size_t pinned_cap = 0;
     void *pinned2 = nullptr; size_t pinned2_cap = 0;   // target of the second stream's copies (indicator bits, regression-block count)
     // bulk copies between the caller's pageable arrays and the device: SZH_STAGE_T host threads, two pinned buffers + events each
@@ -184,6 +186,7 @@ namespace {
 #include "szhip_pwr.inc"     // point-wise relative bounds
 #include "szhip_omp.inc"     // the reference's OpenMP container
 #include "szhip_ompbatch.inc" // ... over many same-shape arrays in one call
+#include "szhip_quality.inc" // an array against its decoded copy: the error report
 
 } // namespace
 
@@ -290,7 +293,7 @@ void szhip_destroy(szhip_ctx *ctx)
                       &ctx->order, &ctx->small, &ctx->hist, &ctx->col_zeros, &ctx->col_zeros64, &ctx->seg_bits, &ctx->seg_zeros, &ctx->seg_bitoff, &ctx->seg_zoff, &ctx->seg_hist, &ctx->seg_tab, &ctx->col_off, &ctx->partial,
                       &ctx->samples, &ctx->unpred, &ctx->stream_buf, &ctx->chunk_bits, &ctx->chunk_off, &ctx->code_tab,
                       &ctx->len_tab, &ctx->dec_tab, &ctx->starts, &ctx->ends, &ctx->counts, &ctx->offs, &ctx->dirty, &ctx->zcnt, &ctx->zpos,
-                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe, &ctx->book_tree, &ctx->book_rec, &ctx->book_stage, &ctx->batch_rec, &ctx->batch_blob};
+                      &ctx->pwr_log, &ctx->pwr_signs, &ctx->pwr_small, &ctx->coef_dec, &ctx->msst_ptab, &ctx->msst_cells, &ctx->msst_rec, &ctx->msst_pe, &ctx->book_tree, &ctx->book_rec, &ctx->book_stage, &ctx->batch_rec, &ctx->batch_blob, &ctx->in2, &ctx->quality};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     if (ctx->pinned2) hipHostFree(ctx->pinned2);
@@ -615,6 +618,36 @@ int szhip_decompress_omp_view(szhip_ctx *ctx, int dtype, const unsigned char *st
     TRY(check_alignment_set_device(ctx, dtype, out));
     return synced_on_failure(ctx,
                BY_DTYPE(dtype, decompress_omp_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, out, out_on_device, pitch0, pitch1, stats));
+}
+
+// ---- an array against its decoded copy (szhip.h): the error report
+static int compare_args(szhip_ctx *ctx, int dtype, const void *ori, const void *dec, size_t r0, size_t r1, size_t r2, szhip_quality *q)
+{
+    if (!ctx || !ori || !dec || !q || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || (double)r0 * (double)r1 * (double)r2 >= 1099511627776.0) return SZHIP_ERR_ARG;
+    return SZHIP_OK;
+}
+
+int szhip_compare_view(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device, size_t o_pitch0, size_t o_pitch1, const void *dec, int dec_on_device,
+                       size_t d_pitch0, size_t d_pitch1, size_t r0, size_t r1, size_t r2, double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *q)
+{
+    TRY(compare_args(ctx, dtype, ori, dec, r0, r1, r2, q));
+    TRY(check_view(ctx, r0, r1, r2, o_pitch0, o_pitch1));
+    TRY(check_view(ctx, r0, r1, r2, d_pitch0, d_pitch1));
+    TRY(check_alignment_set_device(ctx, dtype, ori));
+    TRY(check_alignment_set_device(ctx, dtype, dec));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_impl, ctx, ori, ori_on_device, o_pitch0, o_pitch1, dec, dec_on_device, d_pitch0, d_pitch1, r0, r1, r2,
+                                           abs_bound, pw_rel_bound, flags, q));
+}
+
+int szhip_compare(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device, const void *dec, int dec_on_device, size_t n, double abs_bound, double pw_rel_bound,
+                  unsigned flags, szhip_quality *q)
+{
+    TRY(compare_args(ctx, dtype, ori, dec, 1, 1, 1, q));
+    if (n == 0 || n >= ((size_t)1 << 40)) return SZHIP_ERR_ARG;
+    TRY(check_alignment_set_device(ctx, dtype, ori));
+    TRY(check_alignment_set_device(ctx, dtype, dec));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_impl, ctx, ori, ori_on_device, n, n, dec, dec_on_device, n, n, 1, 1, n, abs_bound, pw_rel_bound, flags, q));
 }
 
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,
