@@ -231,8 +231,8 @@ void decompressDataSeries_double_3D_openmp(double **data, size_t r1, size_t r2, 
  * (sz_set_num_threads / SZ_HIP_OMP_THREADS, else picked from the shape), the body behind 4 + MetaDataByteLength bytes.  The inverse takes comp_data[i] at the stream's
  * FIRST byte, as returned (it skips the parameter bytes itself), comp_sizes[i] bytes long, and writes array i to out[i] (host, or device with out_on_device).
  * Both return SZ_SCES, or SZ_NSCS with a printed reason; when any array fails every returned stream is freed and its pointer nulled.
- * Out of scope: error-bound modes other than an absolute bound per array, SZ_HIP_MODE=omp through SZ_compress_args, the lossless stage (the streams are what the
- * `*_openmp` entry points write: never wrapped). */
+ * These two take an absolute bound per array and write unmarked streams, as the `*_openmp` entry points do (never wrapped by the lossless stage); the range-based
+ * modes and the streams of SZ_compress_args under SZ_HIP_MODE=omp are SZ_hip_compress_args_batch's, below. */
 int SZ_hip_compress_openmp_batch(int dataType, int count, const void *const *data, int data_on_device, const double *realPrecision,
                                  size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes);
 int SZ_hip_decompress_openmp_batch(int dataType, int count, unsigned char *const *comp_data, const size_t *comp_sizes, void *const *out, int out_on_device,
@@ -292,6 +292,33 @@ int SZ_hip_compare(int dataType, const void *ori, const void *dec, size_t r5, si
 int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, double absBound,
                           double pwRelBound, int flags, struct szhip_quality *out);
 void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int is_double);
+/* SZ_compress_args over MANY 3-D arrays of one shape r1 x r2 x r3 (r1 slowest, as SZ_hip_compress_openmp_batch) and type in one call, with its inverse and the error
+ * report over the round trip.
+ * SZ_hip_compress_args_batch: errBoundMode is ABS, REL, ABS_AND_REL, ABS_OR_REL, PSNR or NORM (psnr and normErr from the configuration); every array's value range
+ * comes from ONE launch (szhip_minmax_batch), its bound from the rule SZ_compress_args applies, its own range and the call's absErrBound / relBoundRatio.  streams[i]
+ * (malloc'd, caller frees; comp_sizes[i] bytes) is byte for byte what SZ_compress_args of this library returns under SZ_HIP_MODE=omp for array i ALONE -- the same
+ * configuration and arguments, as the first call after the same SZ_Init (a PSNR call rewrites confparams_cpr->errorBoundMode, as the reference does) -- including the
+ * parameter bytes, which carry the item's own bound and range, and the mark in byte 19.  The call does not read SZ_HIP_MODE: it always writes this form.
+ * Arrays with range > bound > 0 go through one szhip_compress_omp_batch with per-item bounds and parameter bytes (batched[i] = 1; batched may be NULL); an array
+ * with range <= bound (a constant array, or two values closer than an ABS bound) gets the reference's constant stream -- of a device array only its first value
+ * crosses the bus; a bound that is not positive takes SZ_compress_args' ordinary path from inside the call (both batched[i] = 0).  A host array crosses the bus once.
+ * SZ_NSCS with a printed reason and nothing launched: a mode >= PW_REL, a configuration whose szMode is not SZ_BEST_SPEED (the lossless stage is host code) or that
+ * asks for random access, a shape with an extent below 2, of at most 20 values or for which no box grid is found (SZ_HIP_OMP_THREADS / sz_set_num_threads as for
+ * SZ_HIP_MODE=omp).  When an item fails its stream is NULL, the others are delivered, and the call returns SZ_NSCS.
+ * SZ_hip_decompress_batch takes what that call returns (host streams): the streams SZ_decompress recognises as marked containers, with the box count of the first of
+ * them, go through one szhip_decompress_omp_batch; everything else -- constant streams, a container of another box count, an SZ 2.1 stream -- through SZ_decompress'
+ * own path, stream by stream.  out[i] (host, or device with out_on_device; aligned to its element) receives bit for bit what SZ_decompress returns for stream i.  A
+ * failing item does not disturb the others; the call returns SZ_NSCS if any item failed.
+ * SZ_hip_compare_batch: szhip_compare_batch (szhip.h) on `count` pairs of r1 x r2 x r3 values, pair i against absBound[i] and pwRelBound[i] (pwRelBound NULL: not
+ * asked): out[i] is byte for byte SZ_hip_compare's record for pair i.
+ * SZ_hip_last_stats after each call: the stats of its shared launches (quant_kernel_launches: the sweep launches, one per form; the pass-1 launches of the report).
+ * Not covered: batches of mixed shape, the lossless stage, point-wise relative modes, views, the slab container. */
+int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                               size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched);
+int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
+                            size_t r1, size_t r2, size_t r3);
+int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
+                         const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

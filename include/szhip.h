@@ -93,6 +93,9 @@ const char *szhip_last_error(szhip_ctx *ctx);
 /* copy a host array into the context's device input buffer once, so that szhip_minmax and
  * szhip_compress can both run on it (data_on_device = 1) without a second PCIe transfer */
 int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void **device_ptr);
+/* ... and `count` host arrays of `bytes` bytes each, one behind the other at multiples of 16 (one copy when they total at most 64 MiB): device_ptrs[i] then serves
+ * as array i with data_on_device = 1 for szhip_minmax_batch and szhip_compress_omp_batch, so that a host array crosses the bus once for both */
+int szhip_stage_input_batch(szhip_ctx *ctx, const void *const *host_data, int count, size_t bytes, const void **device_ptrs);
 
 /*
  * Device pointers and ordering (all calls below): a call runs on the context's own NON-BLOCKING streams and returns when its results are complete.
@@ -115,6 +118,19 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
  */
 /* min / max of n values (device or host pointer) */
 int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double *vmin, double *vmax);
+/*
+ * ... of `count` arrays of n values each in ONE launch and ONE read-back of `count` pairs (kernel: sz_amd/csrc/szh_rangebatch.h): what a
+ * range-based error bound needs before a batch compress call.  The array is the grid's second dimension; its base pointer comes through a device table that is
+ * uploaded once.  Each array is contiguous and aligned to its element, and is cut at the 16-byte boundaries of its OWN address: the pieces between move 16 bytes per
+ * lane, the head and the tail value by value -- so the arrays of a batch may lie at different offsets from a boundary.
+ * vmin[i] / vmax[i] are bit for bit what szhip_minmax returns for array i alone: a NaN takes no part, zeros of both signs are ordered -0.0 < +0.0, an array
+ * without a number gives what szhip_minmax gives (min and max do not depend on the order of reduction; the reduction is over ordered integers, no float atomics).
+ * Host arrays (data_on_device = 0) are staged one behind the other into the context's input buffer, as szhip_compress_omp_batch stages them.
+ * SZHIP_ERR_ARG before anything is launched: count < 1, n == 0, a null pointer, a pointer that is not aligned to its element.  SZHIP_ERR_UNSUP beyond
+ * count <= 65535 and count x n < 2^32, the limits of the batch.  stats (may be NULL): quant_kernel_launches is the number of scan launches, 1 whatever `count` is.
+ */
+int szhip_minmax_batch(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t n, double *vmin, double *vmax,
+                       szhip_stats *stats);
 
 /*
  * Compress a 3-D array (r0 slowest ... r2 fastest, the callee convention of sz_float.c:6527) with
@@ -415,6 +431,18 @@ int szhip_compare(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device,
 int szhip_compare_view(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device, size_t o_pitch0, size_t o_pitch1,
                        const void *dec, int dec_on_device, size_t d_pitch0, size_t d_pitch1, size_t r0, size_t r1, size_t r2,
                        double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *q);
+/*
+ * ... for `count` PAIRS of contiguous arrays of n values each (no views), each pair against its own bounds (abs_bound[i]; pw_rel_bound[i], or pw_rel_bound == NULL:
+ * not asked), in a number of launches, copies and synchronisations that does not grow with `count`: one pass-1 launch with the pair as the grid's second dimension,
+ * one final launch with one workgroup per pair, one read-back of `count` records -- and the same again around the per-pair means with SZHIP_Q_CORR.
+ * out[i] is BYTE FOR BYTE (memcmp of the struct) what szhip_compare returns for pair i alone, sums included: a pair's workgroups, slots and merge tree are those of the
+ * single call (the grid's first dimension is a function of n alone).  The 16-byte-or-value-by-value decision stays per array and per piece, so the two arrays of a
+ * pair, and the pairs of a batch, may be aligned differently.  on_device: all 2 x count pointers are device (1) or host (0) pointers; host arrays are staged one behind
+ * the other.  Arguments and limits as szhip_minmax_batch (SZHIP_ERR_ARG / SZHIP_ERR_UNSUP, nothing launched, `out` untouched).  stats (may be NULL):
+ * quant_kernel_launches counts the pass-1 launches: 1.
+ */
+int szhip_compare_batch(szhip_ctx *ctx, int dtype, const void *const *ori, const void *const *dec, int count, int on_device, size_t n,
+                        const double *abs_bound, const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats);
 
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)

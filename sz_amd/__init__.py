@@ -16,4 +16,5 @@ from .api import (  # noqa: F401
     SZ_hip_decompress_region, SZ_hip_compress_region, SZ_hip_decompress_into_region, sz_slab_compress, sz_slab_decompress, sz_slab_decompress_region,
     conf_params, HipContext, HipPool, make_meta,
     szhip_quality, Quality, SZHIP_Q_CORR, NO_INDEX, SZ_hip_compare, SZ_hip_compare_device, SZ_hip_print_quality,
+    SZ_hip_compress_args_batch, SZ_hip_decompress_batch, SZ_hip_compare_batch,
 )

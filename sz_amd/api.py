@@ -245,6 +245,22 @@ def _bind(L):
             f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [sz] * 5 + [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(szhip_quality)]
             f.restype = ctypes.c_int
         L.SZ_hip_print_quality.argtypes = [ctypes.POINTER(szhip_quality), sz, ctypes.c_int]; L.SZ_hip_print_quality.restype = None
+    if hasattr(L, "szhip_minmax_batch"):
+        vpp, dp = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double)
+        L.szhip_minmax_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, vpp, ctypes.c_int, ctypes.c_int, sz, dp, dp, ctypes.POINTER(szhip_stats)]
+        L.szhip_minmax_batch.restype = ctypes.c_int
+        L.szhip_compare_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, vpp, vpp, ctypes.c_int, ctypes.c_int, sz, dp, dp, ctypes.c_uint,
+                                          ctypes.POINTER(szhip_quality), ctypes.POINTER(szhip_stats)]
+        L.szhip_compare_batch.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_compress_args_batch"):
+        vpp, dp = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double)
+        L.SZ_hip_compress_args_batch.argtypes = [ctypes.c_int, ctypes.c_int, vpp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, sz, sz, sz,
+                                                 vpp, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]
+        L.SZ_hip_compress_args_batch.restype = ctypes.c_int
+        L.SZ_hip_decompress_batch.argtypes = [ctypes.c_int, ctypes.c_int, vpp, ctypes.POINTER(sz), vpp, ctypes.c_int, sz, sz, sz]
+        L.SZ_hip_decompress_batch.restype = ctypes.c_int
+        L.SZ_hip_compare_batch.argtypes = [ctypes.c_int, ctypes.c_int, vpp, vpp, ctypes.c_int, sz, sz, sz, dp, dp, ctypes.c_int, ctypes.POINTER(szhip_quality)]
+        L.SZ_hip_compare_batch.restype = ctypes.c_int
     L.szhost_write_meta.argtypes = [ctypes.POINTER(szhost_meta), ctypes.c_ubyte, ctypes.c_char_p]
     L.szhost_write_meta.restype = sz
     L.free.argtypes = [ctypes.c_void_p]
@@ -465,6 +481,54 @@ def SZ_hip_decompress_openmp_batch(streams, out_ptrs, out_on_device, shape, dtyp
     rc = lib().SZ_hip_decompress_openmp_batch(dt, count, c_streams, c_sizes, c_out, 1 if out_on_device else 0, shape[0], shape[1], shape[2])
     if rc != SZ_SCES:
         raise SZError(f"SZ_hip_decompress_openmp_batch failed ({rc})")
+
+
+def SZ_hip_compress_args_batch(ptrs, on_device, shape, dtype, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, raise_on_error=True):
+    """include/sz.h: SZ_compress_args over `len(ptrs)` arrays of one 3-D `shape` / `dtype` at the addresses ptrs (host, or device with on_device) in one call.
+    Returns (rc, streams, batched): stream i (bytes, or None when the item failed) is byte for byte what SZ_compress_args returns for array i alone under
+    SZ_HIP_MODE=omp; batched[i] is 1 for the items that went through the shared launches."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(ptrs)
+    c_ptrs = (ctypes.c_void_p * max(count, 1))(*ptrs)
+    streams, sizes, batched = (ctypes.c_void_p * max(count, 1))(), (ctypes.c_size_t * max(count, 1))(), (ctypes.c_int * max(count, 1))()
+    rc = lib().SZ_hip_compress_args_batch(dt, count, c_ptrs, 1 if on_device else 0, errBoundMode, absErrBound, relBoundRatio, shape[0], shape[1], shape[2],
+                                          streams, sizes, batched)
+    out = [ctypes.string_at(streams[i], sizes[i]) if streams[i] else None for i in range(count)]
+    for i in range(count):
+        if streams[i]:
+            lib().free(streams[i])
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_compress_args_batch failed ({rc})")
+    return rc, out, [batched[i] for i in range(count)]
+
+
+def SZ_hip_decompress_batch(streams, out_ptrs, out_on_device, shape, dtype, raise_on_error=True):
+    """include/sz.h: streams[i] (bytes, as SZ_hip_compress_args_batch or SZ_compress_args returned it) into the array at out_ptrs[i] (host, or device with
+    out_on_device), bit for bit what SZ_decompress returns for it.  Returns rc: SZ_NSCS when any item failed (the others are decoded)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(streams)
+    keep = [ctypes.create_string_buffer(bytes(s), len(s)) for s in streams]
+    c_streams = (ctypes.c_void_p * max(count, 1))(*[ctypes.addressof(k) for k in keep])
+    c_sizes = (ctypes.c_size_t * max(count, 1))(*[len(s) for s in streams])
+    c_out = (ctypes.c_void_p * max(count, 1))(*out_ptrs)
+    rc = lib().SZ_hip_decompress_batch(dt, count, c_streams, c_sizes, c_out, 1 if out_on_device else 0, shape[0], shape[1], shape[2])
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_decompress_batch failed ({rc})")
+    return rc
+
+
+def SZ_hip_compare_batch(ori_ptrs, dec_ptrs, on_device, shape, dtype, absBounds, pwRelBounds=None, corr=False):
+    """include/sz.h: `len(ori_ptrs)` pairs of arrays of `shape` / `dtype` (host, or device with on_device), pair i against absBounds[i] (and pwRelBounds[i]): a list
+    of Quality, record i byte for byte SZ_hip_compare's for pair i."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(ori_ptrs)
+    c_ori, c_dec = (ctypes.c_void_p * max(count, 1))(*ori_ptrs), (ctypes.c_void_p * max(count, 1))(*dec_ptrs)
+    c_abs = (ctypes.c_double * max(count, 1))(*[float(b) for b in absBounds])
+    c_pwr = (ctypes.c_double * max(count, 1))(*[float(b) for b in pwRelBounds]) if pwRelBounds is not None else None
+    out = (szhip_quality * max(count, 1))()
+    if lib().SZ_hip_compare_batch(dt, count, c_ori, c_dec, 1 if on_device else 0, shape[0], shape[1], shape[2], c_abs, c_pwr, SZHIP_Q_CORR if corr else 0, out) != SZ_SCES:
+        raise SZError("SZ_hip_compare_batch failed")
+    return [_quality(out[i]) for i in range(count)]
 
 
 def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
@@ -798,6 +862,31 @@ class HipContext:
         if rc:
             self._err(rc, "szhip_compare")
         return _quality(q)
+
+    def minmax_batch(self, ptrs, on_device, n, dtype, raise_on_error=True):
+        """szhip_minmax_batch: the value ranges of len(ptrs) arrays of n values each (host, or device with on_device) in one launch and one read-back.
+        Returns (rc, [(vmin, vmax), ...], stats); pair i is bit for bit what minmax returns for array i alone."""
+        count = len(ptrs)
+        c_ptrs = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        lo, hi, st = (ctypes.c_double * max(count, 1))(), (ctypes.c_double * max(count, 1))(), szhip_stats()
+        rc = lib().szhip_minmax_batch(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ptrs, count, int(on_device), n, lo, hi, ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_minmax_batch")
+        return rc, [(lo[i], hi[i]) for i in range(count)], st
+
+    def compare_batch(self, ori_ptrs, dec_ptrs, on_device, n, dtype, abs_bounds, pw_rel_bounds=None, corr=False, raise_on_error=True):
+        """szhip_compare_batch: len(ori_ptrs) pairs of contiguous arrays of n values each, pair i against abs_bounds[i] (and pw_rel_bounds[i]; None: not asked), in a
+        number of launches that does not grow with the count.  Returns (rc, [Quality, ...], stats); record i is byte for byte what compare returns for pair i alone."""
+        count = len(ori_ptrs)
+        c_ori, c_dec = (ctypes.c_void_p * max(count, 1))(*ori_ptrs), (ctypes.c_void_p * max(count, 1))(*dec_ptrs)
+        c_abs = (ctypes.c_double * max(count, 1))(*[float(b) for b in abs_bounds])
+        c_pwr = (ctypes.c_double * max(count, 1))(*[float(b) for b in pw_rel_bounds]) if pw_rel_bounds is not None else None
+        out, st = (szhip_quality * max(count, 1))(), szhip_stats()
+        rc = lib().szhip_compare_batch(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ori, c_dec, count, int(on_device), n, c_abs, c_pwr,
+                                       SZHIP_Q_CORR if corr else 0, out, ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_compare_batch")
+        return rc, [_quality(out[i]) for i in range(count)], st
 
     def compare_view(self, ori_ptr, ori_pitches, dec_ptr, dec_pitches, on_device, shape3, dtype, abs_bound=-1.0, pw_rel_bound=-1.0, corr=False):
         """szhip_compare_view: two boxes of shape3 values, each inside a larger array with its own (pitch0, pitch1) in elements.  The Quality of compare on contiguous

@@ -366,6 +366,40 @@ static void set_range(int dataType, double vmin, double vmax, double *valueRange
     } else { *valueRangeSize = vmax - vmin; confparams_cpr->dmin = vmin; confparams_cpr->dmax = vmin + *valueRangeSize; }
 }
 
+/* The mode -> bound rule of a compress call (compress_fp, SZ_hip_compress_args_batch): the absolute bound the quantiser works with, from the call's mode and bounds,
+ * the array's value range (set_range: the subtraction in the array's type) and its length.  PSNR and NORM rewrite confparams_cpr->errorBoundMode to ABS, as the
+ * reference does; every mode records the bound in confparams_cpr->absErrBound.  Returns the call's status (SZ_BERR for a mode that is none). */
+static int bound_from_mode(int dataType, int errBoundMode, double absErr_Bound, double relBoundRatio, double valueRangeSize, size_t dataLength, double *bound)
+{
+    int status = SZ_SCES;
+    double realPrecision = 0;
+    if (confparams_cpr->errorBoundMode == PSNR) { /* conf.c:54-60 */
+        confparams_cpr->errorBoundMode = ABS;
+        double v1 = confparams_cpr->psnr + 10 * log10(1 - 2.0 / 3.0 * (double)confparams_cpr->predThreshold);
+        realPrecision = confparams_cpr->absErrBound = valueRangeSize * pow(10, v1 / (-20));
+    } else if (confparams_cpr->errorBoundMode == NORM) { /* conf.c:62-65 */
+        confparams_cpr->errorBoundMode = ABS;
+        realPrecision = confparams_cpr->absErrBound = sqrt(3.0 / dataLength) * confparams_cpr->normErr;
+    } else { /* getRealPrecision_float/_double, dataCompression.c:288-332 */
+        if (errBoundMode == ABS) realPrecision = absErr_Bound;
+        else if (errBoundMode == REL) realPrecision = relBoundRatio * valueRangeSize;
+        else if (errBoundMode == ABS_AND_REL || errBoundMode == ABS_OR_REL) {
+            double b = relBoundRatio * valueRangeSize;
+            if (dataType == SZ_FLOAT) { /* min_f / max_f narrow both operands to float */
+                float fa = (float)absErr_Bound, fb = (float)b;
+                realPrecision = errBoundMode == ABS_AND_REL ? (fa < fb ? fa : fb) : (fa > fb ? fa : fb);
+            } else realPrecision = errBoundMode == ABS_AND_REL ? (absErr_Bound < b ? absErr_Bound : b) : (absErr_Bound > b ? absErr_Bound : b);
+        } else if (errBoundMode == ABS_AND_PW_REL || errBoundMode == ABS_OR_PW_REL) realPrecision = absErr_Bound;
+        else if (errBoundMode == REL_AND_PW_REL || errBoundMode == REL_OR_PW_REL) realPrecision = relBoundRatio * valueRangeSize;
+        else if (errBoundMode == PW_REL) realPrecision = 0;
+        else { printf("Error: error-bound-mode is incorrect!\n"); status = SZ_BERR; }
+        confparams_cpr->absErrBound = realPrecision;
+    }
+
+    *bound = realPrecision;
+    return status;
+}
+
 /* Where a compress call's array lies and where its stream goes.  The host entry points: {0, NULL, 0} -- a host array, the stream returned as malloc'd host memory.
  * SZ_hip_compress_device: dev = 1, the array is device memory and is never copied to the host: the range comes from szhip_minmax as always, the first value of a
  * constant array and the values of a tiny one through szhip_copy, the raw copy through szhip_store_be.  SZ_hip_compress_device_into: d_stream / cap too -- the
@@ -577,30 +611,8 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
         set_range(dataType, vmin, vmax, &valueRangeSize);
     }
 
-    int status = SZ_SCES;
     double realPrecision = 0;
-    if (confparams_cpr->errorBoundMode == PSNR) { /* conf.c:54-60 */
-        confparams_cpr->errorBoundMode = ABS;
-        double v1 = confparams_cpr->psnr + 10 * log10(1 - 2.0 / 3.0 * (double)confparams_cpr->predThreshold);
-        realPrecision = confparams_cpr->absErrBound = valueRangeSize * pow(10, v1 / (-20));
-    } else if (confparams_cpr->errorBoundMode == NORM) { /* conf.c:62-65 */
-        confparams_cpr->errorBoundMode = ABS;
-        realPrecision = confparams_cpr->absErrBound = sqrt(3.0 / dataLength) * confparams_cpr->normErr;
-    } else { /* getRealPrecision_float/_double, dataCompression.c:288-332 */
-        if (errBoundMode == ABS) realPrecision = absErr_Bound;
-        else if (errBoundMode == REL) realPrecision = relBoundRatio * valueRangeSize;
-        else if (errBoundMode == ABS_AND_REL || errBoundMode == ABS_OR_REL) {
-            double b = relBoundRatio * valueRangeSize;
-            if (dataType == SZ_FLOAT) { /* min_f / max_f narrow both operands to float */
-                float fa = (float)absErr_Bound, fb = (float)b;
-                realPrecision = errBoundMode == ABS_AND_REL ? (fa < fb ? fa : fb) : (fa > fb ? fa : fb);
-            } else realPrecision = errBoundMode == ABS_AND_REL ? (absErr_Bound < b ? absErr_Bound : b) : (absErr_Bound > b ? absErr_Bound : b);
-        } else if (errBoundMode == ABS_AND_PW_REL || errBoundMode == ABS_OR_PW_REL) realPrecision = absErr_Bound;
-        else if (errBoundMode == REL_AND_PW_REL || errBoundMode == REL_OR_PW_REL) realPrecision = relBoundRatio * valueRangeSize;
-        else if (errBoundMode == PW_REL) realPrecision = 0;
-        else { printf("Error: error-bound-mode is incorrect!\n"); status = SZ_BERR; }
-        confparams_cpr->absErrBound = realPrecision;
-    }
+    int status = bound_from_mode(dataType, errBoundMode, absErr_Bound, relBoundRatio, valueRangeSize, dataLength, &realPrecision);
 
     szhost_meta m; fill_meta(&m, confparams_cpr, dataType);
     unsigned char meta[4 + MetaDataByteLength_double];
@@ -777,11 +789,9 @@ static int compress_fp(int dataType, int withRegression, unsigned char **newByte
     return finish_stream(io, tmp, tmpSize, newByteData, outSize, status);
 }
 
-/* SZ_compress_args for an array on the host or on the device, the stream returned or written to the caller's device buffer (cpr_io); *status: compress_fp's */
-static unsigned char *compress_args_io(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound, double relBoundRatio, double pwrBoundRatio,
-                                       size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const cpr_io *io, int *status)
+/* the configuration and the execution state a compress call starts from */
+static void ensure_cpr_state(void)
 {
-    *status = SZ_NSCS;
     if (confparams_cpr == NULL) SZ_Init(NULL);
     else if (exe_params == NULL) exe_params = (sz_exedata *)calloc(1, sizeof(sz_exedata));
     if (exe_params->intvCapacity == 0) {
@@ -790,6 +800,14 @@ static unsigned char *compress_args_io(int dataType, void *data, size_t *outSize
         exe_params->optQuantMode = 1;
     }
     if (exe_params->SZ_SIZE_TYPE == 0) exe_params->SZ_SIZE_TYPE = sizeof(size_t);
+}
+
+/* SZ_compress_args for an array on the host or on the device, the stream returned or written to the caller's device buffer (cpr_io); *status: compress_fp's */
+static unsigned char *compress_args_io(int dataType, void *data, size_t *outSize, int errBoundMode, double absErrBound, double relBoundRatio, double pwrBoundRatio,
+                                       size_t r5, size_t r4, size_t r3, size_t r2, size_t r1, const cpr_io *io, int *status)
+{
+    *status = SZ_NSCS;
+    ensure_cpr_state();
     size_t _r[5];
     filterDimension(r5, r4, r3, r2, r1, _r);
     confparams_cpr->dataType = dataType;
@@ -1625,6 +1643,163 @@ int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, si
 {
     return compare_fp(dataType, d_ori, d_dec, 1, r5, r4, r3, r2, r1, absBound, pwRelBound, flags, out);
 }
+/* ---- SZ_compress_args over many same-shape 3-D arrays in one call, the inverse, and the error report over the round trip (sz.h) */
+int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                               size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched)
+{
+    static const char *const who = "SZ_hip_compress_args_batch";
+    if (count < 1 || !data || !streams || !comp_sizes || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    for (int i = 0; i < count; ++i) { streams[i] = NULL; comp_sizes[i] = 0; if (batched) batched[i] = 0; }
+    for (int i = 0; i < count; ++i) if (!data[i]) { printf("Error: %s: array %d is a null pointer.\n", who, i); return SZ_NSCS; }
+    ensure_cpr_state();
+    if (errBoundMode < ABS || errBoundMode > NORM) {
+        printf("Error: %s takes the modes ABS, REL, ABS_AND_REL, ABS_OR_REL, PSNR and NORM; mode %d (%s) is not covered.\n", who, errBoundMode,
+               errBoundMode >= PW_REL ? "point-wise relative" : "none of SZ's");
+        return SZ_NSCS;
+    }
+    if (confparams_cpr->szMode != SZ_BEST_SPEED) { printf("Error: %s writes bare SZ streams: szMode must be SZ_BEST_SPEED (the lossless stage is host code).\n", who); return SZ_NSCS; }
+    if (confparams_cpr->randomAccess) { printf("Error: %s: the random-access form is not covered.\n", who); return SZ_NSCS; }
+    const size_t n = r1 * r2 * r3, esz = dataType == SZ_FLOAT ? 4 : 8;
+    const int threads = r1 >= 2 && r2 >= 2 && r3 >= 2 && n > MIN_NUM_OF_ELEMENTS ? omp_pick_threads(r1, r2, r3) : 0;
+    g_omp_last_threads = threads;
+    if (threads <= 0) { printf("Error: %s: no power-of-two box grid divides %zu x %zu x %zu into boxes the MI355X build takes; set SZ_HIP_OMP_THREADS.\n", who, r1, r2, r3); return SZ_NSCS; }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const int dt = dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64;
+    const size_t ML = 4 + MetaDataByteLength_double;
+    const void **d_in = (const void **)malloc((size_t)count * sizeof(void *));
+    double *vmin = (double *)malloc((size_t)count * 2 * sizeof(double)), *vmax = vmin ? vmin + count : NULL;
+    szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
+    unsigned char *metas = (unsigned char *)malloc((size_t)count * ML);
+    int *idx = (int *)malloc((size_t)count * 2 * sizeof(int)), *later = idx ? idx + count : NULL;
+    unsigned char *blob = NULL;
+    int rc_all = SZ_NSCS, nb = 0, nl = 0;
+    szhip_stats bstats; memset(&bstats, 0, sizeof(bstats));
+    szhip_params hp; memset(&hp, 0, sizeof(hp));
+    if (!d_in || !vmin || !items || !metas || !idx) { printf("Error: %s: out of memory.\n", who); goto done; }
+    /* 1. host arrays cross the bus once; 2. every array's range in one launch */
+    if (data_on_device) memcpy(d_in, data, (size_t)count * sizeof(void *));
+    else if (szhip_stage_input_batch(ctx, data, count, n * esz, d_in) != SZHIP_OK) { printf("Error: %s: staging failed: %s\n", who, szhip_last_error(ctx)); goto done; }
+    {
+        const int mrc = szhip_minmax_batch(ctx, dt, (const void *const *)d_in, count, 1, n, vmin, vmax, NULL);
+        if (mrc != SZHIP_OK) { printf("Error: szhip_minmax_batch failed (%d): %s\n", mrc, mrc == SZHIP_ERR_ARG ? "a pointer that is not aligned to its element" : szhip_last_error(ctx)); goto done; }
+    }
+    rc_all = SZ_SCES;
+    /* 3. / 4. per item what compress_fp does with its range: the bound, then the constant stream, the container, or the ordinary path */
+    const cpr_io dev_io = {1, NULL, 0};
+    const cpr_io *io = data_on_device ? &dev_io : &g_host_io;
+    for (int i = 0; i < count; ++i) {
+        double range = 0, bound = 0;
+        confparams_cpr->dataType = dataType; confparams_cpr->errorBoundMode = errBoundMode;
+        set_range(dataType, vmin[i], vmax[i], &range);
+        const int status = bound_from_mode(dataType, errBoundMode, absErrBound, relBoundRatio, range, n, &bound);
+        if (range <= bound) {
+            szhost_meta m; fill_meta(&m, confparams_cpr, dataType);
+            if (constant_out(dataType, &m, data[i], n, io, &streams[i], &comp_sizes[i], status) != SZ_SCES || !streams[i]) { printf("Error: %s: array %d (constant) failed.\n", who, i); rc_all = SZ_NSCS; }
+            continue;
+        }
+        if (!(bound > 0) || !(range > bound) || !((dataType == SZ_FLOAT ? (double)(float)bound : bound) > 0)) { later[nl++] = i; continue; }
+        unsigned char *meta = metas + (size_t)nb * ML;
+        omp_meta_params(meta, &hp);
+        meta[19] = SZH_OMP_MARK;
+        items[nb].data = d_in[i]; items[nb].eb = dataType == SZ_FLOAT ? (double)(float)bound : bound; items[nb].meta = meta;
+        idx[nb++] = i;
+    }
+    if (nb > 0) {
+        size_t blob_size = 0;
+        const int rc = szhip_compress_omp_batch(ctx, dt, items, nb, 1, r1, r2, r3, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats);
+        if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp_batch failed (%d): %s\n", rc, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
+        for (int k = 0; k < nb && blob; ++k) {
+            const int i = idx[k];
+            if (items[k].rc != SZHIP_OK || items[k].size == 0) { rc_all = SZ_NSCS; continue; }
+            streams[i] = (unsigned char *)malloc(items[k].size);
+            if (!streams[i]) { rc_all = SZ_NSCS; continue; }
+            memcpy(streams[i], blob + items[k].offset, items[k].size);
+            comp_sizes[i] = items[k].size;
+            if (batched) batched[i] = 1;
+        }
+    }
+    /* the ordinary path (a bound that is not positive, a range that is no number): the single call's own code, once the staged arrays are no longer needed */
+    for (int k = 0; k < nl; ++k) {
+        const int i = later[k];
+        const int status = compress_fp(dataType, confparams_cpr->withRegression, &streams[i], (void *)data[i], 0, 0, r1, r2, r3, &comp_sizes[i], errBoundMode, absErrBound,
+                                       relBoundRatio, 0, io);
+        if (!streams[i]) { printf("Error: %s: array %d failed on the ordinary path (%d).\n", who, i, status); comp_sizes[i] = 0; rc_all = SZ_NSCS; }
+    }
+    g_last_stats = bstats;
+done:
+    free(blob); free(idx); free(metas); free(items); free(vmin); free((void *)d_in);
+    return rc_all;
+}
+
+int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
+                            size_t r1, size_t r2, size_t r3)
+{
+    static const char *const who = "SZ_hip_decompress_batch";
+    if (count < 1 || !bytes || !byteLengths || !out || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const size_t n = computeDataLength(0, 0, r1, r2, r3), esz = dataType == SZ_FLOAT ? 4 : 8, body = 4 + (size_t)MetaDataByteLength;
+    szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
+    int *idx = (int *)malloc((size_t)count * 2 * sizeof(int)), *single = idx ? idx + count : NULL;
+    if (!items || !idx) { free(items); free(idx); return SZ_NSCS; }
+    int rc_all = SZ_SCES, nb = 0, ns = 0;
+    uint32_t boxes = 0;
+    szhip_stats bstats; memset(&bstats, 0, sizeof(bstats));
+    /* the streams SZ_decompress takes for marked OpenMP containers (decompress_fp), with the box count of the first of them: one batched decode */
+    for (int i = 0; i < count; ++i) {
+        const unsigned char *s = bytes[i];
+        const int marked = s && out[i] && r1 >= 2 && r2 >= 2 && r3 >= 2 && n > MIN_NUM_OF_ELEMENTS && byteLengths[i] > body + 4 && s[0] == versionNumber[0] &&
+                           s[1] == versionNumber[1] && s[2] == versionNumber[2] && (s[3] & 0x80) && !(s[3] & 0x31) && s[19] == SZH_OMP_MARK;
+        const uint32_t t = marked ? szhost_get_u32be(s + body) : 0;
+        if (marked && boxes == 0) boxes = t;
+        if (marked && t == boxes && t != 0) {
+            items[nb].stream = s; items[nb].stream_len = byteLengths[i]; items[nb].body_off = body; items[nb].out = out[i];
+            idx[nb++] = i;
+        } else single[ns++] = i;
+    }
+    if (nb > 0) {
+        fresh_dec_state();
+        const int rc = szhip_decompress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, &bstats);
+        if (rc != SZHIP_OK) {
+            rc_all = SZ_NSCS;
+            for (int k = 0; k < nb; ++k) if (items[k].rc != SZHIP_OK) printf("Error: %s: stream %d failed (%d).\n", who, idx[k], items[k].rc);
+            printf("Error: szhip_decompress_omp_batch failed (%d): %s\n", rc, szhip_last_error(ctx));
+        }
+    }
+    /* everything else: the single call, stream by stream */
+    for (int k = 0; k < ns; ++k) {
+        const int i = single[k];
+        void *o = NULL;
+        if (bytes[i] && out[i]) {
+            size_t _r[5];
+            filterDimension(0, 0, r1, r2, r3, _r);
+            fresh_dec_state();
+            o = decompress_fp(dataType, bytes[i], byteLengths[i], _r[4], _r[3], _r[2], _r[1], _r[0], 0, out_on_device ? out[i] : NULL);
+        }
+        if (!o) { printf("Error: %s: stream %d failed.\n", who, i); rc_all = SZ_NSCS; continue; }
+        if (!out_on_device) { memcpy(out[i], o, n * esz); free(o); }
+    }
+    if (nb > 0) g_last_stats = bstats;
+    free(items); free(idx);
+    return rc_all;
+}
+
+int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
+                         const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out)
+{
+    static const char *const who = "SZ_hip_compare_batch";
+    if (count < 1 || !ori || !dec || !absBound || !out) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    if (dataType != SZ_FLOAT && dataType != SZ_DOUBLE) { printf("Error: %s: float and double arrays only.\n", who); return SZ_NSCS; }
+    const size_t n = computeDataLength(0, 0, r1, r2, r3);
+    if (n == 0) { printf("Error: %s: no points (r3 = 0).\n", who); return SZ_NSCS; }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const int rc = szhip_compare_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, ori, dec, count, on_device, n, absBound, pwRelBound, (unsigned)flags, out, &g_last_stats);
+    if (rc != SZHIP_OK) { printf("Error: szhip_compare_batch failed (%d): %s\n", rc, rc == SZHIP_ERR_ARG ? "a null or misaligned pointer" : szhip_last_error(ctx)); return SZ_NSCS; }
+    return SZ_SCES;
+}
+
 /* example/sz.c:613-620 */
 void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int is_double)
 {

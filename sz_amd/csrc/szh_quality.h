@@ -126,8 +126,8 @@ __device__ __forceinline__ void szh_q_sweep(const T *__restrict__ ori, const szh
 // A point whose ori, dec or error is a NaN is EXCLUDED: counted, and counted again when the two bit patterns differ, and takes part in nothing else.  (inf against
 // the same inf: the difference is a NaN.)  abs_bound / pw_rel_bound < 0: not asked, the counts stay 0.
 template <class T>
-__global__ __launch_bounds__(256) void k_quality_pass1(const T *__restrict__ ori, szh_qview VO, const T *__restrict__ dec, szh_qview VD, int64_t n,
-                                                       double abs_bound, double pw_rel_bound, unsigned long long *slots)
+__device__ __forceinline__ void szh_q_pass1_body(const T *__restrict__ ori, const szh_qview &VO, const T *__restrict__ dec, const szh_qview &VD, int64_t n,
+                                                 double abs_bound, double pw_rel_bound, unsigned long long *slot)
 {
     unsigned long long omin = ~0ull, omax = 0, ekey = 0, eidx = ~0ull, first = ~0ull, n_ex = 0, n_exd = 0, n_zc = 0, n_oa = 0, n_op = 0, n_ob = 0;
     double pw = 0, s_o = 0, s_d = 0, s_dd = 0, s_ee = 0;
@@ -154,7 +154,13 @@ __global__ __launch_bounds__(256) void k_quality_pass1(const T *__restrict__ ori
     a[SZH_Q_OMIN] = omin; a[SZH_Q_OMAX] = omax; a[SZH_Q_EKEY] = ekey; a[SZH_Q_EIDX] = eidx; a[SZH_Q_PW] = szh_q_dbits(pw); a[SZH_Q_FIRST] = first;
     a[SZH_Q_NEX] = n_ex; a[SZH_Q_NEXD] = n_exd; a[SZH_Q_NZC] = n_zc; a[SZH_Q_NOA] = n_oa; a[SZH_Q_NOP] = n_op; a[SZH_Q_NOB] = n_ob;
     a[SZH_Q_S0] = szh_q_dbits(s_o); a[SZH_Q_S1] = szh_q_dbits(s_d); a[SZH_Q_S2] = szh_q_dbits(s_dd); a[SZH_Q_S3] = szh_q_dbits(s_ee);
-    szh_q_block_merge(a, slots + (size_t)blockIdx.x * SZH_Q_WORDS);
+    szh_q_block_merge(a, slot);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_quality_pass1(const T *__restrict__ ori, szh_qview VO, const T *__restrict__ dec, szh_qview VD, int64_t n,
+                                                       double abs_bound, double pw_rel_bound, unsigned long long *slots)
+{
+    szh_q_pass1_body<T>(ori, VO, dec, VD, n, abs_bound, pw_rel_bound, slots + (size_t)blockIdx.x * SZH_Q_WORDS);
 }
 
 // sz.c:595-597 around the means of pass 1, over the points pass 1 took: S0 = sum (ori - m1)(dec - m2), S1 = sum (ori - m1)^2, S2 = sum (dec - m2)^2
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(256) void k_quality_pass2(const T *__restrict__ ori
 }
 
 // one workgroup: the slots of `nslots` workgroups, in index order, into `out`
-__global__ __launch_bounds__(256) void k_quality_final(const unsigned long long *__restrict__ slots, int nslots, unsigned long long *out)
+__device__ __forceinline__ void szh_q_final_body(const unsigned long long *__restrict__ slots, int nslots, unsigned long long *out)
 {
     unsigned long long a[SZH_Q_WORDS];
     szh_q_neutral(a);
@@ -186,4 +192,46 @@ __global__ __launch_bounds__(256) void k_quality_final(const unsigned long long 
         szh_q_merge(a, b);
     }
     szh_q_block_merge(a, out);
+}
+__global__ __launch_bounds__(256) void k_quality_final(const unsigned long long *__restrict__ slots, int nslots, unsigned long long *out)
+{
+    szh_q_final_body(slots, nslots, out);
+}
+
+// ---- MANY PAIRS of one length in one launch (szhip_compare_batch): the bodies above with the pair as the grid's second dimension.  A pair's
+// workgroups are blockIdx.x = 0 .. szh_quality_grid(n) - 1 as in the single call and write the pair's own run of slots, which k_quality_final_batch merges with one
+// workgroup per pair -- the same values meet in the same order, so a pair's record is bit for bit the single call's.  Contiguous arrays only.
+struct szh_qpair { const void *ori, *dec; double abs_bound, pw_rel_bound, mean_ori, mean_dec; };
+
+template <class T>
+__global__ __launch_bounds__(256) void k_quality_pass1_batch(const szh_qpair *__restrict__ pairs, int64_t n, unsigned long long *slots)
+{
+    const szh_qpair P = pairs[blockIdx.y];
+    const szh_qview V = {1, n, n, n, 1};
+    szh_q_pass1_body<T>((const T *)P.ori, V, (const T *)P.dec, V, n, P.abs_bound, P.pw_rel_bound, slots + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SZH_Q_WORDS);
+}
+// (k_quality_pass2's text, repeated: as a wrapper of a shared body the single-call kernel compiled to 110 VGPRs instead of the 112 it had, and its registers are
+// pinned -- profiles/r17_quality_batch_kernel_resources.txt; as k_ompb_col repeats k_omp_col's)
+template <class T>
+__global__ __launch_bounds__(256) void k_quality_pass2_batch(const szh_qpair *__restrict__ pairs, int64_t n, unsigned long long *slots)
+{
+    const szh_qpair P = pairs[blockIdx.y];
+    const szh_qview V = {1, n, n, n, 1};
+    const double mean_ori = P.mean_ori, mean_dec = P.mean_dec;
+    double s_od = 0, s_oo = 0, s_dd = 0;
+    szh_q_sweep<T>((const T *)P.ori, V, (const T *)P.dec, V, n, [&](T o, T d, unsigned long long) {
+        const T diff = d - o;
+        if (o != o || d != d || diff != diff) return;
+        const double a = (double)o - mean_ori, b = (double)d - mean_dec;
+        s_od += a * b; s_oo += a * a; s_dd += b * b;
+    });
+    unsigned long long a[SZH_Q_WORDS];
+    szh_q_neutral(a);
+    a[SZH_Q_S0] = szh_q_dbits(s_od); a[SZH_Q_S1] = szh_q_dbits(s_oo); a[SZH_Q_S2] = szh_q_dbits(s_dd);
+    szh_q_block_merge(a, slots + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SZH_Q_WORDS);
+}
+// one workgroup per pair: the pair's `nslots` slots into its record of SZH_Q_WORDS words
+__global__ __launch_bounds__(256) void k_quality_final_batch(const unsigned long long *__restrict__ slots, int nslots, unsigned long long *out)
+{
+    szh_q_final_body(slots + (size_t)blockIdx.y * (size_t)nslots * SZH_Q_WORDS, nslots, out + (size_t)blockIdx.y * SZH_Q_WORDS);
 }

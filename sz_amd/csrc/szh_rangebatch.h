@@ -1,0 +1,63 @@
+// szh_rangebatch.h -- the value range of MANY arrays of one length in one launch (szhip_minmax_batch of include/szhip.h): what k_minmax
+// does for one array, with the array as the grid's second dimension and its base pointer taken from a device table.
+// Mapping.  An array of n values is cut at the 16-byte boundaries of ITS OWN address: a head of (16 - address % 16) % 16 bytes (fewer than VW = 16 / sizeof(T)
+// values: element alignment is all the contract asks, and with it a head always reaches a boundary), whole 16-byte PIECES, a tail of fewer than VW values.  Lane l of
+// the array's workgroups takes the pieces l, l + lanes, ... with one 16-byte load each, SZH_RB_UNROLL of them in flight; the head and the tail are read value by
+// value by lanes of the array's first workgroup.  So the arrays of one batch may lie at different offsets from a boundary and still all move 16 bytes per lane.
+// The grid (szh_rangebatch_grid) is a function of n alone: ceil(n / share) workgroups per array with share = 256 lanes x SZH_RB_UNROLL pieces x VW values, at most
+// SZH_RB_MAX_GRID; beyond n = SZH_RB_MAX_GRID x share a lane sweeps more than once.
+// Reduction.  Ordered integers (ord_enc), as k_minmax: min and max do not depend on the order in which values meet, so the result is bit for bit that of the single
+// call and no floating-point atomic is needed.  A NaN takes no part.  res[2 a] holds the COMPLEMENT of array a's smallest ordering (so that both words start from
+// zero bytes and both are reduced with atomicMax), res[2 a + 1] its largest; an array without a number leaves both 0.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+// (u64, ord_enc, wave_min_u64, wave_max_u64: szhip_kernels.h, included in front of this file by szhip.hip)
+
+constexpr int SZH_RB_UNROLL = 4;        // pieces a lane has in flight; a workgroup is sized for 256 x 4 of them
+constexpr int SZH_RB_MAX_GRID = 128;    // workgroups per array (the batch fills the chip through the grid's second dimension)
+
+static inline int szh_rangebatch_grid(uint64_t n, int vw)
+{
+    const uint64_t share = (uint64_t)256 * SZH_RB_UNROLL * (uint64_t)vw;
+    const uint64_t g = (n + share - 1) / share;
+    return (int)(g < 1 ? 1 : g > (uint64_t)SZH_RB_MAX_GRID ? (uint64_t)SZH_RB_MAX_GRID : g);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_minmax_batch(const T *const *__restrict__ bases, int64_t n, u64 *res)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    __shared__ u64 red[8];
+    const T *__restrict__ base = bases[blockIdx.y];
+    int64_t head = (int64_t)(((16u - (unsigned)((uintptr_t)base & 15u)) & 15u) / (unsigned)sizeof(T));
+    head = head < n ? head : n;
+    const int64_t pieces = (n - head) / VW, tail0 = head + pieces * VW;          // (tail0 + tail == n, tail < VW)
+    u64 lmin = ~0ull, lmax = 0ull;
+    auto take = [&](T v) { const u64 e = ord_enc(v); const bool num = v == v; lmin = num && e < lmin ? e : lmin; lmax = num && e > lmax ? e : lmax; };
+    const uint4 *__restrict__ vp = reinterpret_cast<const uint4 *>(base + head);
+    const int64_t lane = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x, lanes = (int64_t)gridDim.x * 256;
+    for (int64_t p0 = lane; p0 < pieces; p0 += lanes * SZH_RB_UNROLL) {
+        uint4 w[SZH_RB_UNROLL];
+        for (int u = 0; u < SZH_RB_UNROLL; ++u) { const int64_t p = p0 + (int64_t)u * lanes; if (p < pieces) w[u] = vp[p]; }
+        for (int u = 0; u < SZH_RB_UNROLL; ++u) {
+            if (p0 + (int64_t)u * lanes >= pieces) break;
+            T v[VW];
+            __builtin_memcpy(v, &w[u], 16);
+            for (int q = 0; q < VW; ++q) take(v[q]);
+        }
+    }
+    if (blockIdx.x == 0) {                                          // the head: lanes 0 .. head - 1; the tail: lanes VW .. VW + tail - 1
+        const int64_t t = (int64_t)threadIdx.x;
+        if (t < head) take(base[t]);
+        else if (t >= VW && t - VW < n - tail0) take(base[tail0 + t - VW]);
+    }
+    lmin = wave_min_u64(lmin); lmax = wave_max_u64(lmax);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = lmin; red[4 + (threadIdx.x >> 6)] = lmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 mn = red[0], mx = red[4];
+        for (int w = 1; w < 4; ++w) { mn = red[w] < mn ? red[w] : mn; mx = red[4 + w] > mx ? red[4 + w] : mx; }
+        atomicMax(&res[2 * (size_t)blockIdx.y], ~mn); atomicMax(&res[2 * (size_t)blockIdx.y + 1], mx);
+    }
+}

@@ -22,6 +22,7 @@
 #include "szhost.h"
 #include "szhip_kernels.h"
 #include "szh_quality.h"
+#include "szh_rangebatch.h"
 
 namespace {
 
@@ -186,7 +187,8 @@ namespace {
 #include "szhip_pwr.inc"     // point-wise relative bounds
 #include "szhip_omp.inc"     // the reference's OpenMP container
 #include "szhip_ompbatch.inc" // ... over many same-shape arrays in one call
-#include "szhip_quality.inc" // an array against its decoded copy: the error report
+#include "szhip_rangebatch.inc" // the value range of many arrays in one launch
+#include "szhip_quality.inc" // an array against its decoded copy: the error report, for one pair and for many
 
 } // namespace
 
@@ -421,6 +423,18 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
     return SZHIP_OK;
 }
 
+int szhip_stage_input_batch(szhip_ctx *ctx, const void *const *host_data, int count, size_t bytes, const void **device_ptrs)
+{
+    if (!ctx || !host_data || !device_ptrs || count < 1 || bytes == 0) return SZHIP_ERR_ARG;
+    for (int i = 0; i < count; ++i) if (!host_data[i]) return SZHIP_ERR_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    std::vector<const void *> d;
+    TRY(synced_on_failure(ctx, batch_stage(ctx, ctx->in, count, bytes, ctx->stream, [&](int i) { return host_data[i]; }, d)));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) device_ptrs[i] = d[i];
+    return SZHIP_OK;
+}
+
 // include/szhip.h, "Device pointers and ordering": a pointer to VALUES (`data`, `out` of a decompress call) is aligned to its element, on the host or on the device;
 // refused here, before anything is launched; then the context's device is made current.  Byte pointers (streams, parameter bytes, a caller's stream buffer) take any alignment.
 static int check_alignment_set_device(szhip_ctx *ctx, int dtype, const void *p)
@@ -439,6 +453,28 @@ int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int on_dev, size_t
     if (!ctx || !data || !n || !vmin || !vmax) return SZHIP_ERR_ARG;
     TRY(check_alignment_set_device(ctx, dtype, data));
     return BY_DTYPE(dtype, minmax_impl, ctx, data, on_dev, n, vmin, vmax);
+}
+
+// the refusals of the batch calls over arrays of n values, before anything is launched: SZHIP_ERR_ARG
+static int batch_pointers(szhip_ctx *ctx, int dtype, const void *const *p, int count, size_t n)
+{
+    if (!ctx || !p || count < 1 || n == 0 || (dtype != SZHIP_F32 && dtype != SZHIP_F64)) return SZHIP_ERR_ARG;
+    for (int i = 0; i < count; ++i) {
+        if (!p[i]) { snprintf(ctx->err, sizeof(ctx->err), "array %d of the batch: a null pointer", i); return SZHIP_ERR_ARG; }
+        if (((uintptr_t)p[i] & (dtype == SZHIP_F32 ? 3u : 7u)) != 0) {
+            snprintf(ctx->err, sizeof(ctx->err), "array %d of the batch: pointer %p is not aligned to its %d-byte elements", i, p[i], dtype == SZHIP_F32 ? 4 : 8);
+            return SZHIP_ERR_ARG;
+        }
+    }
+    return SZHIP_OK;
+}
+
+int szhip_minmax_batch(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t n, double *vmin, double *vmax, szhip_stats *stats)
+{
+    if (!vmin || !vmax) return SZHIP_ERR_ARG;
+    TRY(batch_pointers(ctx, dtype, data, count, n));
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, n, vmin, vmax, stats));
 }
 
 int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -648,6 +684,16 @@ int szhip_compare(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_device,
     TRY(check_alignment_set_device(ctx, dtype, ori));
     TRY(check_alignment_set_device(ctx, dtype, dec));
     return synced_on_failure(ctx, BY_DTYPE(dtype, quality_impl, ctx, ori, ori_on_device, n, n, dec, dec_on_device, n, n, 1, 1, n, abs_bound, pw_rel_bound, flags, q));
+}
+
+int szhip_compare_batch(szhip_ctx *ctx, int dtype, const void *const *ori, const void *const *dec, int count, int on_device, size_t n, const double *abs_bound,
+                        const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats)
+{
+    if (!abs_bound || !out) return SZHIP_ERR_ARG;
+    TRY(batch_pointers(ctx, dtype, ori, count, n));
+    TRY(batch_pointers(ctx, dtype, dec, count, n));
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_batch_impl, ctx, ori, dec, count, on_device, n, abs_bound, pw_rel_bound, flags, out, stats));
 }
 
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,

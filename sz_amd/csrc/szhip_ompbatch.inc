@@ -17,6 +17,23 @@ static int ompb_limits(szhip_ctx *ctx, int count, size_t nb, size_t n)
         FAIL(SZHIP_ERR_UNSUP, "OpenMP-container batch: %d arrays of %zu boxes and %zu values (at most 65535 arrays, 2^22 boxes and 2^32 - 1 values in all)", count, nb, n);
     return SZHIP_OK;
 }
+// `count` host arrays of `bytes` bytes each, one behind the other at multiples of 16 into `buf` (asynchronous on `st`; the callers' arrays have been read on return):
+// ONE copy through the context's pinned block when they total at most 64 MiB, else array by array.  d[i]: where array i lies then.
+template <class GET>
+int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_t st, GET &&host, std::vector<const void *> &d)
+{
+    const size_t stride = up16(bytes);
+    d.resize((size_t)count);
+    TRY(ensure(ctx, buf, (size_t)count * stride));
+    for (int i = 0; i < count; ++i) d[i] = (const char *)buf.p + (size_t)i * stride;
+    if ((size_t)count * stride <= ((size_t)64 << 20)) {
+        TRY(ensure_pinned3(ctx, (size_t)count * stride));
+        for (int i = 0; i < count; ++i) memcpy((char *)ctx->pinned3 + (size_t)i * stride, host(i), bytes);
+        HIPCHK(hipMemcpyAsync(buf.p, ctx->pinned3, (size_t)count * stride, hipMemcpyHostToDevice, st));
+    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)buf.p + (size_t)i * stride, host(i), bytes, true));
+    return SZHIP_OK;
+}
+
 // the device table of a batch in ctx->batch_rec: [totals: 4 u64 per array][records][LISTS lists of `count` array numbers][what a version of the table adds behind]
 enum { OMPB_L_ALL = 0, OMPB_L_F3, OMPB_L_F4, OMPB_L_F5, OMPB_L_ENT, OMPB_L_PACK, OMPB_LISTS };
 struct ompb_table {
@@ -64,17 +81,12 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
     const bool shared = g.bel % 8 == 0 && r0 > 1 && r1 > 1;
     if (!shared) state.assign((size_t)count, EARLY);
     // ---- 1. host arrays one behind the other into the context's input buffer
-    const size_t in_stride = up16(n * sizeof(T));
     std::vector<const T *> d_in((size_t)count);
     if (data_on_device) for (int i = 0; i < count; ++i) d_in[i] = (const T *)items[i].data;
     else {
-        TRY(ensure(ctx, ctx->in, (size_t)count * in_stride));
-        for (int i = 0; i < count; ++i) d_in[i] = (const T *)((const char *)ctx->in.p + (size_t)i * in_stride);
-        if ((size_t)count * in_stride <= ((size_t)64 << 20)) {
-            TRY(ensure_pinned3(ctx, (size_t)count * in_stride));
-            for (int i = 0; i < count; ++i) memcpy((char *)ctx->pinned3 + (size_t)i * in_stride, items[i].data, n * sizeof(T));
-            HIPCHK(hipMemcpyAsync(ctx->in.p, ctx->pinned3, (size_t)count * in_stride, hipMemcpyHostToDevice, st));
-        } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)ctx->in.p + (size_t)i * in_stride, items[i].data, n * sizeof(T), true));
+        std::vector<const void *> d;
+        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return items[i].data; }, d));
+        for (int i = 0; i < count; ++i) d_in[i] = (const T *)d[i];
     }
     // the single call for array i, from the device copy of it: its stream on the host until the blob is laid out
     std::vector<std::vector<unsigned char>> fb((size_t)count);

@@ -31,6 +31,43 @@ static int quality_collect(szhip_ctx *ctx, u64 *d_slots, int grid, u64 (&res)[SZ
 
 static double quality_double(u64 bits) { double d; memcpy(&d, &bits, 8); return d; }
 
+// pass 1's merged record `res` of n points into the report's counts, extremes and sums (everything else zero)
+template <class T>
+void quality_from_pass1(const u64 (&res)[SZH_Q_WORDS], size_t n, szhip_quality *out)
+{
+    szhip_quality q;
+    memset(&q, 0, sizeof(q));
+    q.n = n; q.n_excluded = res[SZH_Q_NEX]; q.n_excluded_diff = res[SZH_Q_NEXD]; q.n_zero_changed = res[SZH_Q_NZC];
+    q.n_over_abs = res[SZH_Q_NOA]; q.n_over_pwr = res[SZH_Q_NOP]; q.n_over_both = res[SZH_Q_NOB];
+    q.max_abs_idx = res[SZH_Q_EIDX]; q.first_over_idx = res[SZH_Q_FIRST];
+    const bool any = res[SZH_Q_EKEY] != 0;                          // (no point took part: every one was excluded)
+    q.vmin = any ? ord_dec<T>(res[SZH_Q_OMIN]) : NAN; q.vmax = any ? ord_dec<T>(res[SZH_Q_OMAX]) : NAN;
+    q.max_abs_err = any ? quality_double(res[SZH_Q_EKEY] - 1) : 0.0;
+    q.max_pw_rel_err = quality_double(res[SZH_Q_PW]);
+    q.sum_ori = quality_double(res[SZH_Q_S0]); q.sum_dec = quality_double(res[SZH_Q_S1]);
+    q.sum_dec_sq = quality_double(res[SZH_Q_S2]); q.sum_err_sq = quality_double(res[SZH_Q_S3]);
+    *out = q;
+}
+// pass 2's merged record into the centred sums
+static void quality_from_pass2(const u64 (&res)[SZH_Q_WORDS], szhip_quality *q)
+{
+    q->cov = quality_double(res[SZH_Q_S0]); q->var_ori = quality_double(res[SZH_Q_S1]); q->var_dec = quality_double(res[SZH_Q_S2]);
+}
+template <class T>
+void quality_derive(szhip_quality *out, unsigned flags)
+{
+    szhip_quality q = *out;
+    const double took_part = (double)(q.n - q.n_excluded);
+    // the derived values, by the formulas of example/sz.c:600-611 (the range of float data is the FLOAT difference, as `float Max - Min` there)
+    q.range = sizeof(T) == 4 ? (double)(float)((float)q.vmax - (float)q.vmin) : q.vmax - q.vmin;
+    q.mse = q.sum_err_sq / took_part;
+    q.psnr = 20 * log10(q.range) - 10 * log10(q.mse);
+    q.nrmse = sqrt(q.mse) / q.range;
+    q.norm_err = sqrt(q.sum_err_sq);
+    q.ac_eff = (flags & SZHIP_Q_CORR) ? q.cov / took_part / sqrt(q.var_ori / took_part) / sqrt(q.var_dec / took_part) : NAN;
+    *out = q;
+}
+
 template <class T>
 int quality_impl(szhip_ctx *ctx, const void *ori, int ori_on_device, size_t o_pitch0, size_t o_pitch1, const void *dec, int dec_on_device, size_t d_pitch0, size_t d_pitch1,
                  size_t r0, size_t r1, size_t r2, double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *out)
@@ -55,31 +92,75 @@ int quality_impl(szhip_ctx *ctx, const void *ori, int ori_on_device, size_t o_pi
     TRY(quality_collect(ctx, d_slots, grid, res));
 
     szhip_quality q;
-    memset(&q, 0, sizeof(q));
-    q.n = n; q.n_excluded = res[SZH_Q_NEX]; q.n_excluded_diff = res[SZH_Q_NEXD]; q.n_zero_changed = res[SZH_Q_NZC];
-    q.n_over_abs = res[SZH_Q_NOA]; q.n_over_pwr = res[SZH_Q_NOP]; q.n_over_both = res[SZH_Q_NOB];
-    q.max_abs_idx = res[SZH_Q_EIDX]; q.first_over_idx = res[SZH_Q_FIRST];
-    const bool any = res[SZH_Q_EKEY] != 0;                          // (no point took part: every one was excluded)
-    q.vmin = any ? ord_dec<T>(res[SZH_Q_OMIN]) : NAN; q.vmax = any ? ord_dec<T>(res[SZH_Q_OMAX]) : NAN;
-    q.max_abs_err = any ? quality_double(res[SZH_Q_EKEY] - 1) : 0.0;
-    q.max_pw_rel_err = quality_double(res[SZH_Q_PW]);
-    q.sum_ori = quality_double(res[SZH_Q_S0]); q.sum_dec = quality_double(res[SZH_Q_S1]);
-    q.sum_dec_sq = quality_double(res[SZH_Q_S2]); q.sum_err_sq = quality_double(res[SZH_Q_S3]);
+    quality_from_pass1<T>(res, n, &q);
     const double took_part = (double)(n - q.n_excluded);
     if (flags & SZHIP_Q_CORR) {
         hipLaunchKernelGGL((k_quality_pass2<T>), dim3(grid), dim3(256), 0, ctx->stream, d_ori, VO, d_dec, VD, (int64_t)n, q.sum_ori / took_part, q.sum_dec / took_part,
                            (unsigned long long *)d_slots);
         HIPCHK(hipGetLastError());
         TRY(quality_collect(ctx, d_slots, grid, res));
-        q.cov = quality_double(res[SZH_Q_S0]); q.var_ori = quality_double(res[SZH_Q_S1]); q.var_dec = quality_double(res[SZH_Q_S2]);
+        quality_from_pass2(res, &q);
     }
-    // the derived values, by the formulas of example/sz.c:600-611 (the range of float data is the FLOAT difference, as `float Max - Min` there)
-    q.range = sizeof(T) == 4 ? (double)(float)((float)q.vmax - (float)q.vmin) : q.vmax - q.vmin;
-    q.mse = q.sum_err_sq / took_part;
-    q.psnr = 20 * log10(q.range) - 10 * log10(q.mse);
-    q.nrmse = sqrt(q.mse) / q.range;
-    q.norm_err = sqrt(q.sum_err_sq);
-    q.ac_eff = (flags & SZHIP_Q_CORR) ? q.cov / took_part / sqrt(q.var_ori / took_part) / sqrt(q.var_dec / took_part) : NAN;
+    quality_derive<T>(&q, flags);
     *out = q;
     return SZHIP_OK;
+}
+
+// ---- many pairs of one length in one call (szhip_compare_batch): the steps above, each ONE launch with the pair as the grid's second dimension.  ctx->quality holds
+// [count x grid slots][count records][the pairs' table]; the table goes up once, and once more with the means of pass 1 when the correlation is asked for.
+template <class T>
+int quality_batch_impl(szhip_ctx *ctx, const void *const *ori, const void *const *dec, int count, int on_device, size_t n, const double *abs_bound,
+                       const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
+    TRY(batch_value_limits(ctx, "szhip_compare_batch", count, n));
+    S.n_elements = (uint64_t)count * n;
+    std::vector<const void *> d_ori(ori, ori + count), d_dec(dec, dec + count);
+    if (!on_device) {                                               // (both through the one pinned block: the first copy has left it before the second fills it)
+        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return ori[i]; }, d_ori));
+        HIPCHK(hipStreamSynchronize(st));
+        TRY(batch_stage(ctx, ctx->in2, count, n * sizeof(T), st, [&](int i) { return dec[i]; }, d_dec));
+    }
+    const int grid = szh_quality_grid(n, VW);
+    const size_t rec_bytes = (size_t)SZH_Q_WORDS * 8, o_res = (size_t)count * grid * rec_bytes, o_tab = o_res + (size_t)count * rec_bytes;
+    TRY(ensure(ctx, ctx->quality, o_tab + (size_t)count * sizeof(szh_qpair)));
+    TRY(ensure_pinned(ctx, (size_t)count * rec_bytes));
+    unsigned char *base = (unsigned char *)ctx->quality.p;
+    unsigned long long *d_slots = (unsigned long long *)base, *d_res = (unsigned long long *)(base + o_res);
+    const szh_qpair *d_tab = (const szh_qpair *)(base + o_tab);
+    std::vector<szh_qpair> tab((size_t)count), tab2;               // (pageable sources of the uploads: they live until the synchronisation behind each)
+    for (int i = 0; i < count; ++i) tab[i] = szh_qpair{d_ori[i], d_dec[i], abs_bound[i], pw_rel_bound ? pw_rel_bound[i] : -1.0, 0.0, 0.0};
+    HIPCHK(hipMemcpyAsync(base + o_tab, tab.data(), (size_t)count * sizeof(szh_qpair), hipMemcpyHostToDevice, st));
+    // the pairs' slots into their records, the records to the host: one launch, one read-back
+    auto collect = [&]() -> int {
+        hipLaunchKernelGGL(k_quality_final_batch, dim3(1, (unsigned)count), dim3(256), 0, st, (const unsigned long long *)d_slots, grid, d_res);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctx->pinned, d_res, (size_t)count * rec_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return SZHIP_OK;
+    };
+    typedef const u64 (&rec_ref)[SZH_Q_WORDS];
+    auto rec = [&](int i) -> rec_ref { return *(const u64 (*)[SZH_Q_WORDS])((const u64 *)ctx->pinned + (size_t)i * SZH_Q_WORDS); };
+    hipLaunchKernelGGL((k_quality_pass1_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
+    HIPCHK(hipGetLastError());
+    S.quant_kernel_launches = 1;
+    TRY(collect());
+    std::vector<szhip_quality> q((size_t)count);
+    for (int i = 0; i < count; ++i) quality_from_pass1<T>(rec(i), n, &q[i]);
+    if (flags & SZHIP_Q_CORR) {
+        tab2 = tab;
+        for (int i = 0; i < count; ++i) {
+            const double took_part = (double)(n - q[i].n_excluded);
+            tab2[i].mean_ori = q[i].sum_ori / took_part; tab2[i].mean_dec = q[i].sum_dec / took_part;
+        }
+        HIPCHK(hipMemcpyAsync(base + o_tab, tab2.data(), (size_t)count * sizeof(szh_qpair), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((k_quality_pass2_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
+        HIPCHK(hipGetLastError());
+        TRY(collect());
+        for (int i = 0; i < count; ++i) quality_from_pass2(rec(i), &q[i]);
+    }
+    for (int i = 0; i < count; ++i) { quality_derive<T>(&q[i], flags); out[i] = q[i]; }
+    S.ms_total = now_ms() - cb.t_begin;
+    return cb.done(stats);
 }

@@ -1,0 +1,39 @@
+// szhip_rangebatch.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace, behind szhip_ompbatch.inc): the value range of many
+// arrays of one length in one launch (include/szhip.h: szhip_minmax_batch; kernel: szh_rangebatch.h; DESIGN section 4.5.5).
+
+// the limits of the batch calls over `count` arrays of n values (those of ompb_limits that do not speak of boxes)
+static int batch_value_limits(szhip_ctx *ctx, const char *who, int count, size_t n)
+{
+    if (count > 65535 || n >= ((size_t)1 << 32) || (size_t)count * n >= ((size_t)1 << 32))
+        FAIL(SZHIP_ERR_UNSUP, "%s: %d arrays of %zu values (at most 65535 arrays and 2^32 - 1 values in all)", who, count, n);
+    return SZHIP_OK;
+}
+
+template <class T>
+int minmax_batch_impl(szhip_ctx *ctx, const void *const *data, int count, int on_dev, size_t n, double *vmin, double *vmax, szhip_stats *stats)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
+    TRY(batch_value_limits(ctx, "szhip_minmax_batch", count, n));
+    S.n_elements = (uint64_t)count * n;
+    // ---- host arrays one behind the other into the context's input buffer; the table of base pointers, uploaded once
+    std::vector<const void *> d_in(data, data + count);
+    if (!on_dev) TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return data[i]; }, d_in));
+    const size_t o_res = up64((size_t)count * sizeof(void *));
+    TRY(ensure(ctx, ctx->batch_rec, o_res + (size_t)count * 16));
+    TRY(ensure_pinned(ctx, (size_t)count * 16));
+    unsigned char *tab = (unsigned char *)ctx->batch_rec.p;
+    HIPCHK(hipMemcpyAsync(tab, d_in.data(), (size_t)count * sizeof(void *), hipMemcpyHostToDevice, st));      // (`d_in` lives until the synchronisation below)
+    HIPCHK(hipMemsetAsync(tab + o_res, 0, (size_t)count * 16, st));
+    // ---- one launch, one read-back
+    const int grid = szh_rangebatch_grid(n, VW);
+    hipLaunchKernelGGL((k_minmax_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, (const T *const *)tab, (int64_t)n, (u64 *)(tab + o_res));
+    HIPCHK(hipGetLastError());
+    S.quant_kernel_launches = 1;
+    HIPCHK(hipMemcpyAsync(ctx->pinned, tab + o_res, (size_t)count * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const u64 *res = (const u64 *)ctx->pinned;
+    for (int i = 0; i < count; ++i) { vmin[i] = ord_dec<T>(~res[2 * (size_t)i]); vmax[i] = ord_dec<T>(res[2 * (size_t)i + 1]); }
+    S.ms_total = now_ms() - cb.t_begin;
+    return cb.done(stats);
+}
