@@ -312,13 +312,34 @@ void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int i
  * SZ_hip_compare_batch: szhip_compare_batch (szhip.h) on `count` pairs of r1 x r2 x r3 values, pair i against absBound[i] and pwRelBound[i] (pwRelBound NULL: not
  * asked): out[i] is byte for byte SZ_hip_compare's record for pair i.
  * SZ_hip_last_stats after each call: the stats of its shared launches (quant_kernel_launches: the sweep launches, one per form; the pass-1 launches of the report).
- * Not covered: batches of mixed shape, the lossless stage, point-wise relative modes, views, the slab container. */
+ * Not covered: batches of mixed shape, the lossless stage, point-wise relative modes, the slab container; sub-boxes: the three *_region calls below. */
 int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
                                size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched);
 int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
                             size_t r1, size_t r2, size_t r3);
 int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
                          const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out);
+/* ---- the three calls above on ONE BOX [start, end) common to `count` 3-D parents of r1 x r2 x r3 values (r1 slowest; start / end as in SZ_hip_compress_region): the
+ * interiors of patches with ghost layers.  parents[i] points at parent i's first value; the ghost cells are neither read into a stream or a
+ * range nor written.
+ * SZ_hip_compress_args_batch_region: streams[i] is byte for byte what SZ_hip_compress_args_batch returns for contiguous copies of the sub-boxes -- the same modes,
+ * refusals (on the sub-box's extents) and per-item failure rule.  The range is the sub-box's own, from ONE szhip_minmax_batch_view launch; the items with
+ * range > bound > 0 go through one szhip_compress_omp_batch_view; a constant sub-box gets the reference's constant stream (of a device parent only the sub-box's
+ * first value crosses the bus); a bound that is not positive takes SZ_compress_args' ordinary path from a packed copy of that one item (szhip_pack_view).  Of host
+ * parents only the sub-boxes' rows cross the bus, once for the ranges and once for the streams.
+ * SZ_hip_decompress_batch_into_region accepts what SZ_hip_decompress_batch accepts and writes into sub-box i bit for bit what that call writes into out[i], and no
+ * other byte of a parent: containers through one szhip_decompress_omp_batch_view, every other stream (constant streams among them) decoded whole and then placed
+ * through the pitches (szhip_scatter_view for a device parent); of a stream that fails nothing reaches its parent.
+ * SZ_hip_compare_batch_region: szhip_compare_batch_view on the sub-boxes of ori_parents[i] and dec_parents[i]; out[i] is byte for byte SZ_hip_compare's record of
+ * contiguous copies of pair i.
+ * SZ_NSCS with a printed reason and nothing launched or written: a null parent, a parent that is not 3-D, start[d] >= end[d] or end[d] beyond the extent. */
+int SZ_hip_compress_args_batch_region(int dataType, int count, const void *const *parents, int data_on_device, int errBoundMode, double absErrBound,
+                                      double relBoundRatio, size_t r1, size_t r2, size_t r3, const size_t start[3], const size_t end[3],
+                                      unsigned char **streams, size_t *comp_sizes, int *batched);
+int SZ_hip_decompress_batch_into_region(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *parents, int out_on_device,
+                                        size_t r1, size_t r2, size_t r3, const size_t start[3], const size_t end[3]);
+int SZ_hip_compare_batch_region(int dataType, int count, const void *const *ori_parents, const void *const *dec_parents, int on_device, size_t r1, size_t r2, size_t r3,
+                                const size_t start[3], const size_t end[3], const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out);
 /* per-call measurements of the last SZ_compress_args / SZ_decompress on this thread's context; see szhip.h */
 struct szhip_stats;
 int SZ_hip_last_stats(struct szhip_stats *out);

@@ -67,7 +67,8 @@ typedef struct szhip_stats {
     double vmin, vmax;      /* the array's range when SZHIP_RANGE_FROM_DATA was set (else 0) */
     int chain_overlapped;   /* 1: the regression-coefficient chain ran next to the wavefront kernel */
     int quant_kernel;       /* which mapping of the wavefront kernel ran: 0 = k_pencil (8x8 pencils), 2 = k_beam (szh_beam.h); the OpenMP container: 3 = k_omp_col (32 x 32 box faces, 16-byte aligned array), 4 = k_omp_box reading rows 16 bytes at a time, 5 = k_omp_box value by value */
-    int packing;            /* (round 6) 1: the Huffman packing read the sweep's natural-order codes segment by segment (szh_segenc.h); 0: block-ordered copy first */
+    int packing;            /* (round 6) 1: the Huffman packing read the sweep's natural-order codes segment by segment (szh_segenc.h); 0: block-ordered copy first.
+                               The batched view calls (szhip_*_omp_batch_view): the number of gather / scatter launches of the call, 0 or 1 whatever `count` is */
     int book_on_device;     /* 1: the Huffman code book of this stream was built on the device (SZ_HIP_DEV_BOOK=1, szh_book.h); 0: on the host */
 } szhip_stats;
 
@@ -131,6 +132,15 @@ int szhip_minmax(szhip_ctx *ctx, int dtype, const void *data, int data_on_device
  */
 int szhip_minmax_batch(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t n, double *vmin, double *vmax,
                        szhip_stats *stats);
+/*
+ * ... of `count` SUB-BOXES of r0 x r1 x r2 values with the common element pitches pitch0 / pitch1 (the VIEWS below; data[i] is sub-box i's first value), still one
+ * launch and one read-back: every ROW is cut at its own 16-byte boundaries as the call above cuts every array (k_minmax_batch_view: a group of lanes per row), so
+ * vmin[i] / vmax[i] are bit for bit szhip_minmax of a contiguous copy of sub-box i, and nothing outside the sub-boxes is read.  pitch1 == r2 with pitch0 == r1 * r2 is
+ * the call above, exactly.  Sub-boxes on the host: their rows alone are staged, packed.  Arguments and limits as above, on r0 x r1 x r2 values; pitch1 < r2 or
+ * pitch0 < r1 * pitch1: SZHIP_ERR_ARG.
+ */
+int szhip_minmax_batch_view(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t r0, size_t r1, size_t r2,
+                            size_t pitch0, size_t pitch1, double *vmin, double *vmax, szhip_stats *stats);
 
 /*
  * Compress a 3-D array (r0 slowest ... r2 fastest, the callee convention of sz_float.c:6527) with
@@ -241,7 +251,8 @@ int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *
  * value-by-value head and tail per row, no read of the view) or on the host.  Both take 2-D views as r0 == 0 (pitch0 is ignored).
  * Costs (MI355X, 512^3 float32, device-resident): the direct calls on an aligned view 1.04 x / 1.03 x the contiguous calls and 0.85 x / 0.83 x pack + compress /
  * decompress + scatter; packing 0.15 ms, scattering 0.24 ms; SZ 2.1 from a view 1.11 x the contiguous call.
- * Not covered: a strided szhip_minmax, region decode into a view, the slab container.
+ * Many views of one shape in one call: szhip_compress_omp_batch_view / szhip_decompress_omp_batch_view, szhip_minmax_batch_view, szhip_compare_batch_view (below).
+ * Not covered: a strided single-array szhip_minmax (szhip_minmax_batch_view with count 1 serves), region decode into a view, the slab container.
  */
 int szhip_compress_omp_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
                             double eb, int thread_num, const szhip_params *params, const unsigned char *meta, size_t meta_len,
@@ -296,6 +307,35 @@ int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items,
                              const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats);
 int szhip_decompress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
                                int out_on_device, szhip_stats *stats);
+/*
+ * BATCHES OF VIEWS: many same-shape PATCHES WITH GHOST LAYERS in one call -- the interiors of the padded arrays of a block-structured code.
+ * The batch calls above on sub-boxes: r0 x r1 x r2, dtype, thread_num, params, meta_len, the pointer kinds AND the two element pitches (the meaning and the rules of
+ * the VIEWS above: pitch1 >= r2, pitch0 >= r1 * pitch1, pitch0 need not be a multiple of pitch1; anything else SZHIP_ERR_ARG before anything is launched or written)
+ * are common; items[i].data / items[i].out is the FIRST VALUE of sub-box i.  pitch1 == r2 with pitch0 == r1 * r2 is the contiguous batch call, exactly.
+ * The bar is the union of the two bars: blob[offset_i, offset_i + size_i) is byte for byte what szhip_compress_omp makes from a contiguous copy of sub-box i; the
+ * batched decode writes into sub-box i bit for bit what szhip_decompress_omp writes, and no other byte of any parent -- not between rows, not between planes, not in
+ * the ghost layers, not in front or behind; inputs are never written.
+ * Form PER ITEM, from its own base address and the common pitches (items[i].quant_kernel):
+ *   - base, pitch1 and pitch0 all multiples of 16 bytes: the column form (3) or the vector box form (4) DIRECTLY on the parent, through the pitches;
+ *   - any of them off, boxes with 32 x 32 faces (e.g. float32 with 1 - 3 ghost values): the view is GATHERED into (decoded in) a contiguous copy in the context's
+ *     input (output) buffer and runs the column form there; quant_kernel reports 3, as the single view call does.  ONE gather launch (k_ompb_crop) covers all such
+ *     items of a compress call, ONE scatter launch (k_ompb_view_scatter: 16 bytes per lane between the 16-byte boundaries of each destination row, a value-by-value
+ *     head and tail, no read of the view) all such items of a decode that decoded without error -- of a damaged stream nothing reaches its parent;
+ *   - any other view that misses the 16 bytes: the value-by-value form (5) where it lies.
+ * stats->quant_kernel_launches: one sweep launch per form AND addressing (direct / gathered) that occurs in the batch -- at most 2 (the column shape: 3 direct and 3
+ * gathered; any other shape: 4 and 5); stats->packing: the gather / scatter launches of the call, counted where they are launched: 0 or 1.  Neither grows with `count`, nor do the synchronisations and copies.
+ * The interval optimiser samples every view where it lies (k_ompb_sample_view: the lattice of the contiguous copy, addresses through the pitches).
+ * Fallbacks, errors and limits are those of the contiguous batch calls on the sub-box's extents; a fallback item runs szhip_compress_omp_view /
+ * szhip_decompress_omp_view from inside the call (items[i].batched = 0).  Views on the HOST (data_on_device / out_on_device = 0): only the sub-boxes' rows cross the
+ * bus, staged one behind the other; then the contiguous batch runs, and of a damaged stream nothing reaches the caller's parent.  out_on_device = 2 of the compress
+ * call stays SZHIP_ERR_UNSUP.  A device view inside the context's input buffer (what szhip_stage_input handed out) is SZHIP_ERR_ARG before anything is launched: the gather uses that buffer.
+ * Cost (MI355X, 64 patches of 64^3 float32, device-resident): DESIGN section 4.5.6.
+ */
+int szhip_compress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2,
+                                  size_t pitch0, size_t pitch1, int thread_num, const szhip_params *params, size_t meta_len, int out_on_device,
+                                  unsigned char **blob, size_t *blob_size, szhip_stats *stats);
+int szhip_decompress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
+                                    int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats);
 
 /*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of
@@ -432,7 +472,7 @@ int szhip_compare_view(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_de
                        const void *dec, int dec_on_device, size_t d_pitch0, size_t d_pitch1, size_t r0, size_t r1, size_t r2,
                        double abs_bound, double pw_rel_bound, unsigned flags, szhip_quality *q);
 /*
- * ... for `count` PAIRS of contiguous arrays of n values each (no views), each pair against its own bounds (abs_bound[i]; pw_rel_bound[i], or pw_rel_bound == NULL:
+ * ... for `count` PAIRS of contiguous arrays of n values each (views: szhip_compare_batch_view, below), each pair against its own bounds (abs_bound[i]; pw_rel_bound[i], or pw_rel_bound == NULL:
  * not asked), in a number of launches, copies and synchronisations that does not grow with `count`: one pass-1 launch with the pair as the grid's second dimension,
  * one final launch with one workgroup per pair, one read-back of `count` records -- and the same again around the per-pair means with SZHIP_Q_CORR.
  * out[i] is BYTE FOR BYTE (memcmp of the struct) what szhip_compare returns for pair i alone, sums included: a pair's workgroups, slots and merge tree are those of the
@@ -443,6 +483,15 @@ int szhip_compare_view(szhip_ctx *ctx, int dtype, const void *ori, int ori_on_de
  */
 int szhip_compare_batch(szhip_ctx *ctx, int dtype, const void *const *ori, const void *const *dec, int count, int on_device, size_t n,
                         const double *abs_bound, const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats);
+/*
+ * ... for `count` pairs of BOXES of r0 x r1 x r2 values: every ori[i] lies in an array with the element pitches o_pitch0 / o_pitch1, every dec[i] in one with
+ * d_pitch0 / d_pitch1 (common to the batch; the pointers are the boxes' first values).  out[i] is byte for byte szhip_compare_view's record for pair i alone -- which
+ * is that of the contiguous copies --, in the launches, copies and synchronisations of the call above.  Contiguous pitches on both sides: the call above, exactly.
+ * Boxes on the host are staged packed.  Nothing outside the boxes is read, nothing is written.  Arguments and limits as above plus those of szhip_compare_view.
+ */
+int szhip_compare_batch_view(szhip_ctx *ctx, int dtype, const void *const *ori, size_t o_pitch0, size_t o_pitch1, const void *const *dec, size_t d_pitch0,
+                             size_t d_pitch1, int count, int on_device, size_t r0, size_t r1, size_t r2, const double *abs_bound, const double *pw_rel_bound,
+                             unsigned flags, szhip_quality *out, szhip_stats *stats);
 
 /* test/diagnostic hook: copy the first `bytes` bytes of an internal device workspace of the LAST call to host.
  * which: 0 coef (T SoA[4][nblocks]) 1 blk_lor (u8) 2 codes in natural order (u16) 3 codes in block order (u16)

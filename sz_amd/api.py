@@ -252,6 +252,29 @@ def _bind(L):
         L.szhip_compare_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, vpp, vpp, ctypes.c_int, ctypes.c_int, sz, dp, dp, ctypes.c_uint,
                                           ctypes.POINTER(szhip_quality), ctypes.POINTER(szhip_stats)]
         L.szhip_compare_batch.restype = ctypes.c_int
+    if hasattr(L, "szhip_compress_omp_batch_view"):
+        vpp, dp = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double)
+        L.szhip_compress_omp_batch_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.c_int, ctypes.c_int, sz, sz, sz, sz, sz, ctypes.c_int,
+                                                    ctypes.POINTER(szhip_params), sz, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz),
+                                                    ctypes.POINTER(szhip_stats)]
+        L.szhip_compress_omp_batch_view.restype = ctypes.c_int
+        L.szhip_decompress_omp_batch_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.c_int, ctypes.c_int, sz, sz, sz, ctypes.c_int,
+                                                      sz, sz, ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_batch_view.restype = ctypes.c_int
+        L.szhip_minmax_batch_view.argtypes = [ctypes.c_void_p, ctypes.c_int, vpp, ctypes.c_int, ctypes.c_int, sz, sz, sz, sz, sz, dp, dp, ctypes.POINTER(szhip_stats)]
+        L.szhip_minmax_batch_view.restype = ctypes.c_int
+        L.szhip_compare_batch_view.argtypes = [ctypes.c_void_p, ctypes.c_int, vpp, sz, sz, vpp, sz, sz, ctypes.c_int, ctypes.c_int, sz, sz, sz, dp, dp, ctypes.c_uint,
+                                               ctypes.POINTER(szhip_quality), ctypes.POINTER(szhip_stats)]
+        L.szhip_compare_batch_view.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_compress_args_batch_region"):
+        vpp, dp, szp = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(sz)
+        L.SZ_hip_compress_args_batch_region.argtypes = [ctypes.c_int, ctypes.c_int, vpp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, sz, sz, sz, szp, szp,
+                                                        vpp, szp, ctypes.POINTER(ctypes.c_int)]
+        L.SZ_hip_compress_args_batch_region.restype = ctypes.c_int
+        L.SZ_hip_decompress_batch_into_region.argtypes = [ctypes.c_int, ctypes.c_int, vpp, szp, vpp, ctypes.c_int, sz, sz, sz, szp, szp]
+        L.SZ_hip_decompress_batch_into_region.restype = ctypes.c_int
+        L.SZ_hip_compare_batch_region.argtypes = [ctypes.c_int, ctypes.c_int, vpp, vpp, ctypes.c_int, sz, sz, sz, szp, szp, dp, dp, ctypes.c_int, ctypes.POINTER(szhip_quality)]
+        L.SZ_hip_compare_batch_region.restype = ctypes.c_int
     if hasattr(L, "SZ_hip_compress_args_batch"):
         vpp, dp = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_double)
         L.SZ_hip_compress_args_batch.argtypes = [ctypes.c_int, ctypes.c_int, vpp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, sz, sz, sz,
@@ -531,6 +554,62 @@ def SZ_hip_compare_batch(ori_ptrs, dec_ptrs, on_device, shape, dtype, absBounds,
     return [_quality(out[i]) for i in range(count)]
 
 
+def _box3(lo, hi):
+    return (ctypes.c_size_t * 3)(*[int(v) for v in lo]), (ctypes.c_size_t * 3)(*[int(v) for v in hi])
+
+
+def SZ_hip_compress_args_batch_region(parent_ptrs, on_device, parent_shape, dtype, lo, hi, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, raise_on_error=True):
+    """include/sz.h: SZ_hip_compress_args_batch on the box [lo, hi) common to `len(parent_ptrs)` 3-D parents of `parent_shape` / `dtype` (patches with ghost layers;
+    the pointers are the parents' first values).  Returns (rc, streams, batched): stream i is byte for byte that of a contiguous copy of sub-box i."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(parent_ptrs)
+    c_ptrs = (ctypes.c_void_p * max(count, 1))(*parent_ptrs)
+    c_lo, c_hi = _box3(lo, hi)
+    streams, sizes, batched = (ctypes.c_void_p * max(count, 1))(), (ctypes.c_size_t * max(count, 1))(), (ctypes.c_int * max(count, 1))()
+    rc = lib().SZ_hip_compress_args_batch_region(dt, count, c_ptrs, 1 if on_device else 0, errBoundMode, absErrBound, relBoundRatio, parent_shape[0], parent_shape[1],
+                                                 parent_shape[2], c_lo, c_hi, streams, sizes, batched)
+    out = [ctypes.string_at(streams[i], sizes[i]) if streams[i] else None for i in range(count)]
+    for i in range(count):
+        if streams[i]:
+            lib().free(streams[i])
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_compress_args_batch_region failed ({rc})")
+    return rc, out, [batched[i] for i in range(count)]
+
+
+def SZ_hip_decompress_batch_into_region(streams, parent_ptrs, out_on_device, parent_shape, dtype, lo, hi, raise_on_error=True):
+    """include/sz.h: streams[i] into the box [lo, hi) of the parent at parent_ptrs[i] (host, or device with out_on_device); no other byte of a parent is written.
+    Returns rc: SZ_NSCS when any item failed (the others are decoded)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(streams)
+    keep = [ctypes.create_string_buffer(bytes(s), len(s)) for s in streams]
+    c_streams = (ctypes.c_void_p * max(count, 1))(*[ctypes.addressof(k) for k in keep])
+    c_sizes = (ctypes.c_size_t * max(count, 1))(*[len(s) for s in streams])
+    c_out = (ctypes.c_void_p * max(count, 1))(*parent_ptrs)
+    c_lo, c_hi = _box3(lo, hi)
+    rc = lib().SZ_hip_decompress_batch_into_region(dt, count, c_streams, c_sizes, c_out, 1 if out_on_device else 0, parent_shape[0], parent_shape[1], parent_shape[2],
+                                                   c_lo, c_hi)
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_decompress_batch_into_region failed ({rc})")
+    return rc
+
+
+def SZ_hip_compare_batch_region(ori_parent_ptrs, dec_parent_ptrs, on_device, parent_shape, dtype, lo, hi, absBounds, pwRelBounds=None, corr=False):
+    """include/sz.h: the boxes [lo, hi) of `len(ori_parent_ptrs)` pairs of parents against each other, pair i against absBounds[i] (and pwRelBounds[i]): a list of
+    Quality, record i byte for byte SZ_hip_compare's for contiguous copies of pair i."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(ori_parent_ptrs)
+    c_ori, c_dec = (ctypes.c_void_p * max(count, 1))(*ori_parent_ptrs), (ctypes.c_void_p * max(count, 1))(*dec_parent_ptrs)
+    c_abs = (ctypes.c_double * max(count, 1))(*[float(b) for b in absBounds])
+    c_pwr = (ctypes.c_double * max(count, 1))(*[float(b) for b in pwRelBounds]) if pwRelBounds is not None else None
+    c_lo, c_hi = _box3(lo, hi)
+    out = (szhip_quality * max(count, 1))()
+    if lib().SZ_hip_compare_batch_region(dt, count, c_ori, c_dec, 1 if on_device else 0, parent_shape[0], parent_shape[1], parent_shape[2], c_lo, c_hi, c_abs, c_pwr,
+                                         SZHIP_Q_CORR if corr else 0, out) != SZ_SCES:
+        raise SZError("SZ_hip_compare_batch_region failed")
+    return [_quality(out[i]) for i in range(count)]
+
+
 def sz_slab_compress(data, slabs, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, pwrBoundRatio=0.0):
     """include/sz_slab.h: a 3-D array as `slabs` slabs in one container (bytes)."""
     a = np.ascontiguousarray(data)
@@ -797,6 +876,69 @@ class HipContext:
         if rc and raise_on_error:
             self._err(rc, "szhip_decompress_omp_batch")
         return rc, items, st
+
+    def compress_omp_batch_view(self, ptrs, on_device, shape3, pitches, dtype, bounds, thread_num, metas, params=None, out_on_device=False, raise_on_error=True):
+        """szhip_compress_omp_batch_view: compress_omp_batch on len(ptrs) sub-boxes of shape3 values, ptrs[i] the first value of sub-box i inside its parent array,
+        pitches = (pitch0, pitch1) in elements, common to all (patches with ghost layers).  Stream i is byte for byte that of a contiguous copy of sub-box i.
+        Returns (rc, blob, blob_size, items, stats) as compress_omp_batch; stats.packing counts the gather launches (0 or 1)."""
+        count = len(ptrs)
+        items = (szhip_batch_item * max(count, 1))()
+        keep = [ctypes.create_string_buffer(bytes(m), len(m)) for m in metas]
+        for i in range(count):
+            items[i].data, items[i].eb, items[i].meta = ptrs[i], bounds[i], ctypes.addressof(keep[i]) if metas[i] is not None else None
+        p = params or szhip_params(100, 0.99, 65536, 0)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(0), szhip_stats()
+        rc = lib().szhip_compress_omp_batch_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, count, int(on_device), shape3[0], shape3[1], shape3[2],
+                                                 int(pitches[0]), int(pitches[1]), thread_num, ctypes.byref(p), len(metas[0]) if count else 0, int(out_on_device),
+                                                 ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_compress_omp_batch_view")
+        if out_on_device or not out.value:
+            return rc, out.value, n.value, items, st
+        b = ctypes.string_at(out.value, n.value)
+        lib().free(out)
+        return rc, b, n.value, items, st
+
+    def decompress_omp_batch_view(self, streams, stream_on_device, body_off, shape3, dtype, out_ptrs, out_on_device, pitches, raise_on_error=True):
+        """szhip_decompress_omp_batch_view: decompress_omp_batch into len(streams) sub-boxes of shape3 values, out_ptrs[i] the first value of sub-box i inside its parent,
+        pitches = (pitch0, pitch1) in elements, common to all; no other byte of a parent is written.  Returns (rc, items, stats)."""
+        count = len(streams)
+        items = (szhip_batch_item * max(count, 1))()
+        for i in range(count):
+            items[i].stream, items[i].stream_len, items[i].body_off, items[i].out = streams[i][0], streams[i][1], body_off, out_ptrs[i]
+        st = szhip_stats()
+        rc = lib().szhip_decompress_omp_batch_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, count, int(stream_on_device), shape3[0], shape3[1], shape3[2],
+                                                   int(out_on_device), int(pitches[0]), int(pitches[1]), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_decompress_omp_batch_view")
+        return rc, items, st
+
+    def minmax_batch_view(self, ptrs, on_device, shape3, pitches, dtype, raise_on_error=True):
+        """szhip_minmax_batch_view: the value ranges of len(ptrs) sub-boxes of shape3 values (ptrs[i]: the first value; pitches = (pitch0, pitch1) in elements) in one
+        launch.  Returns (rc, [(vmin, vmax), ...], stats); pair i is bit for bit minmax of a contiguous copy of sub-box i."""
+        count = len(ptrs)
+        c_ptrs = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        lo, hi, st = (ctypes.c_double * max(count, 1))(), (ctypes.c_double * max(count, 1))(), szhip_stats()
+        rc = lib().szhip_minmax_batch_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ptrs, count, int(on_device), shape3[0], shape3[1], shape3[2],
+                                           int(pitches[0]), int(pitches[1]), lo, hi, ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_minmax_batch_view")
+        return rc, [(lo[i], hi[i]) for i in range(count)], st
+
+    def compare_batch_view(self, ori_ptrs, ori_pitches, dec_ptrs, dec_pitches, on_device, shape3, dtype, abs_bounds, pw_rel_bounds=None, corr=False, raise_on_error=True):
+        """szhip_compare_batch_view: len(ori_ptrs) pairs of boxes of shape3 values, the originals with ori_pitches, the decoded ones with dec_pitches (each (pitch0,
+        pitch1) in elements, common to the batch).  Returns (rc, [Quality, ...], stats); record i is byte for byte compare_view of pair i alone."""
+        count = len(ori_ptrs)
+        c_ori, c_dec = (ctypes.c_void_p * max(count, 1))(*ori_ptrs), (ctypes.c_void_p * max(count, 1))(*dec_ptrs)
+        c_abs = (ctypes.c_double * max(count, 1))(*[float(b) for b in abs_bounds])
+        c_pwr = (ctypes.c_double * max(count, 1))(*[float(b) for b in pw_rel_bounds]) if pw_rel_bounds is not None else None
+        out, st = (szhip_quality * max(count, 1))(), szhip_stats()
+        rc = lib().szhip_compare_batch_view(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ori, int(ori_pitches[0]), int(ori_pitches[1]), c_dec,
+                                            int(dec_pitches[0]), int(dec_pitches[1]), count, int(on_device), shape3[0], shape3[1], shape3[2], c_abs, c_pwr,
+                                            SZHIP_Q_CORR if corr else 0, out, ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_compare_batch_view")
+        return rc, [_quality(out[i]) for i in range(count)], st
 
     def decompress_omp_region(self, stream_ptr, stream_on_device, stream_len, body_off, shape3, dtype, lo, hi, out_ptr, out_on_device):
         """The sub-box [lo, hi) (per dimension, dim 0 slowest, hi exclusive) of an OpenMP-container stream (szhip_decompress_omp_region): only the boxes that

@@ -1644,10 +1644,12 @@ int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, si
     return compare_fp(dataType, d_ori, d_dec, 1, r5, r4, r3, r2, r1, absBound, pwRelBound, flags, out);
 }
 /* ---- SZ_compress_args over many same-shape 3-D arrays in one call, the inverse, and the error report over the round trip (sz.h) */
-int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
-                               size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched)
+/* (the arrays are r1 x r2 x r3 values whose planes lie pitch0 and whose rows pitch1 elements apart, data[i] the first value of array i: r2 * r3 and r3 for
+ * SZ_hip_compress_args_batch, the parents' for SZ_hip_compress_args_batch_region, which has checked its box) */
+static int compress_args_batch_at(const char *who, int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound,
+                                  double relBoundRatio, size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1, unsigned char **streams, size_t *comp_sizes, int *batched)
 {
-    static const char *const who = "SZ_hip_compress_args_batch";
+    const int view = pitch1 != r3 || pitch0 != r2 * r3;
     if (count < 1 || !data || !streams || !comp_sizes || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
     for (int i = 0; i < count; ++i) { streams[i] = NULL; comp_sizes[i] = 0; if (batched) batched[i] = 0; }
     for (int i = 0; i < count; ++i) if (!data[i]) { printf("Error: %s: array %d is a null pointer.\n", who, i); return SZ_NSCS; }
@@ -1678,11 +1680,12 @@ int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data,
     szhip_params hp; memset(&hp, 0, sizeof(hp));
     if (!d_in || !vmin || !items || !metas || !idx) { printf("Error: %s: out of memory.\n", who); goto done; }
     /* 1. host arrays cross the bus once; 2. every array's range in one launch */
-    if (data_on_device) memcpy(d_in, data, (size_t)count * sizeof(void *));
+    if (data_on_device || view) memcpy(d_in, data, (size_t)count * sizeof(void *));      /* (sub-boxes on the host: the layer's view calls stage their rows themselves) */
     else if (szhip_stage_input_batch(ctx, data, count, n * esz, d_in) != SZHIP_OK) { printf("Error: %s: staging failed: %s\n", who, szhip_last_error(ctx)); goto done; }
     {
-        const int mrc = szhip_minmax_batch(ctx, dt, (const void *const *)d_in, count, 1, n, vmin, vmax, NULL);
-        if (mrc != SZHIP_OK) { printf("Error: szhip_minmax_batch failed (%d): %s\n", mrc, mrc == SZHIP_ERR_ARG ? "a pointer that is not aligned to its element" : szhip_last_error(ctx)); goto done; }
+        const int mrc = view ? szhip_minmax_batch_view(ctx, dt, (const void *const *)d_in, count, data_on_device, r1, r2, r3, pitch0, pitch1, vmin, vmax, NULL)
+                             : szhip_minmax_batch(ctx, dt, (const void *const *)d_in, count, 1, n, vmin, vmax, NULL);
+        if (mrc != SZHIP_OK) { printf("Error: szhip_minmax_batch%s failed (%d): %s\n", view ? "_view" : "", mrc, mrc == SZHIP_ERR_ARG ? "a pointer that is not aligned to its element" : szhip_last_error(ctx)); goto done; }
     }
     rc_all = SZ_SCES;
     /* 3. / 4. per item what compress_fp does with its range: the bound, then the constant stream, the container, or the ordinary path */
@@ -1707,8 +1710,9 @@ int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data,
     }
     if (nb > 0) {
         size_t blob_size = 0;
-        const int rc = szhip_compress_omp_batch(ctx, dt, items, nb, 1, r1, r2, r3, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats);
-        if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp_batch failed (%d): %s\n", rc, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
+        const int rc = view ? szhip_compress_omp_batch_view(ctx, dt, items, nb, data_on_device, r1, r2, r3, pitch0, pitch1, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats)
+                            : szhip_compress_omp_batch(ctx, dt, items, nb, 1, r1, r2, r3, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats);
+        if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp_batch%s failed (%d): %s\n", view ? "_view" : "", rc, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
         for (int k = 0; k < nb && blob; ++k) {
             const int i = idx[k];
             if (items[k].rc != SZHIP_OK || items[k].size == 0) { rc_all = SZ_NSCS; continue; }
@@ -1722,8 +1726,13 @@ int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data,
     /* the ordinary path (a bound that is not positive, a range that is no number): the single call's own code, once the staged arrays are no longer needed */
     for (int k = 0; k < nl; ++k) {
         const int i = later[k];
-        const int status = compress_fp(dataType, confparams_cpr->withRegression, &streams[i], (void *)data[i], 0, 0, r1, r2, r3, &comp_sizes[i], errBoundMode, absErrBound,
-                                       relBoundRatio, 0, io);
+        void *whole = (void *)data[i];
+        if (view) {                                            /* from a packed copy of that one sub-box (szhip_pack_view: a device array of the context) */
+            const int prc = szhip_pack_view(ctx, dt, data[i], data_on_device, r1, r2, r3, pitch0, pitch1, &whole);
+            if (prc != SZHIP_OK) { printf("Error: %s: szhip_pack_view of array %d failed (%d): %s\n", who, i, prc, szhip_last_error(ctx)); rc_all = SZ_NSCS; continue; }
+        }
+        const int status = compress_fp(dataType, confparams_cpr->withRegression, &streams[i], whole, 0, 0, r1, r2, r3, &comp_sizes[i], errBoundMode, absErrBound,
+                                       relBoundRatio, 0, view ? &dev_io : io);
         if (!streams[i]) { printf("Error: %s: array %d failed on the ordinary path (%d).\n", who, i, status); comp_sizes[i] = 0; rc_all = SZ_NSCS; }
     }
     g_last_stats = bstats;
@@ -1732,10 +1741,50 @@ done:
     return rc_all;
 }
 
-int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
-                            size_t r1, size_t r2, size_t r3)
+int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                               size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched)
 {
-    static const char *const who = "SZ_hip_decompress_batch";
+    return compress_args_batch_at("SZ_hip_compress_args_batch", dataType, count, data, data_on_device, errBoundMode, absErrBound, relBoundRatio, r1, r2, r3, r2 * r3, r3,
+                                  streams, comp_sizes, batched);
+}
+
+/* One box [start, end) common to `count` 3-D parents of r1 x r2 x r3 values (r1 slowest): 1 with *first = the offset in values of the box's first value, else 0 with
+ * the reason printed and nothing else done */
+static int batch_region(const char *who, int dataType, int count, const void *const *a, const void *const *b, size_t r1, size_t r2, size_t r3, const size_t start[3],
+                        const size_t end[3], size_t *first)
+{
+    if (count < 1 || !a) { printf("Error: %s: bad arguments.\n", who); return 0; }
+    for (int i = 0; i < count; ++i) {
+        if (!region_of_parent(who, dataType, a[i], 0, 0, r1, r2, r3, start, end)) return 0;
+        if (b && !b[i]) { printf("Error: %s: null argument.\n", who); return 0; }
+    }
+    *first = (start[0] * r2 + start[1]) * r3 + start[2];
+    return 1;
+}
+
+int SZ_hip_compress_args_batch_region(int dataType, int count, const void *const *parents, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                                      size_t r1, size_t r2, size_t r3, const size_t start[3], const size_t end[3], unsigned char **streams, size_t *comp_sizes, int *batched)
+{
+    static const char *const who = "SZ_hip_compress_args_batch_region";
+    size_t first = 0;
+    if (!streams || !comp_sizes) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    for (int i = 0; i < count; ++i) { streams[i] = NULL; comp_sizes[i] = 0; if (batched) batched[i] = 0; }
+    if (!batch_region(who, dataType, count, parents, NULL, r1, r2, r3, start, end, &first)) return SZ_NSCS;
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    const void **base = (const void **)malloc((size_t)count * sizeof(void *));
+    if (!base) return SZ_NSCS;
+    for (int i = 0; i < count; ++i) base[i] = (const char *)parents[i] + first * esz;
+    const int rc = compress_args_batch_at(who, dataType, count, base, data_on_device, errBoundMode, absErrBound, relBoundRatio, end[0] - start[0], end[1] - start[1],
+                                          end[2] - start[2], r2 * r3, r3, streams, comp_sizes, batched);
+    free((void *)base);
+    return rc;
+}
+
+/* (out[i]: the first value of r1 x r2 x r3 values whose planes lie pitch0 and whose rows pitch1 elements apart, as in compress_args_batch_at) */
+static int decompress_batch_at(const char *who, int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
+                               size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1)
+{
+    const int view = pitch1 != r3 || pitch0 != r2 * r3;
     if (count < 1 || !bytes || !byteLengths || !out || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
     szhip_ctx *ctx = get_ctx();
     if (!ctx) return SZ_NSCS;
@@ -1760,7 +1809,8 @@ int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes
     }
     if (nb > 0) {
         fresh_dec_state();
-        const int rc = szhip_decompress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, &bstats);
+        const int rc = view ? szhip_decompress_omp_batch_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, pitch0, pitch1, &bstats)
+                            : szhip_decompress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, &bstats);
         if (rc != SZHIP_OK) {
             rc_all = SZ_NSCS;
             for (int k = 0; k < nb; ++k) if (items[k].rc != SZHIP_OK) printf("Error: %s: stream %d failed (%d).\n", who, idx[k], items[k].rc);
@@ -1775,14 +1825,50 @@ int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes
             size_t _r[5];
             filterDimension(0, 0, r1, r2, r3, _r);
             fresh_dec_state();
-            o = decompress_fp(dataType, bytes[i], byteLengths[i], _r[4], _r[3], _r[2], _r[1], _r[0], 0, out_on_device ? out[i] : NULL);
+            o = decompress_fp(dataType, bytes[i], byteLengths[i], _r[4], _r[3], _r[2], _r[1], _r[0], 0, out_on_device && !view ? out[i] : NULL);
         }
         if (!o) { printf("Error: %s: stream %d failed.\n", who, i); rc_all = SZ_NSCS; continue; }
+        if (view) {                                            /* decoded whole on the host; its rows into the sub-box: copied, or (a device parent) staged and scattered */
+            int ok = 1;
+            if (!out_on_device)
+                for (size_t k = 0; k < r1; k++)
+                    for (size_t j = 0; j < r2; j++) memcpy((char *)out[i] + (k * pitch0 + j * pitch1) * esz, (char *)o + (k * r2 + j) * r3 * esz, r3 * esz);
+            else {
+                void *d = NULL;
+                const int dt = dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64;
+                ok = szhip_stage_input(ctx, o, n * esz, &d) == SZHIP_OK && szhip_scatter_view(ctx, dt, d, r1, r2, r3, out[i], 1, pitch0, pitch1) == SZHIP_OK;
+            }
+            free(o);
+            if (!ok) { printf("Error: %s: stream %d could not be placed: %s\n", who, i, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
+            continue;
+        }
         if (!out_on_device) { memcpy(out[i], o, n * esz); free(o); }
     }
     if (nb > 0) g_last_stats = bstats;
     free(items); free(idx);
     return rc_all;
+}
+
+int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
+                            size_t r1, size_t r2, size_t r3)
+{
+    return decompress_batch_at("SZ_hip_decompress_batch", dataType, count, bytes, byteLengths, out, out_on_device, r1, r2, r3, r2 * r3, r3);
+}
+
+int SZ_hip_decompress_batch_into_region(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *parents, int out_on_device,
+                                        size_t r1, size_t r2, size_t r3, const size_t start[3], const size_t end[3])
+{
+    static const char *const who = "SZ_hip_decompress_batch_into_region";
+    size_t first = 0;
+    if (!bytes || !byteLengths) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    if (!batch_region(who, dataType, count, (const void *const *)parents, NULL, r1, r2, r3, start, end, &first)) return SZ_NSCS;
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    void **base = (void **)malloc((size_t)count * sizeof(void *));
+    if (!base) return SZ_NSCS;
+    for (int i = 0; i < count; ++i) base[i] = (char *)parents[i] + first * esz;
+    const int rc = decompress_batch_at(who, dataType, count, bytes, byteLengths, base, out_on_device, end[0] - start[0], end[1] - start[1], end[2] - start[2], r2 * r3, r3);
+    free(base);
+    return rc;
 }
 
 int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
@@ -1797,6 +1883,26 @@ int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const 
     if (!ctx) return SZ_NSCS;
     const int rc = szhip_compare_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, ori, dec, count, on_device, n, absBound, pwRelBound, (unsigned)flags, out, &g_last_stats);
     if (rc != SZHIP_OK) { printf("Error: szhip_compare_batch failed (%d): %s\n", rc, rc == SZHIP_ERR_ARG ? "a null or misaligned pointer" : szhip_last_error(ctx)); return SZ_NSCS; }
+    return SZ_SCES;
+}
+
+int SZ_hip_compare_batch_region(int dataType, int count, const void *const *ori_parents, const void *const *dec_parents, int on_device, size_t r1, size_t r2, size_t r3,
+                                const size_t start[3], const size_t end[3], const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out)
+{
+    static const char *const who = "SZ_hip_compare_batch_region";
+    size_t first = 0;
+    if (!dec_parents || !absBound || !out) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
+    if (!batch_region(who, dataType, count, ori_parents, dec_parents, r1, r2, r3, start, end, &first)) return SZ_NSCS;
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    const void **base = (const void **)malloc((size_t)count * 2 * sizeof(void *));
+    if (!base) return SZ_NSCS;
+    for (int i = 0; i < count; ++i) { base[i] = (const char *)ori_parents[i] + first * esz; base[count + i] = (const char *)dec_parents[i] + first * esz; }
+    const int rc = szhip_compare_batch_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, base, r2 * r3, r3, base + count, r2 * r3, r3, count, on_device,
+                                            end[0] - start[0], end[1] - start[1], end[2] - start[2], absBound, pwRelBound, (unsigned)flags, out, &g_last_stats);
+    free((void *)base);
+    if (rc != SZHIP_OK) { printf("Error: szhip_compare_batch_view failed (%d): %s\n", rc, rc == SZHIP_ERR_ARG ? "a misaligned pointer" : szhip_last_error(ctx)); return SZ_NSCS; }
     return SZ_SCES;
 }
 

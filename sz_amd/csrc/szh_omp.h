@@ -814,12 +814,11 @@ __global__ __launch_bounds__(256) void k_omp_gather(const unsigned char *__restr
 // array) and goes to dst + (k e1 + i) e2.  A lane takes one 16-byte piece of one row -- consecutive lanes consecutive pieces, `cpr` pieces a
 // row, so a wavefront reads and writes whole lines of a row -- and copies it in one access when both row starts are 16-byte aligned and the
 // piece lies inside the row; else (any address of `dst`, rows that are no multiple of the piece, the last piece of a row) value by value.
+// (piece `idx` of the box, apart from the kernel: k_ompb_crop of szh_ompbatch.h runs it over many boxes)
 template <class T>
-__global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int64_t s0, int64_t s1, T *__restrict__ dst, int e1, int e2, int cpr, int64_t pieces)
+__device__ __forceinline__ void omp_crop_body(const T *__restrict__ src, int64_t s0, int64_t s1, T *__restrict__ dst, int e1, int e2, int cpr, int64_t idx)
 {
     constexpr int VW = 16 / (int)sizeof(T);
-    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (idx >= pieces) return;
     const int64_t row = idx / cpr, k = row / e1;
     const int j0 = (int)(idx - row * cpr) * VW, i = (int)(row - k * e1);
     const T *s = src + k * s0 + (int64_t)i * s1;
@@ -829,6 +828,13 @@ __global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int
     else
         for (int j = j0; j < e2 && j < j0 + VW; ++j) d[j] = s[j];
 }
+template <class T>
+__global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int64_t s0, int64_t s1, T *__restrict__ dst, int e1, int e2, int cpr, int64_t pieces)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    omp_crop_body<T>(src, s0, s1, dst, e1, e2, cpr, idx);
+}
 
 // The inverse of k_omp_crop (szhip_scatter_view): a contiguous array of e0 x e1 x e2 values into a VIEW whose planes lie d0 and whose rows d1 elements apart.
 // Every row is cut at the 16-byte boundaries of its DESTINATION: a head of fewer than 16 bytes up to the first boundary, whole 16-byte pieces -- one
@@ -836,11 +842,9 @@ __global__ __launch_bounds__(256) void k_omp_crop(const T *__restrict__ src, int
 // value by value.  A lane takes one piece of one row, consecutive lanes consecutive pieces (`ppr` pieces a row: the head and (e2 + VW - 1) / VW more).
 // Nothing outside a row's e2 values is written, and no value of the view is read.
 template <class T>
-__global__ __launch_bounds__(256) void k_view_scatter(const T *__restrict__ src, T *__restrict__ dst, int64_t d0, int64_t d1, int e1, int e2, int ppr, int64_t pieces)
+__device__ __forceinline__ void view_scatter_body(const T *__restrict__ src, T *__restrict__ dst, int64_t d0, int64_t d1, int e1, int e2, int ppr, int64_t idx)
 {
     constexpr int VW = 16 / (int)sizeof(T);
-    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
-    if (idx >= pieces) return;
     const int64_t row = idx / ppr, k = row / e1;
     const int p = (int)(idx - row * ppr), i = (int)(row - k * e1);
     const T *s = src + row * e2;
@@ -855,4 +859,11 @@ __global__ __launch_bounds__(256) void k_view_scatter(const T *__restrict__ src,
         *reinterpret_cast<uint4 *>(d + j0) = v;
     } else
         for (int j = j0; j < j1; ++j) d[j] = s[j];
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_view_scatter(const T *__restrict__ src, T *__restrict__ dst, int64_t d0, int64_t d1, int e1, int e2, int ppr, int64_t pieces)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    view_scatter_body<T>(src, dst, d0, d1, e1, e2, ppr, idx);
 }

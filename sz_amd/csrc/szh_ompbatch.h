@@ -6,6 +6,9 @@
 // reads its record once through list[blockIdx.y] (the record is uniform per workgroup: plain loads through a const __restrict__ pointer, scalar on the GPU) and runs
 // the `*_body` function the single call's kernel runs, with the record's values where that kernel has its arguments.  Nothing of a body is repeated here.
 // `list`: the arrays a launch covers (all batched ones; those of one sweep form; those with verbatim values), so that one table serves every launch of the call.
+// The batched VIEW calls run the same kernels with one of two geometries -- the parents' pitches for the items that are addressed where they
+// lie, the contiguous one for the items that were gathered into a copy -- and keep the two kinds in different lists; k_ompb_sample_view, k_ompb_crop and
+// k_ompb_view_scatter (below) are theirs alone.
 #pragma once
 
 struct szh_ompb_rec {
@@ -33,6 +36,15 @@ __global__ __launch_bounds__(256) void k_ompb_sample(szh_geom3 G, const szh_ompb
 {
     const szh_ompb_rec &r = recs[list[blockIdx.y]];
     sample_body<T, false>(G, (const T *)r.data, nrows, sd, r.eb, (T)0, max_radius, r.radius_hist, nullptr, r.totals + 3);
+}
+
+// ... of arrays that are VIEWS with the common element pitches p0 / p1 (szhip_compress_omp_batch_view): k_sample_view's body; r.data is the view's first value
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_sample_view(szh_geom3 G, const szh_ompb_rec *__restrict__ recs, const int *__restrict__ list, int64_t p0, int64_t p1, int64_t nrows, int sd,
+                                                          unsigned max_radius)
+{
+    const szh_ompb_rec &r = recs[list[blockIdx.y]];
+    sample_view_body<T>(threadIdx.x, G, (const T *)r.data, p0, p1, nrows, sd, r.eb, max_radius, r.radius_hist, r.totals + 3);
 }
 
 template <class T> __device__ __forceinline__ void ompb_sweep_args(const szh_omp_geom &g, const szh_ompb_rec &r, bool dec, int fw, szh_oc::sweep_args<T> &a)
@@ -125,4 +137,24 @@ __global__ __launch_bounds__(256) void k_ompb_fetch(unsigned char *__restrict__ 
         for (u64 i = tid; i < n16; i += 256) reinterpret_cast<uint4 *>(d + head)[i] = reinterpret_cast<const uint4 *>(s + head)[i];
         if (tail + tid < n) d[tail + tid] = s[tail + tid];            // (fewer than 16 bytes)
     } else for (u64 i = tid; i < n; i += 256) d[i] = s[i];
+}
+
+// MANY VIEWS of one shape and one pair of element pitches, each at its own base (the batched view calls): blockIdx.y picks the pair {view base, contiguous copy} of
+// `pairs` (two addresses per view), blockIdx.x x 256 + lane the 16-byte piece inside it -- the pieces of k_omp_crop (gather: view -> copy, `per_row` = cpr) and of
+// k_view_scatter (scatter: copy -> view, `per_row` = ppr; rows cut at the 16-byte boundaries of the view, which is never read), whose bodies these run.
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_crop(const u64 *__restrict__ pairs, int64_t p0, int64_t p1, int e1, int e2, int per_row, int64_t pieces)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    const u64 *pr = pairs + 2 * (u64)blockIdx.y;
+    omp_crop_body<T>(reinterpret_cast<const T *>((uintptr_t)pr[0]), p0, p1, reinterpret_cast<T *>((uintptr_t)pr[1]), e1, e2, per_row, idx);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompb_view_scatter(const u64 *__restrict__ pairs, int64_t p0, int64_t p1, int e1, int e2, int per_row, int64_t pieces)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx >= pieces) return;
+    const u64 *pr = pairs + 2 * (u64)blockIdx.y;
+    view_scatter_body<T>(reinterpret_cast<const T *>((uintptr_t)pr[1]), reinterpret_cast<T *>((uintptr_t)pr[0]), p0, p1, e1, e2, per_row, idx);
 }

@@ -235,3 +235,31 @@ __global__ __launch_bounds__(256) void k_quality_final_batch(const unsigned long
 {
     szh_q_final_body(slots + (size_t)blockIdx.y * (size_t)nslots * SZH_Q_WORDS, nslots, out + (size_t)blockIdx.y * SZH_Q_WORDS);
 }
+
+// ... of pairs that are VIEWS (szhip_compare_batch_view): every `ori` a box of the view VO, every `dec` a box of the view VD -- the extents and the two pairs of
+// pitches are common to the batch, the base pointers per pair.  Siblings of the two kernels above, which keep their code; the points meet in the order the point
+// count gives, so a pair's record is bit for bit szhip_compare_view's, which is that of the contiguous copies.
+template <class T>
+__global__ __launch_bounds__(256) void k_quality_pass1_batch_view(const szh_qpair *__restrict__ pairs, szh_qview VO, szh_qview VD, int64_t n, unsigned long long *slots)
+{
+    const szh_qpair P = pairs[blockIdx.y];
+    szh_q_pass1_body<T>((const T *)P.ori, VO, (const T *)P.dec, VD, n, P.abs_bound, P.pw_rel_bound, slots + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SZH_Q_WORDS);
+}
+// (k_quality_pass2's text once more, as k_quality_pass2_batch has it and for its reason)
+template <class T>
+__global__ __launch_bounds__(256) void k_quality_pass2_batch_view(const szh_qpair *__restrict__ pairs, szh_qview VO, szh_qview VD, int64_t n, unsigned long long *slots)
+{
+    const szh_qpair P = pairs[blockIdx.y];
+    const double mean_ori = P.mean_ori, mean_dec = P.mean_dec;
+    double s_od = 0, s_oo = 0, s_dd = 0;
+    szh_q_sweep<T>((const T *)P.ori, VO, (const T *)P.dec, VD, n, [&](T o, T d, unsigned long long) {
+        const T diff = d - o;
+        if (o != o || d != d || diff != diff) return;
+        const double a = (double)o - mean_ori, b = (double)d - mean_dec;
+        s_od += a * b; s_oo += a * a; s_dd += b * b;
+    });
+    unsigned long long a[SZH_Q_WORDS];
+    szh_q_neutral(a);
+    a[SZH_Q_S0] = szh_q_dbits(s_od); a[SZH_Q_S1] = szh_q_dbits(s_oo); a[SZH_Q_S2] = szh_q_dbits(s_dd);
+    szh_q_block_merge(a, slots + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SZH_Q_WORDS);
+}

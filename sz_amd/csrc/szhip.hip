@@ -474,7 +474,20 @@ int szhip_minmax_batch(szhip_ctx *ctx, int dtype, const void *const *data, int c
     if (!vmin || !vmax) return SZHIP_ERR_ARG;
     TRY(batch_pointers(ctx, dtype, data, count, n));
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, n, vmin, vmax, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, 1, 1, n, n, n, vmin, vmax, stats));
+}
+static int check_view(szhip_ctx *ctx, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1);
+int szhip_minmax_batch_view(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
+                            double *vmin, double *vmax, szhip_stats *stats)
+{
+    if (!vmin || !vmax) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    TRY(batch_pointers(ctx, dtype, data, count, 1));
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    if ((double)r0 * (double)r1 * (double)r2 >= 4294967296.0) { snprintf(ctx->err, sizeof(ctx->err), "szhip_minmax_batch_view: sub-boxes of 2^32 values or more"); return SZHIP_ERR_UNSUP; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    if (pitch1 == r2 && pitch0 == r1 * r2) { const size_t n = r0 * r1 * r2; r0 = r1 = 1; r2 = pitch0 = pitch1 = n; }      // (the contiguous call, exactly)
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, r0, r1, r2, pitch0, pitch1, vmin, vmax, stats));
 }
 
 int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -553,26 +566,56 @@ static int batch_args(szhip_ctx *ctx, int dtype, const szhip_batch_item *items, 
     return SZHIP_OK;
 }
 
-int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
-                             const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+// (the contiguous call: pitch0 = r1 * r2, pitch1 = r2)
+static int compress_omp_batch_entry(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
+                                    int thread_num, const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
 {
     if (!params || !blob || !blob_size || thread_num < 1) return SZHIP_ERR_ARG;
     TRY(batch_args(ctx, dtype, items, count, r0, r1, r2, true));
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
     if (out_on_device != 0 && out_on_device != 1) { snprintf(ctx->err, sizeof(ctx->err), "a batch writes into a host blob (0) or the context's device blob (1)"); return SZHIP_ERR_UNSUP; }
+    if (data_on_device && (pitch1 != r2 || pitch0 != r1 * r2) && ctx->in.p)      // device views: the gather's copies go into the context's input buffer
+        for (int i = 0; i < count; ++i)
+            if ((const char *)items[i].data >= (const char *)ctx->in.p && (const char *)items[i].data < (const char *)ctx->in.p + ctx->in.cap) {
+                snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: a device view inside the context's input buffer (szhip_stage_input), which the call itself uses", i);
+                return SZHIP_ERR_ARG;
+            }
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     for (int i = 0; i < count; ++i) { items[i].offset = items[i].size = 0; items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
     *blob = nullptr; *blob_size = 0;
-    return synced_on_failure(ctx,
-               BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, r0, r1, r2, thread_num, params, meta_len, out_on_device, blob, blob_size, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, r0, r1, r2, pitch0, pitch1, thread_num, params, meta_len, out_on_device,
+                                           blob, blob_size, stats));
+}
+static int decompress_omp_batch_entry(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
+                                      int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
+{
+    TRY(batch_args(ctx, dtype, items, count, r0, r1, r2, false));
+    TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) { items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
+    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, r0, r1, r2, out_on_device, pitch0, pitch1, stats));
+}
+
+int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
+                             const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+{
+    return compress_omp_batch_entry(ctx, dtype, items, count, data_on_device, r0, r1, r2, r1 * r2, r2, thread_num, params, meta_len, out_on_device, blob, blob_size, stats);
+}
+int szhip_compress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
+                                  int thread_num, const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+{
+    return compress_omp_batch_entry(ctx, dtype, items, count, data_on_device, r0, r1, r2, pitch0, pitch1, thread_num, params, meta_len, out_on_device, blob, blob_size, stats);
 }
 
 int szhip_decompress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
                                int out_on_device, szhip_stats *stats)
 {
-    TRY(batch_args(ctx, dtype, items, count, r0, r1, r2, false));
-    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    for (int i = 0; i < count; ++i) { items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
-    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, r0, r1, r2, out_on_device, stats));
+    return decompress_omp_batch_entry(ctx, dtype, items, count, stream_on_device, r0, r1, r2, out_on_device, r1 * r2, r2, stats);
+}
+int szhip_decompress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
+                                    int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
+{
+    return decompress_omp_batch_entry(ctx, dtype, items, count, stream_on_device, r0, r1, r2, out_on_device, pitch0, pitch1, stats);
 }
 
 int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,
@@ -693,7 +736,26 @@ int szhip_compare_batch(szhip_ctx *ctx, int dtype, const void *const *ori, const
     TRY(batch_pointers(ctx, dtype, ori, count, n));
     TRY(batch_pointers(ctx, dtype, dec, count, n));
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_batch_impl, ctx, ori, dec, count, on_device, n, abs_bound, pw_rel_bound, flags, out, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_batch_impl, ctx, ori, n, n, dec, n, n, count, on_device, 1, 1, n, abs_bound, pw_rel_bound, flags, out, stats));
+}
+int szhip_compare_batch_view(szhip_ctx *ctx, int dtype, const void *const *ori, size_t o_pitch0, size_t o_pitch1, const void *const *dec, size_t d_pitch0, size_t d_pitch1,
+                             int count, int on_device, size_t r0, size_t r1, size_t r2, const double *abs_bound, const double *pw_rel_bound, unsigned flags,
+                             szhip_quality *out, szhip_stats *stats)
+{
+    if (!abs_bound || !out) return SZHIP_ERR_ARG;
+    if (r0 < 1 || r1 < 1 || r2 < 1 || r0 > 0x7fffffff || r1 > 0x7fffffff || r2 > 0x7fffffff) return SZHIP_ERR_ARG;
+    TRY(batch_pointers(ctx, dtype, ori, count, 1));
+    TRY(batch_pointers(ctx, dtype, dec, count, 1));
+    TRY(check_view(ctx, r0, r1, r2, o_pitch0, o_pitch1));
+    TRY(check_view(ctx, r0, r1, r2, d_pitch0, d_pitch1));
+    if ((double)r0 * (double)r1 * (double)r2 >= 4294967296.0) { snprintf(ctx->err, sizeof(ctx->err), "szhip_compare_batch_view: boxes of 2^32 values or more"); return SZHIP_ERR_UNSUP; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    if (o_pitch1 == r2 && o_pitch0 == r1 * r2 && d_pitch1 == r2 && d_pitch0 == r1 * r2) {      // (the contiguous call, exactly)
+        const size_t n = r0 * r1 * r2;
+        r0 = r1 = 1; r2 = o_pitch0 = o_pitch1 = d_pitch0 = d_pitch1 = n;
+    }
+    return synced_on_failure(ctx, BY_DTYPE(dtype, quality_batch_impl, ctx, ori, o_pitch0, o_pitch1, dec, d_pitch0, d_pitch1, count, on_device, r0, r1, r2, abs_bound, pw_rel_bound, flags,
+                                           out, stats));
 }
 
 int szhip_pwr_prepare(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t n, double vmin, double vmax, double pwr_ratio,

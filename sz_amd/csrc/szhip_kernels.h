@@ -448,6 +448,39 @@ __global__ void k_sample_walk(szh_geom3 G, const T *__restrict__ data, int sd, d
 // the end test are those of a contiguous copy --, `p0` / `p1` the element pitches of the planes and rows of the array it lies in.  Siblings, not a
 // parameter of the kernels above: those keep their code.  A sample whose column lies inside its row (all but the one overflow sample a row may
 // have when the sample distance exceeds the row) reads its neighbours at pitch offsets; the others map every flat position (szh_sample_point_view).
+// (the body apart from the kernel -- `tid`: threadIdx.x, read in the kernel, whose launch bounds give the compiler its range --: k_ompb_sample_view of szh_ompbatch.h runs it with the array as the grid's second dimension)
+template <class T>
+__device__ __forceinline__ void sample_view_body(const unsigned tid, szh_geom3 G, const T *data, int64_t p0, int64_t p1, int64_t nrows, int sd, double ebD,
+                                                 unsigned max_radius, unsigned *radius_hist, u64 *within)
+{
+    __shared__ unsigned sh_r[SZH_LDS_RADIUS_BINS];
+    for (int i = tid; i < SZH_LDS_RADIUS_BINS; i += 256) sh_r[i] = 0;
+    __syncthreads();
+    const int64_t rpp = G.g1.count - 1, r2 = G.g2.count;
+    unsigned w = 0;
+    for (int64_t ridx = (int64_t)blockIdx.x * 256 + tid; ridx < nrows; ridx += (int64_t)gridDim.x * 256) {
+        const int64_t n1 = ridx / rpp + 1, n2 = ridx - (n1 - 1) * rpp + 1;
+        const int64_t c0 = sd - ((n1 + n2) % sd);
+        const int64_t origin = n1 * G.d0 + n2 * r2;
+        for (int64_t m = 0;; ++m) {
+            const int64_t col = c0 + m * sd;
+            if (m > 0 && col >= r2) break;
+            const int64_t pos = origin + col;
+            if (pos >= G.n) break;
+            unsigned ri; int fi, we;
+            if (col < r2) szh_sample_point<T>(data, n1 * p0 + n2 * p1 + col, p1, p0, ebD, (T)0, max_radius, &ri, &fi, &we);
+            else szh_sample_point_view<T>(data, pos, r2, G.d0, p0, p1, ebD, max_radius, &ri, &we);
+            if (ri < SZH_LDS_RADIUS_BINS) atomicAdd(&sh_r[ri], 1u); else atomicAdd(&radius_hist[ri], 1u);
+            w += (unsigned)we;
+        }
+    }
+    w = wave_sum_u32(w);
+    if ((tid & 63) == 0 && w) atomicAdd(within, (u64)w);
+    __syncthreads();
+    for (int i = tid; i < SZH_LDS_RADIUS_BINS; i += 256) if (sh_r[i]) atomicAdd(&radius_hist[i], sh_r[i]);
+}
+// (k_sample_view keeps its own text, to the letter: as a wrapper of sample_view_body it compiled to another register allocation, and the single view call's
+//  optimiser runs it; as k_ompb_col repeats k_omp_col's)
 template <class T>
 __global__ __launch_bounds__(256) void k_sample_view(szh_geom3 G, const T *__restrict__ data, int64_t p0, int64_t p1, int64_t nrows, int sd, double ebD,
                                                      unsigned max_radius, unsigned *radius_hist, u64 *within)

@@ -4,9 +4,10 @@
 // per-array record (szh_ompb_rec) in a device table that is uploaded whole whenever the host has learnt something new about the arrays (the interval counts, the books).
 // An array the shared launches do not cover goes through compress_omp_impl / decompress_omp_impl from inside the call.
 // =====================================================================================================================
-static int omp_form(const szh_omp_geom &g, const void *base, size_t elem, size_t r1, size_t r2)
+// (`g` carries the pitches of the array `base` lies in -- a view's after omp_view_pitches --, pitch0 / pitch1 are the same in elements)
+static int omp_form(const szh_omp_geom &g, const void *base, size_t elem, size_t pitch0, size_t pitch1)
 {
-    if (omp_col_applies(g, base, r2 * elem, r1 * r2 * elem)) return 3;
+    if (omp_col_applies(g, base, pitch1 * elem, pitch0 * elem)) return 3;
     return g.vec && ((uintptr_t)base & 15u) == 0 ? 4 : 5;
 }
 static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
@@ -19,8 +20,9 @@ static int ompb_limits(szhip_ctx *ctx, int count, size_t nb, size_t n)
 }
 // `count` host arrays of `bytes` bytes each, one behind the other at multiples of 16 into `buf` (asynchronous on `st`; the callers' arrays have been read on return):
 // ONE copy through the context's pinned block when they total at most 64 MiB, else array by array.  d[i]: where array i lies then.
+// `hv`: the host arrays are VIEWS of `bytes` bytes each (the batched view calls): their rows alone are copied, packed, as staged_copy does with a host view.
 template <class GET>
-int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_t st, GET &&host, std::vector<const void *> &d)
+int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_t st, GET &&host, std::vector<const void *> &d, const host_view *hv = nullptr)
 {
     const size_t stride = up16(bytes);
     d.resize((size_t)count);
@@ -28,14 +30,19 @@ int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_
     for (int i = 0; i < count; ++i) d[i] = (const char *)buf.p + (size_t)i * stride;
     if ((size_t)count * stride <= ((size_t)64 << 20)) {
         TRY(ensure_pinned3(ctx, (size_t)count * stride));
-        for (int i = 0; i < count; ++i) memcpy((char *)ctx->pinned3 + (size_t)i * stride, host(i), bytes);
+        for (int i = 0; i < count; ++i) {
+            if (hv) host_view_move(*hv, (char *)const_cast<void *>((const void *)host(i)), (char *)ctx->pinned3 + (size_t)i * stride, 0, bytes, true);
+            else memcpy((char *)ctx->pinned3 + (size_t)i * stride, host(i), bytes);
+        }
         HIPCHK(hipMemcpyAsync(buf.p, ctx->pinned3, (size_t)count * stride, hipMemcpyHostToDevice, st));
-    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)buf.p + (size_t)i * stride, host(i), bytes, true));
+    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)buf.p + (size_t)i * stride, host(i), bytes, true, hv));
     return SZHIP_OK;
 }
 
 // the device table of a batch in ctx->batch_rec: [totals: 4 u64 per array][records][LISTS lists of `count` array numbers][what a version of the table adds behind]
-enum { OMPB_L_ALL = 0, OMPB_L_F3, OMPB_L_F4, OMPB_L_F5, OMPB_L_ENT, OMPB_L_PACK, OMPB_LISTS };
+// (F3G / PACKG: the items of a batched view call that run in a contiguous copy -- gathered views --, apart from those that are addressed where they lie, F3 / F4 / F5 /
+//  PACKD: the two take different geometries, so every launch that reads or writes values through the geometry has one list for each.  PACK = PACKD + PACKG.)
+enum { OMPB_L_ALL = 0, OMPB_L_F3, OMPB_L_F4, OMPB_L_F5, OMPB_L_ENT, OMPB_L_PACK, OMPB_L_F3G, OMPB_L_PACKD, OMPB_L_PACKG, OMPB_LISTS };
 struct ompb_table {
     szhip_ctx *ctx; int count;
     std::vector<szh_ompb_rec> rec; std::vector<int> list[OMPB_LISTS];
@@ -65,13 +72,22 @@ struct ompb_table {
     }
 };
 
+// pitch0 / pitch1: the element pitches of the arrays the items' sub-boxes lie in (szhip_compress_omp_batch_view; r1 * r2 and r2: contiguous arrays).  A view on the
+// device takes one of two ways, per item (omp_view_packs, as in the single view call): where it lies, through the pitched geometry `gv`, or GATHERED into a contiguous
+// copy in the context's input buffer by one k_ompb_crop launch for all such items, where it runs the column form through `g`.  Host views are staged packed.
 template <class T>
-int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
+int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, int thread_num,
                             const szhip_params *prm, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
 {
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
     szh_omp_geom g;
     TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+    const bool host_view_in = !data_on_device && (pitch1 != r2 || pitch0 != r1 * r2);
+    const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
+    if (host_view_in) { pitch0 = r1 * r2; pitch1 = r2; }       // (staged packed below: contiguous from there on)
+    const bool view = pitch1 != r2 || pitch0 != r1 * r2;
+    szh_omp_geom gv = g;
+    if (view) omp_view_pitches(&gv, pitch0, pitch1, sizeof(T));
     const size_t n = r0 * r1 * r2, nb = (size_t)g.nb;
     TRY(ompb_limits(ctx, count, nb, n));
     S.n_elements = (uint64_t)count * n; S.n_blocks = (uint64_t)count * nb;
@@ -85,15 +101,19 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
     if (data_on_device) for (int i = 0; i < count; ++i) d_in[i] = (const T *)items[i].data;
     else {
         std::vector<const void *> d;
-        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return items[i].data; }, d));
+        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return items[i].data; }, d, host_view_in ? &hv : nullptr));
         for (int i = 0; i < count; ++i) d_in[i] = (const T *)d[i];
     }
+    // where the shared launches read array i: d_in[i], or (a gathered view, from the gather on) its contiguous copy
+    std::vector<const T *> src(d_in);
+    std::vector<char> gathered((size_t)count, 0);
+    if (view) for (int i = 0; i < count; ++i) gathered[i] = omp_view_packs(g, d_in[i], pitch0, pitch1, sizeof(T)) ? 1 : 0;
     // the single call for array i, from the device copy of it: its stream on the host until the blob is laid out
     std::vector<std::vector<unsigned char>> fb((size_t)count);
     auto single = [&](int i) {
         unsigned char *p = nullptr; size_t len = 0; szhip_stats s1;
         memset(&s1, 0, sizeof(s1));
-        const int rc = compress_omp_impl<T>(ctx, d_in[i], 1, r0, r1, r2, r1 * r2, r2, items[i].eb, thread_num, prm, items[i].meta, meta_len, 0, &p, &len, &s1);
+        const int rc = compress_omp_impl<T>(ctx, d_in[i], 1, r0, r1, r2, pitch0, pitch1, items[i].eb, thread_num, prm, items[i].meta, meta_len, 0, &p, &len, &s1);
         items[i].rc = rc; items[i].batched = 0;
         if (rc == SZHIP_OK) {
             fb[i].assign(p, p + len); free(p);
@@ -106,7 +126,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
     ompb_table tab(ctx, count);
     uint16_t *d_codes = nullptr; unsigned *d_hist = nullptr;
     if (shared) {
-        TRY(tab.reserve(0));
+        TRY(tab.reserve(view ? (size_t)count * 16 : 0));       // (a view call: the gather's pairs of addresses behind the lists)
         TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
         TRY(ensure(ctx, ctx->zcnt, (size_t)count * nb * 4)); TRY(ensure(ctx, ctx->samples, (size_t)count * nb * sizeof(T)));
         TRY(ensure(ctx, ctx->col_zeros64, (size_t)count * nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)count * (nb + 1) * 8));
@@ -118,7 +138,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         for (int i = 0; i < count; ++i) {
             szh_ompb_rec &r = tab.rec[i];
             const T ebT = (T)items[i].eb;
-            r.data = d_in[i]; r.eb = (double)ebT; r.recip = (double)(T)(1 / ebT);
+            r.data = src[i]; r.eb = (double)ebT; r.recip = (double)(T)(1 / ebT);
             r.codes = d_codes + (size_t)i * n;
             r.ucount = (unsigned *)ctx->zcnt.p + (size_t)i * nb; r.ucount64 = (u64 *)ctx->col_zeros64.p + (size_t)i * nb; r.first = (T *)ctx->samples.p + (size_t)i * nb;
             r.box_bytes = (u64 *)ctx->reg_flags.p + (size_t)i * nb; r.box_off = (u64 *)ctx->reg_rank.p + (size_t)i * nb; r.uoff = (u64 *)ctx->col_off.p + (size_t)i * (nb + 1);
@@ -140,7 +160,9 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         TRY(tab.upload(0, {}));
         if (nrows > 0) {
             const int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-            hipLaunchKernelGGL((k_ompb_sample<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), nrows, prm->sample_distance, max_radius);
+            if (view) hipLaunchKernelGGL((k_ompb_sample_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), (int64_t)pitch0, (int64_t)pitch1, nrows,
+                                         prm->sample_distance, max_radius);         // (every view where it lies: the gather comes behind the single calls, which use its buffer)
+            else hipLaunchKernelGGL((k_ompb_sample<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), nrows, prm->sample_distance, max_radius);
             HIPCHK(hipGetLastError());
         }
         const unsigned *h_rh = (const unsigned *)ctx->pinned;
@@ -163,9 +185,9 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         if (state[i] == BATCH && (iv[i] > 1024 || nb * iv[i] * 4 > ((size_t)64 << 20))) state[i] = EARLY;
         if (state[i] == EARLY) { single(i); continue; }
         if (state[i] != BATCH) continue;
-        const int form = omp_form(g, d_in[i], sizeof(T), r1, r2);
+        const int form = gathered[i] ? 3 : omp_form(gv, d_in[i], sizeof(T), pitch0, pitch1);      // (a gathered view: the column form in its contiguous, aligned copy)
         items[i].intervals = iv[i]; items[i].quant_kernel = form; items[i].batched = 1;
-        tab.list[form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
+        tab.list[gathered[i] ? OMPB_L_F3G : form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
         tab.list[OMPB_L_ENT].push_back(i);
         int rshift = 0;
         while ((iv[i] << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)iv[i] << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
@@ -186,19 +208,44 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         TRY(ensure(ctx, ctx->chunk_bits, hb_bytes));
         TRY(tab.clear_totals());
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)count * 1024 * 4, st));
+        // the gathered views: their contiguous copies one behind the other in the context's input buffer (the single calls above are through with it), the pairs
+        // {view, copy} behind the lists of the table
+        const int n3g = (int)tab.list[OMPB_L_F3G].size();
+        std::vector<unsigned char> pairs;
+        if (n3g) {
+            const size_t stride = up16(n * sizeof(T));
+            TRY(ensure(ctx, ctx->in, (size_t)n3g * stride));
+            pairs.resize((size_t)n3g * 16);
+            u64 *pp = (u64 *)pairs.data();
+            for (int k = 0; k < n3g; ++k) {
+                const int i = tab.list[OMPB_L_F3G][k];
+                src[i] = (const T *)((const char *)ctx->in.p + (size_t)k * stride);
+                pp[2 * k] = (u64)(uintptr_t)d_in[i]; pp[2 * k + 1] = (u64)(uintptr_t)src[i];
+            }
+        }
         fill_static();
         for (int i : tab.list[OMPB_L_ENT]) { tab.rec[i].hist_box = (unsigned *)((char *)ctx->chunk_bits.p + o_hb[i]); tab.rec[i].hist = d_hist + (size_t)i * 1024; }
-        TRY(tab.upload(1, {}));
+        TRY(tab.upload(1, pairs));
+        if (n3g) {                                               // ONE gather launch for all of them
+            const int cpr = (int)((r2 + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+            const int64_t total = (int64_t)(r0 * r1) * cpr;
+            hipLaunchKernelGGL((k_ompb_crop<T>), dim3((unsigned)((total + 255) / 256), (unsigned)n3g), dim3(256), 0, st, (const u64 *)(tab.dev() + tab.o_extra), (int64_t)pitch0, (int64_t)pitch1,
+                               (int)r1, (int)r2, cpr, total);
+            HIPCHK(hipGetLastError());
+            ++S.packing;                                         // (counted where it is launched)
+        }
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size();
         const int rows = g.c0 * g.c1;
         const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
-        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3), 0);
-        if (n4) hipLaunchKernelGGL((k_ompb_box<T, false, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F4));
-        if (n5) hipLaunchKernelGGL((k_ompb_box<T, false, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
+        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), 0);
+        if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), 0);
+        if (n4) hipLaunchKernelGGL((k_ompb_box<T, false, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
+        if (n5) hipLaunchKernelGGL((k_ompb_box<T, false, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel_launches += (n3 ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
         S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
         // ---- 4. the boxes' histograms and every array's own: one launch, one read-back
         const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
@@ -242,6 +289,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
             packed[i].resize(iv[i]);
             for (unsigned s2 = 0; s2 < iv[i]; ++s2) packed[i][s2] = ((tab_code[s2] & (tab_len[s2] >= 64 ? ~0ull : (1ull << tab_len[s2]) - 1)) << 8) | tab_len[s2];
             tab.list[OMPB_L_PACK].push_back(i);
+            tab.list[gathered[i] ? OMPB_L_PACKG : OMPB_L_PACKD].push_back(i);      // (the encoder reads the verbatim values through the geometry)
         }
         cb.host_ms += now_ms() - h0;
     }
@@ -290,7 +338,9 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         // ---- 7. / 8. every box its size and place inside its own stream; every stream's tables and payloads
         hipLaunchKernelGGL(k_ompb_layout, dim3(1, (unsigned)n_pack), dim3(1024), 0, st, (int)nb, tab.d_rec(), tab.d_list(OMPB_L_PACK));
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_pack), dim3(256), lds3_max, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACK));
+        const int n_packd = (int)tab.list[OMPB_L_PACKD].size(), n_packg = (int)tab.list[OMPB_L_PACKG].size();
+        if (n_packd) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packd), dim3(256), lds3_max, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD));
+        if (n_packg) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packg), dim3(256), lds3_max, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG));
         HIPCHK(hipGetLastError());
         if (n_spans) {
             hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)n_spans), dim3(256), 0, st, d_blob, (const u64 *)(tab.dev() + tab.o_extra + o_spans));
@@ -356,11 +406,17 @@ struct ompb_stream {
     size_t have = 0;
 };
 
+// pitch0 / pitch1: the element pitches of the arrays the items' sub-boxes lie in (szhip_decompress_omp_batch_view; r1 * r2 and r2: contiguous arrays).  The mirror of the
+// compress call: a device view is written where it lies through the pitched geometry, or (omp_view_packs) decoded contiguous in the context's output buffer and placed
+// by ONE k_ompb_view_scatter launch for all such items -- those whose boxes all decoded.  A host view is decoded contiguous and its rows are copied out.
 template <class T>
-int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2, int out_on_device, szhip_stats *stats)
+int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2, int out_on_device, size_t pitch0, size_t pitch1,
+                              szhip_stats *stats)
 {
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
     const size_t n = r0 * r1 * r2;
+    const bool any_view = pitch1 != r2 || pitch0 != r1 * r2, view = any_view && out_on_device;
+    const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
     enum { BATCH, SINGLE, FAILED };
     std::vector<int> state((size_t)count, BATCH);
     std::vector<ompb_stream<T>> ps((size_t)count);
@@ -501,7 +557,15 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     // ---- the arrays of the shared launches: their places, forms, records
     ompb_table tab(ctx, count);
     const size_t out_stride = up16(n * sizeof(T));
-    if (!out_on_device) TRY(ensure(ctx, ctx->out, (size_t)count * out_stride));
+    szh_omp_geom gv = g;                                        // the geometry of the items that are written where they lie
+    std::vector<char> gathered((size_t)count, 0);
+    bool any_gathered = false;
+    if (view && have_g) {
+        omp_view_pitches(&gv, pitch0, pitch1, sizeof(T));
+        for (int i = 0; i < count; ++i) if (state[i] == BATCH && omp_view_packs(g, items[i].out, pitch0, pitch1, sizeof(T))) { gathered[i] = 1; any_gathered = true; }
+    }
+    if (!out_on_device || any_gathered) TRY(ensure(ctx, ctx->out, (size_t)count * out_stride));
+    const size_t fp0 = view ? pitch0 : r1 * r2, fp1 = view ? pitch1 : r2;      // (what omp_form looks at)
     size_t ex = 0, un_bytes = 0;
     std::vector<size_t> o_ex((size_t)count, 0), o_un((size_t)count, 0);
     int fw = 0;
@@ -523,6 +587,8 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     if (n_ent > 0) {
         const size_t o_spans = ex;
         ex += (size_t)n_ent * 2 * 24;
+        const size_t o_pairs = ex;                              // (the pairs {view, contiguous copy} of the final scatter: uploaded when it is known which items decoded)
+        if (any_gathered) ex += (size_t)count * 16;
         TRY(tab.reserve(ex));
         TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
         TRY(ensure(ctx, ctx->unpred, first_bytes + un_bytes + 16));
@@ -542,18 +608,18 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
             memcpy(hx + o, p.bbytes.data(), nb * 8); r.box_bytes = (u64 *)(dx + o); o += up16(nb * 8);
             memcpy(hx + o, p.boff.data(), nb * 8); r.box_off = (u64 *)(dx + o); o += up16(nb * 8);
             memcpy(hx + o, p.uoff.data(), (nb + 1) * 8); r.uoff = (u64 *)(dx + o);
-            r.out = out_on_device ? items[i].out : (void *)((char *)ctx->out.p + (size_t)i * out_stride);
+            r.out = out_on_device && !gathered[i] ? items[i].out : (void *)((char *)ctx->out.p + (size_t)i * out_stride);
             r.eb = (double)p.eb; r.recip = (double)(T)(1 / p.eb); r.intervals = p.intervals;
             r.codes = (uint16_t *)ctx->codes_nat.p + (size_t)i * n;
             r.first = d_un + (size_t)i * nb * sizeof(T); r.unpred = d_un + o_un[i];
             r.totals = tab.totals(i);
             r.payload = d_streams + p.pos + p.off_pay; r.bytes_before = (unsigned)std::min<size_t>(p.pos + p.off_pay, 0x7fffffffu);
             r.n_nodes = p.D.n_nodes; r.tab_lds = tabs_in_lds && (size_t)p.D.n_nodes * 8 <= 13 * 1024 ? 1 : 0;
-            const int form = omp_form(g, r.out, sizeof(T), r1, r2);
+            const int form = gathered[i] ? 3 : omp_form(gv, r.out, sizeof(T), fp0, fp1);
             items[i].quant_kernel = form;
-            tab.list[form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
+            tab.list[gathered[i] ? OMPB_L_F3G : form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
             if (form == 3 && p.E > 0) {
-                tab.list[OMPB_L_PACK].push_back(i);               // (here: the arrays k_omp_scatter runs for)
+                tab.list[gathered[i] ? OMPB_L_PACKG : OMPB_L_PACKD].push_back(i);      // (here: the arrays k_omp_scatter runs for)
                 if (fw > 0) { r.vflags = (unsigned *)ctx->chunk_bits.p + (size_t)i * nb * fw; any_flags = true; }
             }
             // the first values and the verbatim values to aligned addresses (omp_dec::decode_boxes copies them out of the stream one by one)
@@ -573,16 +639,20 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         HIPCHK(hipEventRecord(ctx->ev[1], st));
         // ---- 6. the verbatim values of the column-form arrays to their places, one sweep launch per form
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size(), ns = (int)tab.list[OMPB_L_PACK].size();
+        const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size(), ns = (int)tab.list[OMPB_L_PACKD].size();
+        const int n3g = (int)tab.list[OMPB_L_F3G].size(), nsg = (int)tab.list[OMPB_L_PACKG].size();
         const int rows = g.c0 * g.c1;
         const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
-        if (ns) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)ns), dim3(256), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACK), fw);
-        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3), fw);
-        if (n4) hipLaunchKernelGGL((k_ompb_box<T, true, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F4));
-        if (n5) hipLaunchKernelGGL((k_ompb_box<T, true, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, g, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
+        if (ns) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)ns), dim3(256), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD), fw);
+        if (nsg) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)nsg), dim3(256), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG), fw);
+        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), fw);
+        if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), fw);
+        if (n4) hipLaunchKernelGGL((k_ompb_box<T, true, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
+        if (n5) hipLaunchKernelGGL((k_ompb_box<T, true, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel_launches += (n3 ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
         S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
         // ---- 7. the arrays' error counts
         TRY(ensure_pinned(ctx, (size_t)count * 32));
@@ -596,14 +666,34 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         if (!out_on_device) {                                 // the decoded arrays to the callers' host arrays: one copy down, then those of the streams that decoded
             std::vector<unsigned char> tmp((size_t)count * out_stride);
             TRY(staged_copy(ctx, tmp.data(), ctx->out.p, tmp.size(), false));
-            for (int i : tab.list[OMPB_L_ENT]) if (state[i] == BATCH) memcpy(items[i].out, tmp.data() + (size_t)i * out_stride, n * sizeof(T));
+            for (int i : tab.list[OMPB_L_ENT]) {
+                if (state[i] != BATCH) continue;
+                if (any_view) host_view_move(hv, (char *)items[i].out, (char *)tmp.data() + (size_t)i * out_stride, 0, n * sizeof(T), false);      // (the sub-box's rows alone)
+                else memcpy(items[i].out, tmp.data() + (size_t)i * out_stride, n * sizeof(T));
+            }
+        }
+        if (n3g) {                                            // the gathered views that decoded: their contiguous copies into the callers' arrays, ONE scatter launch
+            std::vector<u64> pairs;
+            for (int i : tab.list[OMPB_L_F3G]) if (state[i] == BATCH) { pairs.push_back((u64)(uintptr_t)items[i].out); pairs.push_back((u64)(uintptr_t)tab.rec[i].out); }
+            if (!pairs.empty()) {
+                const u64 *d_pairs = (const u64 *)(tab.dev() + tab.o_extra + o_pairs);
+                HIPCHK(hipMemcpyAsync((void *)d_pairs, pairs.data(), pairs.size() * 8, hipMemcpyHostToDevice, st));
+                const int ppr = 1 + (int)((r2 + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+                const int64_t total = (int64_t)(r0 * r1) * ppr;
+                hipLaunchKernelGGL((k_ompb_view_scatter<T>), dim3((unsigned)((total + 255) / 256), (unsigned)(pairs.size() / 2)), dim3(256), 0, st, d_pairs, (int64_t)pitch0, (int64_t)pitch1,
+                                   (int)r1, (int)r2, ppr, total);
+                HIPCHK(hipGetLastError());
+                ++S.packing;                                      // (counted where it is launched)
+                HIPCHK(hipStreamSynchronize(st));                 // (`pairs` is a pageable source; the single calls below use the output buffer)
+            }
         }
     } else HIPCHK(hipStreamSynchronize(st));
     // ---- the streams the shared launches do not cover: the single call
     for (int i = 0; i < count; ++i) {
         if (state[i] != SINGLE) continue;
         szhip_stats s1; memset(&s1, 0, sizeof(s1));
-        const int rc = decompress_omp_impl<T>(ctx, items[i].stream, stream_on_device, items[i].stream_len, items[i].body_off, r0, r1, r2, items[i].out, out_on_device, 0, 0, &s1);
+        const int rc = decompress_omp_impl<T>(ctx, items[i].stream, stream_on_device, items[i].stream_len, items[i].body_off, r0, r1, r2, items[i].out, out_on_device,
+                                               any_view ? pitch0 : 0, any_view ? pitch1 : 0, &s1);
         items[i].rc = rc; items[i].batched = 0;
         if (rc != SZHIP_OK) { hipStreamSynchronize(st); continue; }
         items[i].intervals = s1.intervals; items[i].n_unpred = s1.n_unpred; items[i].quant_kernel = s1.quant_kernel;

@@ -108,20 +108,26 @@ int quality_impl(szhip_ctx *ctx, const void *ori, int ori_on_device, size_t o_pi
 
 // ---- many pairs of one length in one call (szhip_compare_batch): the steps above, each ONE launch with the pair as the grid's second dimension.  ctx->quality holds
 // [count x grid slots][count records][the pairs' table]; the table goes up once, and once more with the means of pass 1 when the correlation is asked for.
+// szhip_compare_batch_view: every `ori` a box of r0 x r1 x r2 values with the element pitches o_pitch0 / o_pitch1, every `dec` one with d_pitch0 / d_pitch1 (the
+// contiguous call comes as 1 x 1 x n with pitches n); the view kernels run when either side is a view on the device, host views are staged packed.
 template <class T>
-int quality_batch_impl(szhip_ctx *ctx, const void *const *ori, const void *const *dec, int count, int on_device, size_t n, const double *abs_bound,
-                       const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats)
+int quality_batch_impl(szhip_ctx *ctx, const void *const *ori, size_t o_pitch0, size_t o_pitch1, const void *const *dec, size_t d_pitch0, size_t d_pitch1, int count, int on_device,
+                       size_t r0, size_t r1, size_t r2, const double *abs_bound, const double *pw_rel_bound, unsigned flags, szhip_quality *out, szhip_stats *stats)
 {
     constexpr int VW = 16 / (int)sizeof(T);
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
-    TRY(batch_value_limits(ctx, "szhip_compare_batch", count, n));
+    const size_t n = r0 * r1 * r2;
+    const bool o_view = o_pitch1 != r2 || o_pitch0 != r1 * r2, d_view = d_pitch1 != r2 || d_pitch0 != r1 * r2, view = (o_view || d_view) && on_device;
+    TRY(batch_value_limits(ctx, o_view || d_view ? "szhip_compare_batch_view" : "szhip_compare_batch", count, n));
     S.n_elements = (uint64_t)count * n;
     std::vector<const void *> d_ori(ori, ori + count), d_dec(dec, dec + count);
     if (!on_device) {                                               // (both through the one pinned block: the first copy has left it before the second fills it)
-        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return ori[i]; }, d_ori));
+        const host_view hvo = {r1, r2 * sizeof(T), o_pitch0 * sizeof(T), o_pitch1 * sizeof(T)}, hvd = {r1, r2 * sizeof(T), d_pitch0 * sizeof(T), d_pitch1 * sizeof(T)};
+        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return ori[i]; }, d_ori, o_view ? &hvo : nullptr));
         HIPCHK(hipStreamSynchronize(st));
-        TRY(batch_stage(ctx, ctx->in2, count, n * sizeof(T), st, [&](int i) { return dec[i]; }, d_dec));
+        TRY(batch_stage(ctx, ctx->in2, count, n * sizeof(T), st, [&](int i) { return dec[i]; }, d_dec, d_view ? &hvd : nullptr));
     }
+    const szh_qview VO = {(int64_t)r1, (int64_t)r2, (int64_t)o_pitch0, (int64_t)o_pitch1, o_view ? 0 : 1}, VD = {(int64_t)r1, (int64_t)r2, (int64_t)d_pitch0, (int64_t)d_pitch1, d_view ? 0 : 1};
     const int grid = szh_quality_grid(n, VW);
     const size_t rec_bytes = (size_t)SZH_Q_WORDS * 8, o_res = (size_t)count * grid * rec_bytes, o_tab = o_res + (size_t)count * rec_bytes;
     TRY(ensure(ctx, ctx->quality, o_tab + (size_t)count * sizeof(szh_qpair)));
@@ -142,7 +148,8 @@ int quality_batch_impl(szhip_ctx *ctx, const void *const *ori, const void *const
     };
     typedef const u64 (&rec_ref)[SZH_Q_WORDS];
     auto rec = [&](int i) -> rec_ref { return *(const u64 (*)[SZH_Q_WORDS])((const u64 *)ctx->pinned + (size_t)i * SZH_Q_WORDS); };
-    hipLaunchKernelGGL((k_quality_pass1_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
+    if (view) hipLaunchKernelGGL((k_quality_pass1_batch_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, VO, VD, (int64_t)n, d_slots);
+    else hipLaunchKernelGGL((k_quality_pass1_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
     HIPCHK(hipGetLastError());
     S.quant_kernel_launches = 1;
     TRY(collect());
@@ -155,7 +162,8 @@ int quality_batch_impl(szhip_ctx *ctx, const void *const *ori, const void *const
             tab2[i].mean_ori = q[i].sum_ori / took_part; tab2[i].mean_dec = q[i].sum_dec / took_part;
         }
         HIPCHK(hipMemcpyAsync(base + o_tab, tab2.data(), (size_t)count * sizeof(szh_qpair), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((k_quality_pass2_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
+        if (view) hipLaunchKernelGGL((k_quality_pass2_batch_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, VO, VD, (int64_t)n, d_slots);
+        else hipLaunchKernelGGL((k_quality_pass2_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, d_tab, (int64_t)n, d_slots);
         HIPCHK(hipGetLastError());
         TRY(collect());
         for (int i = 0; i < count; ++i) quality_from_pass2(rec(i), &q[i]);

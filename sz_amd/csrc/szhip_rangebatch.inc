@@ -9,16 +9,22 @@ static int batch_value_limits(szhip_ctx *ctx, const char *who, int count, size_t
     return SZHIP_OK;
 }
 
+// The arrays are sub-boxes of r0 x r1 x r2 values (n in all) whose planes lie pitch0 and whose rows pitch1 elements apart (szhip_minmax_batch_view); the contiguous
+// call comes as 1 x 1 x n with pitches n.  Sub-boxes on the host are staged packed and scanned as contiguous arrays.
 template <class T>
-int minmax_batch_impl(szhip_ctx *ctx, const void *const *data, int count, int on_dev, size_t n, double *vmin, double *vmax, szhip_stats *stats)
+int minmax_batch_impl(szhip_ctx *ctx, const void *const *data, int count, int on_dev, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, double *vmin, double *vmax,
+                      szhip_stats *stats)
 {
     constexpr int VW = 16 / (int)sizeof(T);
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
-    TRY(batch_value_limits(ctx, "szhip_minmax_batch", count, n));
+    const size_t n = r0 * r1 * r2;
+    const bool any_view = pitch1 != r2 || pitch0 != r1 * r2, view = any_view && on_dev;
+    TRY(batch_value_limits(ctx, any_view ? "szhip_minmax_batch_view" : "szhip_minmax_batch", count, n));
     S.n_elements = (uint64_t)count * n;
     // ---- host arrays one behind the other into the context's input buffer; the table of base pointers, uploaded once
     std::vector<const void *> d_in(data, data + count);
-    if (!on_dev) TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return data[i]; }, d_in));
+    const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
+    if (!on_dev) TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return data[i]; }, d_in, any_view ? &hv : nullptr));
     const size_t o_res = up64((size_t)count * sizeof(void *));
     TRY(ensure(ctx, ctx->batch_rec, o_res + (size_t)count * 16));
     TRY(ensure_pinned(ctx, (size_t)count * 16));
@@ -26,8 +32,17 @@ int minmax_batch_impl(szhip_ctx *ctx, const void *const *data, int count, int on
     HIPCHK(hipMemcpyAsync(tab, d_in.data(), (size_t)count * sizeof(void *), hipMemcpyHostToDevice, st));      // (`d_in` lives until the synchronisation below)
     HIPCHK(hipMemsetAsync(tab + o_res, 0, (size_t)count * 16, st));
     // ---- one launch, one read-back
-    const int grid = szh_rangebatch_grid(n, VW);
-    hipLaunchKernelGGL((k_minmax_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, (const T *const *)tab, (int64_t)n, (u64 *)(tab + o_res));
+    if (view) {                                                    // a group of lanes per row, sized to the row's 16-byte pieces
+        int gs = 2 * VW;
+        while (gs < 256 && (size_t)gs * VW < r2) gs *= 2;
+        const size_t rows = r0 * r1, per_wg = 256 / (size_t)gs;
+        const int grid = (int)std::min<size_t>((rows + per_wg - 1) / per_wg, (size_t)SZH_RB_MAX_GRID);
+        hipLaunchKernelGGL((k_minmax_batch_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, (const T *const *)tab, (int64_t)pitch0, (int64_t)pitch1, (int64_t)rows,
+                           (int)r1, (int)r2, gs, (u64 *)(tab + o_res));
+    } else {
+        const int grid = szh_rangebatch_grid(n, VW);
+        hipLaunchKernelGGL((k_minmax_batch<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, (const T *const *)tab, (int64_t)n, (u64 *)(tab + o_res));
+    }
     HIPCHK(hipGetLastError());
     S.quant_kernel_launches = 1;
     HIPCHK(hipMemcpyAsync(ctx->pinned, tab + o_res, (size_t)count * 16, hipMemcpyDeviceToHost, st));
