@@ -312,11 +312,23 @@ void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int i
  * SZ_hip_compare_batch: szhip_compare_batch (szhip.h) on `count` pairs of r1 x r2 x r3 values, pair i against absBound[i] and pwRelBound[i] (pwRelBound NULL: not
  * asked): out[i] is byte for byte SZ_hip_compare's record for pair i.
  * SZ_hip_last_stats after each call: the stats of its shared launches (quant_kernel_launches: the sweep launches, one per form; the pass-1 launches of the report).
- * Not covered: batches of mixed shape, the lossless stage, point-wise relative modes, the slab container; sub-boxes: the three *_region calls below. */
+ * ARRAYS OF DIFFERENT SHAPES: SZ_hip_compress_args_batch_shapes / SZ_hip_decompress_batch_shapes are the two calls above with the extents per
+ * item, dims[3 i], dims[3 i + 1], dims[3 i + 2] = r1, r2, r3 of array i (r1 slowest).  The contracts hold item by item: streams[i] is byte for byte what
+ * SZ_compress_args returns under SZ_HIP_MODE=omp for array i alone -- its box count from the rule that mode applies to ITS shape (sz_set_num_threads /
+ * SZ_HIP_OMP_THREADS, else picked from the shape), its range from ONE szhip_minmax_batch_lens, its bound from SZ_compress_args' rule --, through one
+ * szhip_compress_omp_batch_shapes; the decode puts every marked container, whatever its box count, through one szhip_decompress_omp_batch_shapes.  An item of at most
+ * 20 values, with an extent below 2 or without a box grid takes SZ_compress_args' ordinary path from inside the call (batched[i] = 0) instead of refusing it; the
+ * refusals of the whole call are otherwise those above, and an extent of 0 or an array of 2^32 values or more.
+ * Not covered: the lossless stage, point-wise relative modes, the slab container, arrays of different shapes that are sub-boxes, of different types or not 3-D, the
+ * error report over pairs of different lengths (SZ_hip_compare_batch is element-wise: group the pairs by shape); sub-boxes of one shape: the three *_region calls below. */
 int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
                                size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched);
 int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
                             size_t r1, size_t r2, size_t r3);
+int SZ_hip_compress_args_batch_shapes(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                                      const size_t *dims, unsigned char **streams, size_t *comp_sizes, int *batched);
+int SZ_hip_decompress_batch_shapes(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
+                                   const size_t *dims);
 int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
                          const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out);
 /* ---- the three calls above on ONE BOX [start, end) common to `count` 3-D parents of r1 x r2 x r3 values (r1 slowest; start / end as in SZ_hip_compress_region): the

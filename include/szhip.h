@@ -97,6 +97,8 @@ int szhip_stage_input(szhip_ctx *ctx, const void *host_data, size_t bytes, void 
 /* ... and `count` host arrays of `bytes` bytes each, one behind the other at multiples of 16 (one copy when they total at most 64 MiB): device_ptrs[i] then serves
  * as array i with data_on_device = 1 for szhip_minmax_batch and szhip_compress_omp_batch, so that a host array crosses the bus once for both */
 int szhip_stage_input_batch(szhip_ctx *ctx, const void *const *host_data, int count, size_t bytes, const void **device_ptrs);
+/* ... of different lengths, array i of bytes[i] bytes (for szhip_minmax_batch_lens and szhip_compress_omp_batch_shapes) */
+int szhip_stage_input_batch_lens(szhip_ctx *ctx, const void *const *host_data, int count, const size_t *bytes, const void **device_ptrs);
 
 /*
  * Device pointers and ordering (all calls below): a call runs on the context's own NON-BLOCKING streams and returns when its results are complete.
@@ -336,6 +338,41 @@ int szhip_compress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *i
                                   unsigned char **blob, size_t *blob_size, szhip_stats *stats);
 int szhip_decompress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
                                     int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats);
+/*
+ * ARRAYS OF DIFFERENT SHAPES in one call: the patches of an AMR level, inner and edge chunks of a dataset, the tensors of a checkpoint.  The
+ * batch calls above with the shape AND thread_num per item: item i is a contiguous array of shapes[i].r0 x r1 x r2 values (dim 0 slowest) cut into
+ * shapes[i].thread_num boxes.  dtype, params, meta_len and the pointer kinds stay common.  The bar is the same-shape call's, per item:
+ *   - blob[offset_i, offset_i + size_i) is byte for byte what szhip_compress_omp returns for array i alone with shapes[i], items[i].eb, items[i].meta and params;
+ *     offsets are multiples of 64 and increase with i; out_on_device = 2 stays SZHIP_ERR_UNSUP;
+ *   - the batched decode writes into items[i].out bit for bit what szhip_decompress_omp writes for stream i, and nothing else; inputs are never written.  The box
+ *     count is read from each stream (shapes[i].thread_num is ignored); a stream is batched when the grid of ITS thread_num divides ITS shape -- the same-shape
+ *     call's "thread_num of the batch's first stream" rule does not exist here --, anything else goes to the single call, which says what is wrong with it.
+ * Launches, synchronisations and copies do not grow with `count`, only with the number of KINDS of item: every item's geometry (box grid, sampler lattice and row
+ * limit, boxes per histogram workgroup, flag words) is computed on the host and reaches the kernels through a second per-item record; the first dimension of every
+ * launch is sized to its largest item and the surplus workgroups of the smaller ones return at once.  The column form (3) takes every item with 32 x 32 box faces in
+ * ONE launch, whatever its plane count and box count; the box forms (4, 5) take one launch per distinct box c0 x c1 x c2, because the block is the box's face and
+ * the LDS its ring.  stats->quant_kernel_launches is therefore at most the number of distinct (form, c0 x c1 x c2) among the batched items, and is the same when
+ * every item is given twice.  One sampling launch, one histogram read-back, `count` host books between two synchronisations, one encode phase, as above.  A kind with
+ * a single member still runs in the shared launches.
+ * Work arrays (codes, per-box counts, first values, sizes, offsets, ranks, histograms, verbatim values, flag words, the decoder's staging) lie one item behind the
+ * other at each item's own length, each at the alignment the single call gives it.  Host arrays are staged one behind the other at their own lengths.
+ * Fallbacks are PER ITEM (items[i].batched = 0; the rest stays batched): boxes of a number of points that is no multiple of 8, an extent of 1 in dim 0 or dim 1, and
+ * those of the same-shape call (more than 1024 intervals, a code word above 32 bits; decode: a one-symbol book, a stream beyond the look-up-table decoder's LDS).
+ * Errors: per-item rc as above.  An item whose shape the single call refuses (no dividing grid, a box face above 1024 rows) gets that rc and an empty stream; the rest
+ * proceed.  SZHIP_ERR_ARG before anything is launched or written: count < 1, null `shapes`, an extent of 0 or above 2^31 - 1, thread_num < 1 (compress), and the
+ * same-shape call's refusals.  SZHIP_ERR_UNSUP beyond: count <= 65535, boxes of all items <= 2^22, values of all items < 2^32.
+ * Not covered: views (per-item pitches), mixed dtypes, items that are not 3-D, szhip_compare_batch on pairs of different lengths (it is element-wise: group by length).
+ */
+typedef struct szhip_batch_shape { size_t r0, r1, r2; int thread_num; } szhip_batch_shape;
+int szhip_compress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, int count, int data_on_device,
+                                    const szhip_params *params, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats);
+int szhip_decompress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, int count, int stream_on_device,
+                                      int out_on_device, szhip_stats *stats);
+/* szhip_minmax_batch with a length per array (lens[i] >= 1 values): bit for bit szhip_minmax of each array (ordered-integer reduction, a NaN takes no part), ONE launch
+ * whose grid is sized to the longest array (the surplus workgroups of a shorter one return), one read-back.  An element-aligned base at any offset from a 16-byte
+ * boundary is accepted.  Limits: count <= 65535, fewer than 2^32 values in all. */
+int szhip_minmax_batch_lens(szhip_ctx *ctx, int dtype, const void *const *data, const size_t *lens, int count, int data_on_device, double *vmin, double *vmax,
+                            szhip_stats *stats);
 
 /*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of

@@ -62,6 +62,10 @@ class szhip_batch_item(ctypes.Structure):  # include/szhip.h: one array of szhip
                 ("quant_kernel", ctypes.c_int), ("batched", ctypes.c_int)]
 
 
+class szhip_batch_shape(ctypes.Structure):  # include/szhip.h: the shape (dim 0 slowest) and box count of one array of the *_batch_shapes calls
+    _fields_ = [("r0", ctypes.c_size_t), ("r1", ctypes.c_size_t), ("r2", ctypes.c_size_t), ("thread_num", ctypes.c_int)]
+
+
 class szhip_book_record(ctypes.Structure):  # include/szhip.h
     _fields_ = [("n_nodes", ctypes.c_uint32), ("tree_bytes", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("status", ctypes.c_uint32),
                 ("total_bits", ctypes.c_uint64), ("total_unpred", ctypes.c_uint64)]
@@ -192,6 +196,23 @@ def _bind(L):
         L.szhip_decompress_omp_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.c_int, ctypes.c_int, sz, sz, sz, ctypes.c_int,
                                                  ctypes.POINTER(szhip_stats)]
         L.szhip_decompress_omp_batch.restype = ctypes.c_int
+    if hasattr(L, "szhip_compress_omp_batch_shapes"):
+        L.szhip_compress_omp_batch_shapes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.POINTER(szhip_batch_shape), ctypes.c_int, ctypes.c_int,
+                                                      ctypes.POINTER(szhip_params), sz, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(szhip_stats)]
+        L.szhip_compress_omp_batch_shapes.restype = ctypes.c_int
+        L.szhip_decompress_omp_batch_shapes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.POINTER(szhip_batch_shape), ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_batch_shapes.restype = ctypes.c_int
+        L.szhip_minmax_batch_lens.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(szhip_stats)]
+        L.szhip_minmax_batch_lens.restype = ctypes.c_int
+    if hasattr(L, "SZ_hip_compress_args_batch_shapes"):
+        L.SZ_hip_compress_args_batch_shapes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                        ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]
+        L.SZ_hip_compress_args_batch_shapes.restype = ctypes.c_int
+        L.SZ_hip_decompress_batch_shapes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                                     ctypes.POINTER(sz)]
+        L.SZ_hip_decompress_batch_shapes.restype = ctypes.c_int
     if hasattr(L, "SZ_hip_compress_openmp_batch"):
         L.SZ_hip_compress_openmp_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double), sz, sz, sz,
                                                    ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]
@@ -540,6 +561,38 @@ def SZ_hip_decompress_batch(streams, out_ptrs, out_on_device, shape, dtype, rais
     return rc
 
 
+def SZ_hip_compress_args_batch_shapes(ptrs, on_device, shapes, dtype, errBoundMode, absErrBound=0.0, relBoundRatio=0.0, raise_on_error=True):
+    """include/sz.h: SZ_hip_compress_args_batch over arrays of DIFFERENT 3-D shapes, shapes[i] = (r1, r2, r3) of array i, r1 slowest.  Returns (rc, streams, batched)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(ptrs)
+    c_ptrs = (ctypes.c_void_p * max(count, 1))(*ptrs)
+    c_dims = (ctypes.c_size_t * max(3 * count, 3))(*[int(v) for s in shapes for v in s])
+    streams, sizes, batched = (ctypes.c_void_p * max(count, 1))(), (ctypes.c_size_t * max(count, 1))(), (ctypes.c_int * max(count, 1))()
+    rc = lib().SZ_hip_compress_args_batch_shapes(dt, count, c_ptrs, 1 if on_device else 0, errBoundMode, absErrBound, relBoundRatio, c_dims, streams, sizes, batched)
+    out = [ctypes.string_at(streams[i], sizes[i]) if streams[i] else None for i in range(count)]
+    for i in range(count):
+        if streams[i]:
+            lib().free(streams[i])
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_compress_args_batch_shapes failed ({rc})")
+    return rc, out, [batched[i] for i in range(count)]
+
+
+def SZ_hip_decompress_batch_shapes(streams, out_ptrs, out_on_device, shapes, dtype, raise_on_error=True):
+    """include/sz.h: SZ_hip_decompress_batch with the extents per item, shapes[i] = (r1, r2, r3).  Returns rc: SZ_NSCS when any item failed (the others are decoded)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(streams)
+    keep = [ctypes.create_string_buffer(bytes(s), len(s)) for s in streams]
+    c_streams = (ctypes.c_void_p * max(count, 1))(*[ctypes.addressof(k) for k in keep])
+    c_sizes = (ctypes.c_size_t * max(count, 1))(*[len(s) for s in streams])
+    c_out = (ctypes.c_void_p * max(count, 1))(*out_ptrs)
+    c_dims = (ctypes.c_size_t * max(3 * count, 3))(*[int(v) for s in shapes for v in s])
+    rc = lib().SZ_hip_decompress_batch_shapes(dt, count, c_streams, c_sizes, c_out, 1 if out_on_device else 0, c_dims)
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_decompress_batch_shapes failed ({rc})")
+    return rc
+
+
 def SZ_hip_compare_batch(ori_ptrs, dec_ptrs, on_device, shape, dtype, absBounds, pwRelBounds=None, corr=False):
     """include/sz.h: `len(ori_ptrs)` pairs of arrays of `shape` / `dtype` (host, or device with on_device), pair i against absBounds[i] (and pwRelBounds[i]): a list
     of Quality, record i byte for byte SZ_hip_compare's for pair i."""
@@ -877,6 +930,42 @@ class HipContext:
             self._err(rc, "szhip_decompress_omp_batch")
         return rc, items, st
 
+    def compress_omp_batch_shapes(self, ptrs, on_device, shapes, dtype, bounds, metas, params=None, out_on_device=False, raise_on_error=True):
+        """szhip_compress_omp_batch_shapes: compress_omp_batch on arrays of DIFFERENT shapes, shapes[i] = (r0, r1, r2, thread_num) of array i (None: a null table).
+        Returns (rc, blob, blob_size, items, stats) as compress_omp_batch; stats.quant_kernel_launches grows with the kinds of item, not with their number."""
+        count = len(ptrs)
+        items = (szhip_batch_item * max(count, 1))()
+        keep = [ctypes.create_string_buffer(bytes(m), len(m)) for m in metas]
+        for i in range(count):
+            items[i].data, items[i].eb, items[i].meta = ptrs[i], bounds[i], ctypes.addressof(keep[i]) if metas[i] is not None else None
+        c_shapes = (szhip_batch_shape * max(count, 1))(*[szhip_batch_shape(*s) for s in shapes]) if shapes is not None else None
+        p = params or szhip_params(100, 0.99, 65536, 0)
+        out, n, st = ctypes.c_void_p(), ctypes.c_size_t(0), szhip_stats()
+        rc = lib().szhip_compress_omp_batch_shapes(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, c_shapes, count, int(on_device), ctypes.byref(p),
+                                                   len(metas[0]) if count else 0, int(out_on_device), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_compress_omp_batch_shapes")
+        if out_on_device or not out.value:
+            return rc, out.value, n.value, items, st
+        b = ctypes.string_at(out.value, n.value)
+        lib().free(out)
+        return rc, b, n.value, items, st
+
+    def decompress_omp_batch_shapes(self, streams, stream_on_device, body_off, shapes, dtype, out_ptrs, out_on_device, raise_on_error=True):
+        """szhip_decompress_omp_batch_shapes: streams[i] = (address, length) into the array of shapes[i] = (r0, r1, r2[, anything]) at out_ptrs[i]; the box count is read
+        from each stream.  Returns (rc, items, stats); an item whose rc is non-zero failed alone."""
+        count = len(streams)
+        items = (szhip_batch_item * max(count, 1))()
+        for i in range(count):
+            items[i].stream, items[i].stream_len, items[i].body_off, items[i].out = streams[i][0], streams[i][1], body_off, out_ptrs[i]
+        c_shapes = (szhip_batch_shape * max(count, 1))(*[szhip_batch_shape(s[0], s[1], s[2], 0) for s in shapes]) if shapes is not None else None
+        st = szhip_stats()
+        rc = lib().szhip_decompress_omp_batch_shapes(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, c_shapes, count, int(stream_on_device), int(out_on_device),
+                                                     ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_decompress_omp_batch_shapes")
+        return rc, items, st
+
     def compress_omp_batch_view(self, ptrs, on_device, shape3, pitches, dtype, bounds, thread_num, metas, params=None, out_on_device=False, raise_on_error=True):
         """szhip_compress_omp_batch_view: compress_omp_batch on len(ptrs) sub-boxes of shape3 values, ptrs[i] the first value of sub-box i inside its parent array,
         pitches = (pitch0, pitch1) in elements, common to all (patches with ghost layers).  Stream i is byte for byte that of a contiguous copy of sub-box i.
@@ -1014,6 +1103,17 @@ class HipContext:
         rc = lib().szhip_minmax_batch(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ptrs, count, int(on_device), n, lo, hi, ctypes.byref(st))
         if rc and raise_on_error:
             self._err(rc, "szhip_minmax_batch")
+        return rc, [(lo[i], hi[i]) for i in range(count)], st
+
+    def minmax_batch_lens(self, ptrs, on_device, lens, dtype, raise_on_error=True):
+        """szhip_minmax_batch_lens: minmax_batch with a length per array, lens[i] values at ptrs[i].  Returns (rc, [(vmin, vmax), ...], stats)."""
+        count = len(ptrs)
+        c_ptrs = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        c_lens = (ctypes.c_size_t * max(count, 1))(*lens)
+        lo, hi, st = (ctypes.c_double * max(count, 1))(), (ctypes.c_double * max(count, 1))(), szhip_stats()
+        rc = lib().szhip_minmax_batch_lens(self._h, 0 if np.dtype(dtype) == np.float32 else 1, c_ptrs, c_lens, count, int(on_device), lo, hi, ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_minmax_batch_lens")
         return rc, [(lo[i], hi[i]) for i in range(count)], st
 
     def compare_batch(self, ori_ptrs, dec_ptrs, on_device, n, dtype, abs_bounds, pw_rel_bounds=None, corr=False, raise_on_error=True):

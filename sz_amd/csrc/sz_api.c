@@ -1645,11 +1645,15 @@ int SZ_hip_compare_device(int dataType, const void *d_ori, const void *d_dec, si
 }
 /* ---- SZ_compress_args over many same-shape 3-D arrays in one call, the inverse, and the error report over the round trip (sz.h) */
 /* (the arrays are r1 x r2 x r3 values whose planes lie pitch0 and whose rows pitch1 elements apart, data[i] the first value of array i: r2 * r3 and r3 for
- * SZ_hip_compress_args_batch, the parents' for SZ_hip_compress_args_batch_region, which has checked its box) */
+ * SZ_hip_compress_args_batch, the parents' for SZ_hip_compress_args_batch_region, which has checked its box)
+ * `dims` (or NULL): contiguous arrays of DIFFERENT shapes, array i of dims[3 i] x dims[3 i + 1] x dims[3 i + 2] values (SZ_hip_compress_args_batch_shapes; r1 .. pitch1
+ * come as 0).  Every item then takes the box count of its own shape, and an item the container does not take -- at most 20 values, an extent below 2, no grid -- goes
+ * down SZ_compress_args' ordinary path from inside the call instead of refusing it. */
 static int compress_args_batch_at(const char *who, int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound,
-                                  double relBoundRatio, size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1, unsigned char **streams, size_t *comp_sizes, int *batched)
+                                  double relBoundRatio, size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1, const size_t *dims, unsigned char **streams,
+                                  size_t *comp_sizes, int *batched)
 {
-    const int view = pitch1 != r3 || pitch0 != r2 * r3;
+    const int view = pitch1 != r3 || pitch0 != r2 * r3, mixed = dims != NULL;
     if (count < 1 || !data || !streams || !comp_sizes || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
     for (int i = 0; i < count; ++i) { streams[i] = NULL; comp_sizes[i] = 0; if (batched) batched[i] = 0; }
     for (int i = 0; i < count; ++i) if (!data[i]) { printf("Error: %s: array %d is a null pointer.\n", who, i); return SZ_NSCS; }
@@ -1662,9 +1666,15 @@ static int compress_args_batch_at(const char *who, int dataType, int count, cons
     if (confparams_cpr->szMode != SZ_BEST_SPEED) { printf("Error: %s writes bare SZ streams: szMode must be SZ_BEST_SPEED (the lossless stage is host code).\n", who); return SZ_NSCS; }
     if (confparams_cpr->randomAccess) { printf("Error: %s: the random-access form is not covered.\n", who); return SZ_NSCS; }
     const size_t n = r1 * r2 * r3, esz = dataType == SZ_FLOAT ? 4 : 8;
-    const int threads = r1 >= 2 && r2 >= 2 && r3 >= 2 && n > MIN_NUM_OF_ELEMENTS ? omp_pick_threads(r1, r2, r3) : 0;
+    if (mixed) for (int i = 0; i < count; ++i) {
+        const size_t *e = dims + 3 * (size_t)i;
+        if (e[0] < 1 || e[1] < 1 || e[2] < 1 || e[0] > 0x7fffffff || e[1] > 0x7fffffff || e[2] > 0x7fffffff || (double)e[0] * (double)e[1] * (double)e[2] >= 4294967296.0) {
+            printf("Error: %s: array %d: extents %zu x %zu x %zu.\n", who, i, e[0], e[1], e[2]); return SZ_NSCS;
+        }
+    }
+    const int threads = mixed ? 0 : r1 >= 2 && r2 >= 2 && r3 >= 2 && n > MIN_NUM_OF_ELEMENTS ? omp_pick_threads(r1, r2, r3) : 0;
     g_omp_last_threads = threads;
-    if (threads <= 0) { printf("Error: %s: no power-of-two box grid divides %zu x %zu x %zu into boxes the MI355X build takes; set SZ_HIP_OMP_THREADS.\n", who, r1, r2, r3); return SZ_NSCS; }
+    if (!mixed && threads <= 0) { printf("Error: %s: no power-of-two box grid divides %zu x %zu x %zu into boxes the MI355X build takes; set SZ_HIP_OMP_THREADS.\n", who, r1, r2, r3); return SZ_NSCS; }
     szhip_ctx *ctx = get_ctx();
     if (!ctx) return SZ_NSCS;
     const int dt = dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64;
@@ -1674,16 +1684,21 @@ static int compress_args_batch_at(const char *who, int dataType, int count, cons
     szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
     unsigned char *metas = (unsigned char *)malloc((size_t)count * ML);
     int *idx = (int *)malloc((size_t)count * 2 * sizeof(int)), *later = idx ? idx + count : NULL;
+    size_t *lens = (size_t *)malloc((size_t)count * 2 * sizeof(size_t)), *nbytes = lens ? lens + count : NULL;      /* (values and bytes of every array) */
+    szhip_batch_shape *shp = mixed ? (szhip_batch_shape *)calloc((size_t)count, sizeof(szhip_batch_shape)) : NULL;      /* (the batched items' shapes and box counts) */
     unsigned char *blob = NULL;
     int rc_all = SZ_NSCS, nb = 0, nl = 0;
     szhip_stats bstats; memset(&bstats, 0, sizeof(bstats));
     szhip_params hp; memset(&hp, 0, sizeof(hp));
-    if (!d_in || !vmin || !items || !metas || !idx) { printf("Error: %s: out of memory.\n", who); goto done; }
+    if (!d_in || !vmin || !items || !metas || !idx || !lens || (mixed && !shp)) { printf("Error: %s: out of memory.\n", who); goto done; }
+    for (int i = 0; i < count; ++i) { lens[i] = mixed ? dims[3 * (size_t)i] * dims[3 * (size_t)i + 1] * dims[3 * (size_t)i + 2] : n; nbytes[i] = lens[i] * esz; }
     /* 1. host arrays cross the bus once; 2. every array's range in one launch */
     if (data_on_device || view) memcpy(d_in, data, (size_t)count * sizeof(void *));      /* (sub-boxes on the host: the layer's view calls stage their rows themselves) */
-    else if (szhip_stage_input_batch(ctx, data, count, n * esz, d_in) != SZHIP_OK) { printf("Error: %s: staging failed: %s\n", who, szhip_last_error(ctx)); goto done; }
+    else if ((mixed ? szhip_stage_input_batch_lens(ctx, data, count, nbytes, d_in) : szhip_stage_input_batch(ctx, data, count, n * esz, d_in)) != SZHIP_OK) {
+        printf("Error: %s: staging failed: %s\n", who, szhip_last_error(ctx)); goto done;
+    }
     {
-        const int mrc = view ? szhip_minmax_batch_view(ctx, dt, (const void *const *)d_in, count, data_on_device, r1, r2, r3, pitch0, pitch1, vmin, vmax, NULL)
+        const int mrc = mixed ? szhip_minmax_batch_lens(ctx, dt, (const void *const *)d_in, lens, count, 1, vmin, vmax, NULL) : view ? szhip_minmax_batch_view(ctx, dt, (const void *const *)d_in, count, data_on_device, r1, r2, r3, pitch0, pitch1, vmin, vmax, NULL)
                              : szhip_minmax_batch(ctx, dt, (const void *const *)d_in, count, 1, n, vmin, vmax, NULL);
         if (mrc != SZHIP_OK) { printf("Error: szhip_minmax_batch%s failed (%d): %s\n", view ? "_view" : "", mrc, mrc == SZHIP_ERR_ARG ? "a pointer that is not aligned to its element" : szhip_last_error(ctx)); goto done; }
     }
@@ -1693,12 +1708,15 @@ static int compress_args_batch_at(const char *who, int dataType, int count, cons
     const cpr_io *io = data_on_device ? &dev_io : &g_host_io;
     for (int i = 0; i < count; ++i) {
         double range = 0, bound = 0;
+        const size_t *e = mixed ? dims + 3 * (size_t)i : NULL;
+        const int thr = !mixed ? threads : e[0] >= 2 && e[1] >= 2 && e[2] >= 2 && lens[i] > MIN_NUM_OF_ELEMENTS ? omp_pick_threads(e[0], e[1], e[2]) : 0;
+        if (thr <= 0) { later[nl++] = i; continue; }           /* (different shapes only: an item the container does not take) */
         confparams_cpr->dataType = dataType; confparams_cpr->errorBoundMode = errBoundMode;
         set_range(dataType, vmin[i], vmax[i], &range);
-        const int status = bound_from_mode(dataType, errBoundMode, absErrBound, relBoundRatio, range, n, &bound);
+        const int status = bound_from_mode(dataType, errBoundMode, absErrBound, relBoundRatio, range, lens[i], &bound);
         if (range <= bound) {
             szhost_meta m; fill_meta(&m, confparams_cpr, dataType);
-            if (constant_out(dataType, &m, data[i], n, io, &streams[i], &comp_sizes[i], status) != SZ_SCES || !streams[i]) { printf("Error: %s: array %d (constant) failed.\n", who, i); rc_all = SZ_NSCS; }
+            if (constant_out(dataType, &m, data[i], lens[i], io, &streams[i], &comp_sizes[i], status) != SZ_SCES || !streams[i]) { printf("Error: %s: array %d (constant) failed.\n", who, i); rc_all = SZ_NSCS; }
             continue;
         }
         if (!(bound > 0) || !(range > bound) || !((dataType == SZ_FLOAT ? (double)(float)bound : bound) > 0)) { later[nl++] = i; continue; }
@@ -1706,13 +1724,15 @@ static int compress_args_batch_at(const char *who, int dataType, int count, cons
         omp_meta_params(meta, &hp);
         meta[19] = SZH_OMP_MARK;
         items[nb].data = d_in[i]; items[nb].eb = dataType == SZ_FLOAT ? (double)(float)bound : bound; items[nb].meta = meta;
+        if (mixed) { shp[nb].r0 = e[0]; shp[nb].r1 = e[1]; shp[nb].r2 = e[2]; shp[nb].thread_num = thr; g_omp_last_threads = thr; }
         idx[nb++] = i;
     }
     if (nb > 0) {
         size_t blob_size = 0;
-        const int rc = view ? szhip_compress_omp_batch_view(ctx, dt, items, nb, data_on_device, r1, r2, r3, pitch0, pitch1, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats)
+        const int rc = mixed ? szhip_compress_omp_batch_shapes(ctx, dt, items, shp, nb, 1, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats)
+                     : view ? szhip_compress_omp_batch_view(ctx, dt, items, nb, data_on_device, r1, r2, r3, pitch0, pitch1, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats)
                             : szhip_compress_omp_batch(ctx, dt, items, nb, 1, r1, r2, r3, threads, &hp, 4 + (size_t)MetaDataByteLength, 0, &blob, &blob_size, &bstats);
-        if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp_batch%s failed (%d): %s\n", view ? "_view" : "", rc, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
+        if (rc != SZHIP_OK) { printf("Error: szhip_compress_omp_batch%s failed (%d): %s\n", mixed ? "_shapes" : view ? "_view" : "", rc, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
         for (int k = 0; k < nb && blob; ++k) {
             const int i = idx[k];
             if (items[k].rc != SZHIP_OK || items[k].size == 0) { rc_all = SZ_NSCS; continue; }
@@ -1731,13 +1751,14 @@ static int compress_args_batch_at(const char *who, int dataType, int count, cons
             const int prc = szhip_pack_view(ctx, dt, data[i], data_on_device, r1, r2, r3, pitch0, pitch1, &whole);
             if (prc != SZHIP_OK) { printf("Error: %s: szhip_pack_view of array %d failed (%d): %s\n", who, i, prc, szhip_last_error(ctx)); rc_all = SZ_NSCS; continue; }
         }
-        const int status = compress_fp(dataType, confparams_cpr->withRegression, &streams[i], whole, 0, 0, r1, r2, r3, &comp_sizes[i], errBoundMode, absErrBound,
-                                       relBoundRatio, 0, view ? &dev_io : io);
+        const size_t *e = mixed ? dims + 3 * (size_t)i : NULL;
+        const int status = compress_fp(dataType, confparams_cpr->withRegression, &streams[i], whole, 0, 0, mixed ? e[0] : r1, mixed ? e[1] : r2, mixed ? e[2] : r3, &comp_sizes[i],
+                                       errBoundMode, absErrBound, relBoundRatio, 0, view ? &dev_io : io);
         if (!streams[i]) { printf("Error: %s: array %d failed on the ordinary path (%d).\n", who, i, status); comp_sizes[i] = 0; rc_all = SZ_NSCS; }
     }
     g_last_stats = bstats;
 done:
-    free(blob); free(idx); free(metas); free(items); free(vmin); free((void *)d_in);
+    free(blob); free(shp); free(lens); free(idx); free(metas); free(items); free(vmin); free((void *)d_in);
     return rc_all;
 }
 
@@ -1745,6 +1766,13 @@ int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data,
                                size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched)
 {
     return compress_args_batch_at("SZ_hip_compress_args_batch", dataType, count, data, data_on_device, errBoundMode, absErrBound, relBoundRatio, r1, r2, r3, r2 * r3, r3,
+                                  NULL, streams, comp_sizes, batched);
+}
+int SZ_hip_compress_args_batch_shapes(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
+                                      const size_t *dims, unsigned char **streams, size_t *comp_sizes, int *batched)
+{
+    if (!dims) { printf("Error: SZ_hip_compress_args_batch_shapes: bad arguments.\n"); return SZ_NSCS; }
+    return compress_args_batch_at("SZ_hip_compress_args_batch_shapes", dataType, count, data, data_on_device, errBoundMode, absErrBound, relBoundRatio, 0, 0, 0, 0, 0, dims,
                                   streams, comp_sizes, batched);
 }
 
@@ -1775,55 +1803,69 @@ int SZ_hip_compress_args_batch_region(int dataType, int count, const void *const
     if (!base) return SZ_NSCS;
     for (int i = 0; i < count; ++i) base[i] = (const char *)parents[i] + first * esz;
     const int rc = compress_args_batch_at(who, dataType, count, base, data_on_device, errBoundMode, absErrBound, relBoundRatio, end[0] - start[0], end[1] - start[1],
-                                          end[2] - start[2], r2 * r3, r3, streams, comp_sizes, batched);
+                                          end[2] - start[2], r2 * r3, r3, NULL, streams, comp_sizes, batched);
     free((void *)base);
     return rc;
 }
 
-/* (out[i]: the first value of r1 x r2 x r3 values whose planes lie pitch0 and whose rows pitch1 elements apart, as in compress_args_batch_at) */
+/* (out[i]: the first value of r1 x r2 x r3 values whose planes lie pitch0 and whose rows pitch1 elements apart, as in compress_args_batch_at; `dims` (or NULL):
+ * contiguous arrays of different shapes, as there -- every marked container then goes into the one batched decode, whatever its box count) */
 static int decompress_batch_at(const char *who, int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
-                               size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1)
+                               size_t r1, size_t r2, size_t r3, size_t pitch0, size_t pitch1, const size_t *dims)
 {
-    const int view = pitch1 != r3 || pitch0 != r2 * r3;
+    const int view = pitch1 != r3 || pitch0 != r2 * r3, mixed = dims != NULL;
+    if (mixed) for (int i = 0; i < count; ++i) {
+        const size_t *e = dims + 3 * (size_t)i;
+        if (e[0] < 1 || e[1] < 1 || e[2] < 1 || e[0] > 0x7fffffff || e[1] > 0x7fffffff || e[2] > 0x7fffffff || (double)e[0] * (double)e[1] * (double)e[2] >= 4294967296.0) {
+            printf("Error: %s: array %d: extents %zu x %zu x %zu.\n", who, i, e[0], e[1], e[2]); return SZ_NSCS;
+        }
+    }
     if (count < 1 || !bytes || !byteLengths || !out || (dataType != SZ_FLOAT && dataType != SZ_DOUBLE)) { printf("Error: %s: bad arguments.\n", who); return SZ_NSCS; }
     szhip_ctx *ctx = get_ctx();
     if (!ctx) return SZ_NSCS;
     const size_t n = computeDataLength(0, 0, r1, r2, r3), esz = dataType == SZ_FLOAT ? 4 : 8, body = 4 + (size_t)MetaDataByteLength;
     szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
     int *idx = (int *)malloc((size_t)count * 2 * sizeof(int)), *single = idx ? idx + count : NULL;
-    if (!items || !idx) { free(items); free(idx); return SZ_NSCS; }
+    szhip_batch_shape *shp = mixed ? (szhip_batch_shape *)calloc((size_t)count, sizeof(szhip_batch_shape)) : NULL;
+    if (!items || !idx || (mixed && !shp)) { free(items); free(idx); free(shp); return SZ_NSCS; }
     int rc_all = SZ_SCES, nb = 0, ns = 0;
     uint32_t boxes = 0;
     szhip_stats bstats; memset(&bstats, 0, sizeof(bstats));
     /* the streams SZ_decompress takes for marked OpenMP containers (decompress_fp), with the box count of the first of them: one batched decode */
     for (int i = 0; i < count; ++i) {
         const unsigned char *s = bytes[i];
-        const int marked = s && out[i] && r1 >= 2 && r2 >= 2 && r3 >= 2 && n > MIN_NUM_OF_ELEMENTS && byteLengths[i] > body + 4 && s[0] == versionNumber[0] &&
+        const size_t *e = mixed ? dims + 3 * (size_t)i : NULL;
+        const size_t e1 = mixed ? e[0] : r1, e2 = mixed ? e[1] : r2, e3 = mixed ? e[2] : r3, ni = mixed ? e1 * e2 * e3 : n;
+        const int marked = s && out[i] && e1 >= 2 && e2 >= 2 && e3 >= 2 && ni > MIN_NUM_OF_ELEMENTS && byteLengths[i] > body + 4 && s[0] == versionNumber[0] &&
                            s[1] == versionNumber[1] && s[2] == versionNumber[2] && (s[3] & 0x80) && !(s[3] & 0x31) && s[19] == SZH_OMP_MARK;
         const uint32_t t = marked ? szhost_get_u32be(s + body) : 0;
         if (marked && boxes == 0) boxes = t;
-        if (marked && t == boxes && t != 0) {
+        if (marked && (mixed || t == boxes) && t != 0) {
+            if (mixed) { shp[nb].r0 = e1; shp[nb].r1 = e2; shp[nb].r2 = e3; }
             items[nb].stream = s; items[nb].stream_len = byteLengths[i]; items[nb].body_off = body; items[nb].out = out[i];
             idx[nb++] = i;
         } else single[ns++] = i;
     }
     if (nb > 0) {
         fresh_dec_state();
-        const int rc = view ? szhip_decompress_omp_batch_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, pitch0, pitch1, &bstats)
+        const int rc = mixed ? szhip_decompress_omp_batch_shapes(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, shp, nb, 0, out_on_device, &bstats)
+                     : view ? szhip_decompress_omp_batch_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, pitch0, pitch1, &bstats)
                             : szhip_decompress_omp_batch(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, nb, 0, r1, r2, r3, out_on_device, &bstats);
         if (rc != SZHIP_OK) {
             rc_all = SZ_NSCS;
             for (int k = 0; k < nb; ++k) if (items[k].rc != SZHIP_OK) printf("Error: %s: stream %d failed (%d).\n", who, idx[k], items[k].rc);
-            printf("Error: szhip_decompress_omp_batch failed (%d): %s\n", rc, szhip_last_error(ctx));
+            printf("Error: szhip_decompress_omp_batch%s failed (%d): %s\n", mixed ? "_shapes" : "", rc, szhip_last_error(ctx));
         }
     }
     /* everything else: the single call, stream by stream */
     for (int k = 0; k < ns; ++k) {
         const int i = single[k];
         void *o = NULL;
+        const size_t *e = mixed ? dims + 3 * (size_t)i : NULL;
+        const size_t ni = mixed ? e[0] * e[1] * e[2] : n;
         if (bytes[i] && out[i]) {
             size_t _r[5];
-            filterDimension(0, 0, r1, r2, r3, _r);
+            filterDimension(0, 0, mixed ? e[0] : r1, mixed ? e[1] : r2, mixed ? e[2] : r3, _r);
             fresh_dec_state();
             o = decompress_fp(dataType, bytes[i], byteLengths[i], _r[4], _r[3], _r[2], _r[1], _r[0], 0, out_on_device && !view ? out[i] : NULL);
         }
@@ -1842,17 +1884,22 @@ static int decompress_batch_at(const char *who, int dataType, int count, unsigne
             if (!ok) { printf("Error: %s: stream %d could not be placed: %s\n", who, i, szhip_last_error(ctx)); rc_all = SZ_NSCS; }
             continue;
         }
-        if (!out_on_device) { memcpy(out[i], o, n * esz); free(o); }
+        if (!out_on_device) { memcpy(out[i], o, ni * esz); free(o); }
     }
     if (nb > 0) g_last_stats = bstats;
-    free(items); free(idx);
+    free(items); free(idx); free(shp);
     return rc_all;
 }
 
 int SZ_hip_decompress_batch(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device,
                             size_t r1, size_t r2, size_t r3)
 {
-    return decompress_batch_at("SZ_hip_decompress_batch", dataType, count, bytes, byteLengths, out, out_on_device, r1, r2, r3, r2 * r3, r3);
+    return decompress_batch_at("SZ_hip_decompress_batch", dataType, count, bytes, byteLengths, out, out_on_device, r1, r2, r3, r2 * r3, r3, NULL);
+}
+int SZ_hip_decompress_batch_shapes(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *out, int out_on_device, const size_t *dims)
+{
+    if (!dims) { printf("Error: SZ_hip_decompress_batch_shapes: bad arguments.\n"); return SZ_NSCS; }
+    return decompress_batch_at("SZ_hip_decompress_batch_shapes", dataType, count, bytes, byteLengths, out, out_on_device, 0, 0, 0, 0, 0, dims);
 }
 
 int SZ_hip_decompress_batch_into_region(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *parents, int out_on_device,
@@ -1866,7 +1913,7 @@ int SZ_hip_decompress_batch_into_region(int dataType, int count, unsigned char *
     void **base = (void **)malloc((size_t)count * sizeof(void *));
     if (!base) return SZ_NSCS;
     for (int i = 0; i < count; ++i) base[i] = (char *)parents[i] + first * esz;
-    const int rc = decompress_batch_at(who, dataType, count, bytes, byteLengths, base, out_on_device, end[0] - start[0], end[1] - start[1], end[2] - start[2], r2 * r3, r3);
+    const int rc = decompress_batch_at(who, dataType, count, bytes, byteLengths, base, out_on_device, end[0] - start[0], end[1] - start[1], end[2] - start[2], r2 * r3, r3, NULL);
     free(base);
     return rc;
 }

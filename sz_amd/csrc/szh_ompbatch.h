@@ -158,3 +158,104 @@ __global__ __launch_bounds__(256) void k_ompb_view_scatter(const u64 *__restrict
     const u64 *pr = pairs + 2 * (u64)blockIdx.y;
     view_scatter_body<T>(reinterpret_cast<const T *>((uintptr_t)pr[1]), reinterpret_cast<T *>((uintptr_t)pr[0]), p0, p1, e1, e2, per_row, idx);
 }
+
+// =====================================================================================================================
+// Arrays of DIFFERENT shapes in one launch (szhip_compress_omp_batch_shapes / szhip_decompress_omp_batch_shapes).
+// What the kernels above take as an argument -- the box grid, the sampler's geometry and row limit, the boxes per histogram workgroup, the flag words -- is here a
+// second per-array record (szh_ompb_geo) beside the first; a workgroup reads both through list[blockIdx.y] (uniform: scalar loads, as the record's).  The grid's first
+// dimension is sized to the LARGEST array of the launch's list; a workgroup whose blockIdx.x lies beyond its own array's count returns at once (a uniform test).
+// The bodies are the single call's once more; k_ompbs_col repeats k_ompb_col's dozen lines, which repeat k_omp_col's (both stay as they are, to the letter).
+// One launch has one block size and one dynamic-LDS size, so k_ompbs_box is launched once per distinct box (c0 x c1 x c2) among the items of a form; the column
+// form takes every item with 32 x 32 faces in one launch, whatever its plane count and box count.
+struct szh_ompb_geo {
+    szh_omp_geom g;                            // the array's own box grid (omp_box_grid of its shape and thread_num)
+    szh_geom3 G; int64_t nrows;                // compress: the sampler's geometry and row limit
+    int per_wg, fw;                            // compress: boxes per workgroup of the histogram pass; decompress, column form: flag words per box (0: none)
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_ompbs_sample(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list, int sd,
+                                                      unsigned max_radius)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int64_t)blockIdx.x * 256 >= e.nrows) return;           // (rows go round the grid: a workgroup beyond the array's rows has none)
+    const szh_ompb_rec &r = recs[a];
+    sample_body<T, false>(e.G, (const T *)r.data, e.nrows, sd, r.eb, (T)0, max_radius, r.radius_hist, nullptr, r.totals + 3);
+}
+template <class T, int C1, int C2, bool DEC, bool COUNT>
+__global__ __launch_bounds__(64, (sizeof(T) == 4 ? 2 : 1)) void k_ompbs_col(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    typedef szh_oc::shape<T, C1, C2> S;
+    __shared__ __attribute__((aligned(16))) unsigned char ring_raw[S::RS * S::PITCH];
+    __shared__ unsigned flags_raw[DEC ? S::NB * OC_FLAG_WORDS : 1];
+    const int ai = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[ai];
+    if ((int)blockIdx.x * S::NB >= e.g.nb) return;
+    OC_LDS unsigned char *ring = (OC_LDS unsigned char *)ring_raw;
+    OC_LDS unsigned *fl = (OC_LDS unsigned *)flags_raw;
+    szh_oc::sweep_args<T> a;
+    ompb_sweep_args<T>(e.g, recs[ai], DEC, e.fw, a);
+    if (!DEC) { szh_oc::sweep<T, C1, C2, szh_oc::M_CMP, COUNT> s(ring, fl, a); s.run(); }
+    else {
+        const int b0 = (int)blockIdx.x * S::NB;
+        const bool verb = a.uoff[b0 + S::NB] != a.uoff[b0];          // (uniform)
+        if (verb) { szh_oc::sweep<T, C1, C2, szh_oc::M_DECV> s(ring, fl, a); s.run(); }
+        else { szh_oc::sweep<T, C1, C2, szh_oc::M_DEC> s(ring, fl, a); s.run(); }
+    }
+}
+// (every array of the list has the launch's box: blockDim.x = c0 * c1 rows, the dynamic LDS of 4 * c0 * pitch values)
+template <class T, bool DEC, bool VEC>
+__global__ __launch_bounds__(1024) void k_ompbs_box(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int)blockIdx.x >= e.g.nb) return;
+    const szh_ompb_rec &r = recs[a];
+    omp_box_body<T, DEC, VEC>(e.g, DEC ? nullptr : (const T *)r.data, DEC ? (T *)r.out : nullptr, (T)r.eb, (T)r.recip, (int)r.intervals, r.codes,
+                              DEC ? (unsigned *)(r.totals + 2) : r.ucount, DEC ? nullptr : r.ucount64, (T *)r.first, DEC ? (const T *)r.unpred : nullptr, DEC ? r.uoff : nullptr);
+}
+__global__ __launch_bounds__(256) void k_ompbs_hist_box(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int)blockIdx.x * e.per_wg >= e.g.nb) return;
+    const szh_ompb_rec &r = recs[a];
+    omp_hist_box_body(e.g.bel, r.codes, r.intervals, r.rshift, r.hist_box, r.hist, r.count_in_hist ? r.ucount : nullptr, r.count_in_hist ? r.ucount64 : nullptr, e.g.nb, e.per_wg);
+}
+__global__ __launch_bounds__(1024) void k_ompbs_layout(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_rec &r = recs[a];
+    omp_layout_body(geos[a].g.nb, r.intervals, r.hist_box, r.packed, r.ucount64, r.box_bytes, r.box_off, r.uoff, r.totals, r.totals + 1, 0);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompbs_encode_box3(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int)blockIdx.x >= e.g.nb) return;
+    const szh_ompb_rec &r = recs[a];
+    szh_omp_tables tb;
+    tb.stream = r.stream; tb.hdr = r.hdr; tb.hdr_len = r.hdr_len;
+    tb.off_ucount = r.off_ucount; tb.off_first = r.off_first; tb.off_unpred = r.off_unpred; tb.off_sizes = r.off_sizes; tb.first = r.first;
+    omp_encode_box3_body<T>(e.g, (const T *)r.data, r.codes, r.packed, r.intervals, (unsigned)r.maxlen, r.box_off, r.box_bytes, r.uoff, r.ucount, r.off_pay * 8,
+                            (unsigned *)r.stream, (T *)r.unpred, (unsigned *)(r.totals + 2), tb);
+}
+__global__ __launch_bounds__(256) void k_ompbs_hdec_lut(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list, unsigned stage_bytes)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int)blockIdx.x >= e.g.nb) return;
+    const szh_ompb_rec &r = recs[a];
+    omp_hdec_lut_body(e.g.bel, r.payload, r.bytes_before, r.box_off, r.box_bytes, r.table, r.n_nodes, r.tab_lds, r.lut, stage_bytes, r.codes, (unsigned *)(r.totals + 2));
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompbs_scatter(const szh_ompb_rec *__restrict__ recs, const szh_ompb_geo *__restrict__ geos, const int *__restrict__ list)
+{
+    const int a = list[blockIdx.y];
+    const szh_ompb_geo &e = geos[a];
+    if ((int)blockIdx.x >= e.g.nb) return;
+    const szh_ompb_rec &r = recs[a];
+    omp_scatter_body<T>(e.g, r.codes, r.uoff, (const T *)r.unpred, (T *)r.out, (unsigned *)(r.totals + 2), r.vflags, e.fw);
+}

@@ -107,6 +107,21 @@ __global__ __launch_bounds__(256) void k_minmax_batch(const T *const *__restrict
     }
 }
 
+// ... of arrays of DIFFERENT lengths (szhip_minmax_batch_lens): array a has lens[a] values.  The grid's first dimension is sized to the longest array; a workgroup
+// beyond the pieces of its own array returns (its lanes would find no piece: they go round the grid from blockIdx.x * 256; the first workgroup, which also reads the
+// head and the tail, always stays).  The run and the reduction are the bodies above; min and max do not depend on the order: bit for bit k_minmax_batch per array.
+template <class T>
+__global__ __launch_bounds__(256) void k_minmax_batch_lens(const T *const *__restrict__ bases, const int64_t *__restrict__ lens, u64 *res)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    __shared__ u64 red[8];
+    const int64_t n = lens[blockIdx.y];
+    if (blockIdx.x > 0 && (int64_t)blockIdx.x * 256 >= n / VW) return;          // (uniform; pieces <= n / VW)
+    u64 lmin = ~0ull, lmax = 0ull;
+    minmax_run_body<T, true>(threadIdx.x, bases[blockIdx.y], n, 0, lmin, lmax);
+    minmax_reduce_body(threadIdx.x, lmin, lmax, red, res);
+}
+
 // ... of MANY SUB-BOXES of e0 x e1 x e2 values with the common element pitches p0 / p1 (szhip_minmax_batch_view), each at its own base: every ROW is a run, cut at
 // its own 16-byte boundaries.  The workgroup's lanes form groups of `gs` lanes (a power of two, 2 VW .. 256: the host sizes it to the pieces of a row); group q of
 // the sub-box's workgroups takes the rows q, q + groups, ...  Min and max do not depend on the order: bit for bit k_minmax_batch on the contiguous copy.

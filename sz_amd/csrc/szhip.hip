@@ -434,6 +434,17 @@ int szhip_stage_input_batch(szhip_ctx *ctx, const void *const *host_data, int co
     for (int i = 0; i < count; ++i) device_ptrs[i] = d[i];
     return SZHIP_OK;
 }
+int szhip_stage_input_batch_lens(szhip_ctx *ctx, const void *const *host_data, int count, const size_t *bytes, const void **device_ptrs)
+{
+    if (!ctx || !host_data || !device_ptrs || !bytes || count < 1) return SZHIP_ERR_ARG;
+    for (int i = 0; i < count; ++i) if (!host_data[i] || bytes[i] == 0) return SZHIP_ERR_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    std::vector<const void *> d;
+    TRY(synced_on_failure(ctx, batch_stage(ctx, ctx->in, count, 0, ctx->stream, [&](int i) { return host_data[i]; }, d, nullptr, bytes)));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) device_ptrs[i] = d[i];
+    return SZHIP_OK;
+}
 
 // include/szhip.h, "Device pointers and ordering": a pointer to VALUES (`data`, `out` of a decompress call) is aligned to its element, on the host or on the device;
 // refused here, before anything is launched; then the context's device is made current.  Byte pointers (streams, parameter bytes, a caller's stream buffer) take any alignment.
@@ -474,7 +485,7 @@ int szhip_minmax_batch(szhip_ctx *ctx, int dtype, const void *const *data, int c
     if (!vmin || !vmax) return SZHIP_ERR_ARG;
     TRY(batch_pointers(ctx, dtype, data, count, n));
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
-    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, 1, 1, n, n, n, vmin, vmax, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, 1, 1, n, n, n, nullptr, vmin, vmax, stats));
 }
 static int check_view(szhip_ctx *ctx, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1);
 int szhip_minmax_batch_view(szhip_ctx *ctx, int dtype, const void *const *data, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
@@ -487,7 +498,7 @@ int szhip_minmax_batch_view(szhip_ctx *ctx, int dtype, const void *const *data, 
     if ((double)r0 * (double)r1 * (double)r2 >= 4294967296.0) { snprintf(ctx->err, sizeof(ctx->err), "szhip_minmax_batch_view: sub-boxes of 2^32 values or more"); return SZHIP_ERR_UNSUP; }
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     if (pitch1 == r2 && pitch0 == r1 * r2) { const size_t n = r0 * r1 * r2; r0 = r1 = 1; r2 = pitch0 = pitch1 = n; }      // (the contiguous call, exactly)
-    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, r0, r1, r2, pitch0, pitch1, vmin, vmax, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, r0, r1, r2, pitch0, pitch1, nullptr, vmin, vmax, stats));
 }
 
 int szhip_compress(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, double eb,
@@ -583,7 +594,7 @@ static int compress_omp_batch_entry(szhip_ctx *ctx, int dtype, szhip_batch_item 
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     for (int i = 0; i < count; ++i) { items[i].offset = items[i].size = 0; items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
     *blob = nullptr; *blob_size = 0;
-    return synced_on_failure(ctx, BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, r0, r1, r2, pitch0, pitch1, thread_num, params, meta_len, out_on_device,
+    return synced_on_failure(ctx, BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, nullptr, r0, r1, r2, pitch0, pitch1, thread_num, params, meta_len, out_on_device,
                                            blob, blob_size, stats));
 }
 static int decompress_omp_batch_entry(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2,
@@ -593,7 +604,7 @@ static int decompress_omp_batch_entry(szhip_ctx *ctx, int dtype, szhip_batch_ite
     TRY(check_view(ctx, r0, r1, r2, pitch0, pitch1));
     if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
     for (int i = 0; i < count; ++i) { items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
-    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, r0, r1, r2, out_on_device, pitch0, pitch1, stats));
+    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, nullptr, r0, r1, r2, out_on_device, pitch0, pitch1, stats));
 }
 
 int szhip_compress_omp_batch(szhip_ctx *ctx, int dtype, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, int thread_num,
@@ -616,6 +627,60 @@ int szhip_decompress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item 
                                     int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
 {
     return decompress_omp_batch_entry(ctx, dtype, items, count, stream_on_device, r0, r1, r2, out_on_device, pitch0, pitch1, stats);
+}
+
+// ---- arrays of different shapes in one call
+// the refusals of the shapes, before anything is launched or written: SZHIP_ERR_ARG (an extent that is no extent, no thread_num), SZHIP_ERR_UNSUP (an item of 2^32 values)
+static int batch_shapes_args(szhip_ctx *ctx, const szhip_batch_shape *shapes, int count, bool compress)
+{
+    if (!shapes) return SZHIP_ERR_ARG;
+    for (int i = 0; i < count; ++i) {
+        const szhip_batch_shape &s = shapes[i];
+        if (s.r0 < 1 || s.r1 < 1 || s.r2 < 1 || s.r0 > 0x7fffffff || s.r1 > 0x7fffffff || s.r2 > 0x7fffffff || (compress && s.thread_num < 1)) {
+            snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: extents %zu x %zu x %zu, thread_num %d", i, s.r0, s.r1, s.r2, s.thread_num);
+            return SZHIP_ERR_ARG;
+        }
+    }
+    for (int i = 0; i < count; ++i)
+        if ((double)shapes[i].r0 * (double)shapes[i].r1 * (double)shapes[i].r2 >= 4294967296.0) {
+            snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: 2^32 values or more", i);
+            return SZHIP_ERR_UNSUP;
+        }
+    return SZHIP_OK;
+}
+int szhip_compress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, int count, int data_on_device, const szhip_params *params,
+                                    size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+{
+    if (!params || !blob || !blob_size) return SZHIP_ERR_ARG;
+    TRY(batch_args(ctx, dtype, items, count, 1, 1, 1, true));
+    TRY(batch_shapes_args(ctx, shapes, count, true));
+    if (out_on_device != 0 && out_on_device != 1) { snprintf(ctx->err, sizeof(ctx->err), "a batch writes into a host blob (0) or the context's device blob (1)"); return SZHIP_ERR_UNSUP; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) { items[i].offset = items[i].size = 0; items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
+    *blob = nullptr; *blob_size = 0;
+    return synced_on_failure(ctx, BY_DTYPE(dtype, compress_omp_batch_impl, ctx, items, count, data_on_device, shapes, 0, 0, 0, 0, 0, 0, params, meta_len, out_on_device, blob, blob_size, stats));
+}
+int szhip_decompress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, int count, int stream_on_device, int out_on_device,
+                                      szhip_stats *stats)
+{
+    TRY(batch_args(ctx, dtype, items, count, 1, 1, 1, false));
+    TRY(batch_shapes_args(ctx, shapes, count, false));
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) { items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0; }
+    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_impl, ctx, items, count, stream_on_device, shapes, 0, 0, 0, out_on_device, 0, 0, stats));
+}
+int szhip_minmax_batch_lens(szhip_ctx *ctx, int dtype, const void *const *data, const size_t *lens, int count, int data_on_device, double *vmin, double *vmax, szhip_stats *stats)
+{
+    if (!vmin || !vmax || !lens) return SZHIP_ERR_ARG;
+    TRY(batch_pointers(ctx, dtype, data, count, 1));
+    size_t longest = 0;
+    for (int i = 0; i < count; ++i) {
+        if (lens[i] == 0) { snprintf(ctx->err, sizeof(ctx->err), "array %d of the batch: no values", i); return SZHIP_ERR_ARG; }
+        if (lens[i] >= ((size_t)1 << 32)) { snprintf(ctx->err, sizeof(ctx->err), "array %d of the batch: 2^32 values or more", i); return SZHIP_ERR_UNSUP; }
+        longest = lens[i] > longest ? lens[i] : longest;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    return synced_on_failure(ctx, BY_DTYPE(dtype, minmax_batch_impl, ctx, data, count, data_on_device, 1, 1, longest, longest, longest, lens, vmin, vmax, stats));
 }
 
 int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *stream, int stream_on_device, size_t stream_len, size_t body_off,

@@ -3,6 +3,9 @@
 // The steps are those of omp_call / omp_dec, each ONE launch with the array as the grid's second dimension; what a step of the single call keeps in members is here a
 // per-array record (szh_ompb_rec) in a device table that is uploaded whole whenever the host has learnt something new about the arrays (the interval counts, the books).
 // An array the shared launches do not cover goes through compress_omp_impl / decompress_omp_impl from inside the call.
+// The same two functions serve arrays of DIFFERENT shapes (szhip_compress_omp_batch_shapes / szhip_decompress_omp_batch_shapes; DESIGN section 4.5.7): the geometry is
+// then per item (ompb_shape on the host, szh_ompb_geo in the device table), the work arrays lie at prefix sums of each item's own lengths, the launches are the k_ompbs_*
+// wrappers sized to their largest item, and the conditions that send a whole same-shape batch to the single calls send one item there.
 // =====================================================================================================================
 // (`g` carries the pitches of the array `base` lies in -- a view's after omp_view_pitches --, pitch0 / pitch1 are the same in elements)
 static int omp_form(const szh_omp_geom &g, const void *base, size_t elem, size_t pitch0, size_t pitch1)
@@ -12,30 +15,35 @@ static int omp_form(const szh_omp_geom &g, const void *base, size_t elem, size_t
 }
 static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 static size_t up64(size_t v) { return (v + 63) / 64 * 64; }
-static int ompb_limits(szhip_ctx *ctx, int count, size_t nb, size_t n)
+// (`boxes`, `values`: of all arrays of the batch together)
+static int ompb_limits(szhip_ctx *ctx, int count, size_t boxes, size_t values)
 {
-    if (count > 65535 || (size_t)count * nb > ((size_t)1 << 22) || (size_t)count * n >= ((size_t)1 << 32))
-        FAIL(SZHIP_ERR_UNSUP, "OpenMP-container batch: %d arrays of %zu boxes and %zu values (at most 65535 arrays, 2^22 boxes and 2^32 - 1 values in all)", count, nb, n);
+    if (count > 65535 || boxes > ((size_t)1 << 22) || values >= ((size_t)1 << 32))
+        FAIL(SZHIP_ERR_UNSUP, "OpenMP-container batch: %d arrays of %zu boxes and %zu values in all (at most 65535 arrays, 2^22 boxes and 2^32 - 1 values)", count, boxes, values);
     return SZHIP_OK;
 }
 // `count` host arrays of `bytes` bytes each, one behind the other at multiples of 16 into `buf` (asynchronous on `st`; the callers' arrays have been read on return):
 // ONE copy through the context's pinned block when they total at most 64 MiB, else array by array.  d[i]: where array i lies then.
 // `hv`: the host arrays are VIEWS of `bytes` bytes each (the batched view calls): their rows alone are copied, packed, as staged_copy does with a host view.
+// `each` (or null): array i has each[i] bytes, not `bytes` (arrays of different shapes: every one at its own length, still at multiples of 16)
 template <class GET>
-int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_t st, GET &&host, std::vector<const void *> &d, const host_view *hv = nullptr)
+int batch_stage(szhip_ctx *ctx, DevBuf &buf, int count, size_t bytes, hipStream_t st, GET &&host, std::vector<const void *> &d, const host_view *hv = nullptr,
+                const size_t *each = nullptr)
 {
-    const size_t stride = up16(bytes);
+    std::vector<size_t> at((size_t)count + 1, 0);
+    for (int i = 0; i < count; ++i) at[i + 1] = at[i] + up16(each ? each[i] : bytes);
+    const size_t total = at[count];
     d.resize((size_t)count);
-    TRY(ensure(ctx, buf, (size_t)count * stride));
-    for (int i = 0; i < count; ++i) d[i] = (const char *)buf.p + (size_t)i * stride;
-    if ((size_t)count * stride <= ((size_t)64 << 20)) {
-        TRY(ensure_pinned3(ctx, (size_t)count * stride));
+    TRY(ensure(ctx, buf, total));
+    for (int i = 0; i < count; ++i) d[i] = (const char *)buf.p + at[i];
+    if (total <= ((size_t)64 << 20)) {
+        TRY(ensure_pinned3(ctx, total));
         for (int i = 0; i < count; ++i) {
-            if (hv) host_view_move(*hv, (char *)const_cast<void *>((const void *)host(i)), (char *)ctx->pinned3 + (size_t)i * stride, 0, bytes, true);
-            else memcpy((char *)ctx->pinned3 + (size_t)i * stride, host(i), bytes);
+            if (hv) host_view_move(*hv, (char *)const_cast<void *>((const void *)host(i)), (char *)ctx->pinned3 + at[i], 0, bytes, true);
+            else memcpy((char *)ctx->pinned3 + at[i], host(i), each ? each[i] : bytes);
         }
-        HIPCHK(hipMemcpyAsync(buf.p, ctx->pinned3, (size_t)count * stride, hipMemcpyHostToDevice, st));
-    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)buf.p + (size_t)i * stride, host(i), bytes, true, hv));
+        HIPCHK(hipMemcpyAsync(buf.p, ctx->pinned3, total, hipMemcpyHostToDevice, st));
+    } else for (int i = 0; i < count; ++i) TRY(staged_copy(ctx, (char *)buf.p + at[i], host(i), each ? each[i] : bytes, true, hv));
     return SZHIP_OK;
 }
 
@@ -46,17 +54,21 @@ enum { OMPB_L_ALL = 0, OMPB_L_F3, OMPB_L_F4, OMPB_L_F5, OMPB_L_ENT, OMPB_L_PACK,
 struct ompb_table {
     szhip_ctx *ctx; int count;
     std::vector<szh_ompb_rec> rec; std::vector<int> list[OMPB_LISTS];
-    size_t o_rec, o_list, o_extra;
+    std::vector<szh_ompb_geo> geo;                          // a call on arrays of different shapes: every array's own geometry, between the lists and `extra` (else empty)
+    size_t o_rec, o_list, o_geo, o_extra;
     std::vector<unsigned char> image[3];                    // the host copies of the uploads (one per version: a pageable source stays untouched until the next synchronisation)
-    ompb_table(szhip_ctx *c, int n) : ctx(c), count(n), rec((size_t)n)
+    ompb_table(szhip_ctx *c, int n, bool with_geo = false) : ctx(c), count(n), rec((size_t)n), geo(with_geo ? (size_t)n : 0)
     {
         memset(rec.data(), 0, rec.size() * sizeof(szh_ompb_rec));
-        o_rec = up64((size_t)n * 32); o_list = o_rec + (size_t)n * sizeof(szh_ompb_rec); o_extra = up64(o_list + (size_t)OMPB_LISTS * n * 4);
+        if (with_geo) memset(geo.data(), 0, geo.size() * sizeof(szh_ompb_geo));
+        o_rec = up64((size_t)n * 32); o_list = o_rec + (size_t)n * sizeof(szh_ompb_rec); o_geo = up64(o_list + (size_t)OMPB_LISTS * n * 4);
+        o_extra = up64(o_geo + geo.size() * sizeof(szh_ompb_geo));
     }
     int reserve(size_t extra) { return ensure(ctx, ctx->batch_rec, o_extra + extra + 64); }
     unsigned char *dev() const { return (unsigned char *)ctx->batch_rec.p; }
     u64 *totals(int i) const { return (u64 *)dev() + 4 * (size_t)i; }
     const szh_ompb_rec *d_rec() const { return (const szh_ompb_rec *)(dev() + o_rec); }
+    const szh_ompb_geo *d_geo() const { return (const szh_ompb_geo *)(dev() + o_geo); }
     const int *d_list(int which) const { return (const int *)(dev() + o_list) + (size_t)which * count; }
     int clear_totals() { HIPCHK(hipMemsetAsync(dev(), 0, (size_t)count * 32, ctx->stream)); return SZHIP_OK; }
     // records, lists and `extra` (placed at o_extra) to the device
@@ -66,44 +78,100 @@ struct ompb_table {
         im.assign(o_extra - o_rec + extra.size(), 0);
         memcpy(im.data(), rec.data(), rec.size() * sizeof(szh_ompb_rec));
         for (int l = 0; l < OMPB_LISTS; ++l) if (!list[l].empty()) memcpy(im.data() + (o_list - o_rec) + (size_t)l * count * 4, list[l].data(), list[l].size() * 4);
+        if (!geo.empty()) memcpy(im.data() + (o_geo - o_rec), geo.data(), geo.size() * sizeof(szh_ompb_geo));
         if (!extra.empty()) memcpy(im.data() + (o_extra - o_rec), extra.data(), extra.size());
         HIPCHK(hipMemcpyAsync(dev() + o_rec, im.data(), im.size(), hipMemcpyHostToDevice, ctx->stream));
         return SZHIP_OK;
     }
 };
 
+// what the host knows of item i's geometry: extents, values, boxes, thread_num, omp_box_grid's verdict on them and its grid
+struct ompb_shape { size_t r0, r1, r2, n, nb; int thread_num, rc; szh_omp_geom g; };
+// the items of `l` ordered so that those with equal boxes c0 x c1 x c2 stand together (one k_ompbs_box launch per such run): where the runs end
+static std::vector<int> ompb_box_runs(std::vector<int> &l, const std::vector<ompb_shape> &sh)
+{
+    auto less = [&](int a, int b) {
+        const szh_omp_geom &x = sh[a].g, &y = sh[b].g;
+        return x.c0 != y.c0 ? x.c0 < y.c0 : x.c1 != y.c1 ? x.c1 < y.c1 : x.c2 < y.c2;
+    };
+    std::stable_sort(l.begin(), l.end(), less);
+    std::vector<int> ends;
+    for (size_t k = 0; k < l.size(); ++k) if (k + 1 == l.size() || less(l[k], l[k + 1])) ends.push_back((int)k + 1);
+    return ends;
+}
+// the largest box count among the items l[from .. to): what sizes the first dimension of a launch over them
+static size_t ompb_most_boxes(const std::vector<int> &l, int from, int to, const std::vector<ompb_shape> &sh)
+{
+    size_t m = 1;
+    for (int k = from; k < to; ++k) m = std::max(m, sh[l[k]].nb);
+    return m;
+}
+
 // pitch0 / pitch1: the element pitches of the arrays the items' sub-boxes lie in (szhip_compress_omp_batch_view; r1 * r2 and r2: contiguous arrays).  A view on the
 // device takes one of two ways, per item (omp_view_packs, as in the single view call): where it lies, through the pitched geometry `gv`, or GATHERED into a contiguous
 // copy in the context's input buffer by one k_ompb_crop launch for all such items, where it runs the column form through `g`.  Host views are staged packed.
+// `shapes` (or null): item i is a contiguous array of shapes[i] with shapes[i].thread_num boxes (szhip_compress_omp_batch_shapes; r0 .. thread_num are not looked at,
+// and there are no views): every item has its own grid `sh[i].g`, its work arrays lie behind those of the items before it, and the launches take the geometry from
+// the table's second record (k_ompbs_*).  Without `shapes` every sh[i] is the call's one shape and the launches are the same-shape ones (k_ompb_*).
 template <class T>
-int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1, int thread_num,
-                            const szhip_params *prm, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size, szhip_stats *stats)
+int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int data_on_device, const szhip_batch_shape *shapes, size_t r0, size_t r1, size_t r2,
+                            size_t pitch0, size_t pitch1, int thread_num, const szhip_params *prm, size_t meta_len, int out_on_device, unsigned char **blob, size_t *blob_size,
+                            szhip_stats *stats)
 {
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
-    szh_omp_geom g;
-    TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+    const bool mixed = shapes != nullptr;
+    enum { BATCH, EARLY, LATE, FAILED };
+    std::vector<int> state((size_t)count, BATCH);
+    std::vector<ompb_shape> sh((size_t)count);
+    szh_omp_geom g;                                             // (the same-shape call's grid)
+    memset(&g, 0, sizeof(g));
+    if (mixed) {
+        r0 = r1 = r2 = pitch0 = pitch1 = 0;
+        for (int i = 0; i < count; ++i) {                       // a shape the single call refuses: that item alone
+            ompb_shape &s = sh[i];
+            s.r0 = shapes[i].r0; s.r1 = shapes[i].r1; s.r2 = shapes[i].r2; s.thread_num = shapes[i].thread_num; s.n = s.r0 * s.r1 * s.r2;
+            s.rc = omp_box_grid(ctx, s.thread_num, s.r0, s.r1, s.r2, &s.g);
+            s.nb = s.rc == SZHIP_OK ? (size_t)s.g.nb : 0;
+            if (s.rc != SZHIP_OK) { state[i] = FAILED; items[i].rc = s.rc; }
+        }
+    } else {
+        TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
+        const ompb_shape s = {r0, r1, r2, r0 * r1 * r2, (size_t)g.nb, thread_num, SZHIP_OK, g};
+        sh.assign((size_t)count, s);
+    }
     const bool host_view_in = !data_on_device && (pitch1 != r2 || pitch0 != r1 * r2);
     const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
     if (host_view_in) { pitch0 = r1 * r2; pitch1 = r2; }       // (staged packed below: contiguous from there on)
     const bool view = pitch1 != r2 || pitch0 != r1 * r2;
     szh_omp_geom gv = g;
     if (view) omp_view_pitches(&gv, pitch0, pitch1, sizeof(T));
-    const size_t n = r0 * r1 * r2, nb = (size_t)g.nb;
-    TRY(ompb_limits(ctx, count, nb, n));
-    S.n_elements = (uint64_t)count * n; S.n_blocks = (uint64_t)count * nb;
-    enum { BATCH, EARLY, LATE, FAILED };
-    std::vector<int> state((size_t)count, BATCH);
-    // an array that misses box_hist's conditions whatever its intervals, or whose samples the walk of k_sample_walk takes: every array through the single call
-    const bool shared = g.bel % 8 == 0 && r0 > 1 && r1 > 1;
-    if (!shared) state.assign((size_t)count, EARLY);
+    size_t sum_n = 0, sum_nb = 0;
+    for (const ompb_shape &s : sh) { sum_n += s.n; sum_nb += s.nb; }
+    TRY(ompb_limits(ctx, count, sum_nb, sum_n));
+    S.n_elements = (uint64_t)sum_n; S.n_blocks = (uint64_t)sum_nb;
+    // an array that misses box_hist's conditions whatever its intervals, or whose samples the walk of k_sample_walk takes: through the single call (one shape: every array)
+    bool shared = false;
+    for (int i = 0; i < count; ++i) {
+        if (state[i] != BATCH) continue;
+        if (sh[i].g.bel % 8 == 0 && sh[i].r0 > 1 && sh[i].r1 > 1) shared = true; else state[i] = EARLY;
+    }
+    // the work arrays of the shared launches: item i's codes behind those of the items before it (n is a multiple of 8: 16-byte reads stay aligned), its per-box
+    // tables -- nb or nb + 1 entries -- at multiples of 16 entries (every table keeps the alignment its allocation gives it in the single call)
+    std::vector<size_t> o_code((size_t)count, 0), o_box((size_t)count, 0);
+    size_t n_codes = 0, n_slots = 0;
+    for (int i = 0; i < count; ++i) if (state[i] == BATCH) { o_code[i] = n_codes; n_codes += sh[i].n; o_box[i] = n_slots; n_slots += (sh[i].nb + 1 + 15) / 16 * 16; }
     // ---- 1. host arrays one behind the other into the context's input buffer
     std::vector<const T *> d_in((size_t)count);
     if (data_on_device) for (int i = 0; i < count; ++i) d_in[i] = (const T *)items[i].data;
     else {
         std::vector<const void *> d;
-        TRY(batch_stage(ctx, ctx->in, count, n * sizeof(T), st, [&](int i) { return items[i].data; }, d, host_view_in ? &hv : nullptr));
+        std::vector<size_t> each;
+        if (mixed) for (const ompb_shape &s : sh) each.push_back(s.n * sizeof(T));
+        TRY(batch_stage(ctx, ctx->in, count, r0 * r1 * r2 * sizeof(T), st, [&](int i) { return items[i].data; }, d, host_view_in ? &hv : nullptr, mixed ? each.data() : nullptr));
         for (int i = 0; i < count; ++i) d_in[i] = (const T *)d[i];
     }
+    auto p0 = [&](int i) { return mixed ? sh[i].r1 * sh[i].r2 : pitch0; };      // the element pitches of the array item i lies in
+    auto p1 = [&](int i) { return mixed ? sh[i].r2 : pitch1; };
     // where the shared launches read array i: d_in[i], or (a gathered view, from the gather on) its contiguous copy
     std::vector<const T *> src(d_in);
     std::vector<char> gathered((size_t)count, 0);
@@ -113,7 +181,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
     auto single = [&](int i) {
         unsigned char *p = nullptr; size_t len = 0; szhip_stats s1;
         memset(&s1, 0, sizeof(s1));
-        const int rc = compress_omp_impl<T>(ctx, d_in[i], 1, r0, r1, r2, pitch0, pitch1, items[i].eb, thread_num, prm, items[i].meta, meta_len, 0, &p, &len, &s1);
+        const int rc = compress_omp_impl<T>(ctx, d_in[i], 1, sh[i].r0, sh[i].r1, sh[i].r2, p0(i), p1(i), items[i].eb, sh[i].thread_num, prm, items[i].meta, meta_len, 0, &p, &len, &s1);
         items[i].rc = rc; items[i].batched = 0;
         if (rc == SZHIP_OK) {
             fb[i].assign(p, p + len); free(p);
@@ -123,14 +191,14 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
     // ---- the per-array tables of the shared launches
     const unsigned max_radius = prm->max_quant_intervals / 2;
     const bool optimise = prm->quantization_intervals == 0;
-    ompb_table tab(ctx, count);
+    ompb_table tab(ctx, count, mixed);
     uint16_t *d_codes = nullptr; unsigned *d_hist = nullptr;
     if (shared) {
         TRY(tab.reserve(view ? (size_t)count * 16 : 0));       // (a view call: the gather's pairs of addresses behind the lists)
-        TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
-        TRY(ensure(ctx, ctx->zcnt, (size_t)count * nb * 4)); TRY(ensure(ctx, ctx->samples, (size_t)count * nb * sizeof(T)));
-        TRY(ensure(ctx, ctx->col_zeros64, (size_t)count * nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)count * (nb + 1) * 8));
-        TRY(ensure(ctx, ctx->reg_flags, (size_t)count * nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)count * nb * 8));
+        TRY(ensure(ctx, ctx->codes_nat, n_codes * 2 + 64));
+        TRY(ensure(ctx, ctx->zcnt, n_slots * 4)); TRY(ensure(ctx, ctx->samples, n_slots * sizeof(T)));
+        TRY(ensure(ctx, ctx->col_zeros64, n_slots * 8)); TRY(ensure(ctx, ctx->col_off, n_slots * 8));
+        TRY(ensure(ctx, ctx->reg_flags, n_slots * 8)); TRY(ensure(ctx, ctx->reg_rank, n_slots * 8));
         TRY(ensure(ctx, ctx->hist, std::max((size_t)count * std::max<size_t>(optimise ? max_radius : 0, 1024), (size_t)65536 + 8192) * 4 + 8192 * 4 + 64));      // (never less than a single call asks for: none of them inside this call may move it)
         d_codes = (uint16_t *)ctx->codes_nat.p; d_hist = (unsigned *)ctx->hist.p;
     }
@@ -139,28 +207,41 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
             szh_ompb_rec &r = tab.rec[i];
             const T ebT = (T)items[i].eb;
             r.data = src[i]; r.eb = (double)ebT; r.recip = (double)(T)(1 / ebT);
-            r.codes = d_codes + (size_t)i * n;
-            r.ucount = (unsigned *)ctx->zcnt.p + (size_t)i * nb; r.ucount64 = (u64 *)ctx->col_zeros64.p + (size_t)i * nb; r.first = (T *)ctx->samples.p + (size_t)i * nb;
-            r.box_bytes = (u64 *)ctx->reg_flags.p + (size_t)i * nb; r.box_off = (u64 *)ctx->reg_rank.p + (size_t)i * nb; r.uoff = (u64 *)ctx->col_off.p + (size_t)i * (nb + 1);
+            r.codes = d_codes + o_code[i];
+            r.ucount = (unsigned *)ctx->zcnt.p + o_box[i]; r.ucount64 = (u64 *)ctx->col_zeros64.p + o_box[i]; r.first = (T *)ctx->samples.p + o_box[i];
+            r.box_bytes = (u64 *)ctx->reg_flags.p + o_box[i]; r.box_off = (u64 *)ctx->reg_rank.p + o_box[i]; r.uoff = (u64 *)ctx->col_off.p + o_box[i];
             r.totals = tab.totals(i);
         }
     };
+    if (mixed) for (int i = 0; i < count; ++i) {                // every item's own geometry, for every launch of the call
+        if (state[i] != BATCH) continue;
+        szh_ompb_geo &e = tab.geo[i];
+        e.g = sh[i].g; e.G = szh_make_geom3((int)sh[i].r0, (int)sh[i].r1, (int)sh[i].r2); e.nrows = szh_sample_row_limit(e.G, prm->sample_distance);
+        e.per_wg = std::max(1, std::min(16, 32768 / std::max(1, e.g.bel))); e.fw = 0;
+    }
     // ---- 2. the interval optimiser: one sampling launch, one read-back, pick_intervals per array
     std::vector<unsigned> iv((size_t)count, prm->quantization_intervals);
     HIPCHK(hipEventRecord(ctx->ev[0], st));
     if (shared && optimise) {
-        const szh_geom3 G = szh_make_geom3((int)r0, (int)r1, (int)r2);
-        const int64_t nrows = szh_sample_row_limit(G, prm->sample_distance);
+        const szh_geom3 G = mixed ? szh_make_geom3(1, 1, 1) : szh_make_geom3((int)r0, (int)r1, (int)r2);
+        int64_t nrows = mixed ? 0 : szh_sample_row_limit(G, prm->sample_distance);      // (different shapes: the longest item's, which sizes the grid)
         TRY(ensure_pinned(ctx, (size_t)count * max_radius * 4 + 64));
         HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)count * max_radius * 4, st));
         TRY(tab.clear_totals());
         fill_static();
-        tab.list[OMPB_L_ALL].resize((size_t)count);
-        for (int i = 0; i < count; ++i) { tab.rec[i].radius_hist = d_hist + (size_t)i * max_radius; tab.list[OMPB_L_ALL][i] = i; }
+        for (int i = 0; i < count; ++i) {
+            tab.rec[i].radius_hist = d_hist + (size_t)i * max_radius;
+            if (state[i] != BATCH) continue;
+            tab.list[OMPB_L_ALL].push_back(i);
+            if (mixed) nrows = std::max(nrows, tab.geo[i].nrows);
+        }
+        const int n_all = (int)tab.list[OMPB_L_ALL].size();
         TRY(tab.upload(0, {}));
         if (nrows > 0) {
             const int grid = (int)std::min<int64_t>((nrows + 255) / 256, 1024);
-            if (view) hipLaunchKernelGGL((k_ompb_sample_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), (int64_t)pitch0, (int64_t)pitch1, nrows,
+            if (mixed) hipLaunchKernelGGL((k_ompbs_sample<T>), dim3((unsigned)grid, (unsigned)n_all), dim3(256), 0, st, tab.d_rec(), tab.d_geo(), tab.d_list(OMPB_L_ALL), prm->sample_distance,
+                                          max_radius);
+            else if (view) hipLaunchKernelGGL((k_ompb_sample_view<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), (int64_t)pitch0, (int64_t)pitch1, nrows,
                                          prm->sample_distance, max_radius);         // (every view where it lies: the gather comes behind the single calls, which use its buffer)
             else hipLaunchKernelGGL((k_ompb_sample<T>), dim3((unsigned)grid, (unsigned)count), dim3(256), 0, st, G, tab.d_rec(), tab.d_list(OMPB_L_ALL), nrows, prm->sample_distance, max_radius);
             HIPCHK(hipGetLastError());
@@ -169,7 +250,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         HIPCHK(hipMemcpyAsync(ctx->pinned, d_hist, (size_t)count * max_radius * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         const double h0 = now_ms();
-        for (int i = 0; i < count; ++i) iv[i] = pick_intervals(h_rh + (size_t)i * max_radius, max_radius, prm->pred_threshold, 32u);
+        for (int i = 0; i < count; ++i) if (state[i] == BATCH) iv[i] = pick_intervals(h_rh + (size_t)i * max_radius, max_radius, prm->pred_threshold, 32u);
         cb.host_ms += now_ms() - h0;
     }
     HIPCHK(hipEventRecord(ctx->ev[1], st));
@@ -182,21 +263,24 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
             state[i] = FAILED; items[i].rc = SZHIP_ERR_UNSUP;
             snprintf(ctx->err, sizeof(ctx->err), "quantization interval count %u outside [4,65536]", iv[i]);
         }
+        const size_t nb = sh[i].nb;
         if (state[i] == BATCH && (iv[i] > 1024 || nb * iv[i] * 4 > ((size_t)64 << 20))) state[i] = EARLY;
         if (state[i] == EARLY) { single(i); continue; }
         if (state[i] != BATCH) continue;
-        const int form = gathered[i] ? 3 : omp_form(gv, d_in[i], sizeof(T), pitch0, pitch1);      // (a gathered view: the column form in its contiguous, aligned copy)
+        const int form = gathered[i] ? 3 : omp_form(mixed ? sh[i].g : gv, d_in[i], sizeof(T), p0(i), p1(i));      // (a gathered view: the column form in its contiguous, aligned copy)
         items[i].intervals = iv[i]; items[i].quant_kernel = form; items[i].batched = 1;
         tab.list[gathered[i] ? OMPB_L_F3G : form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
         tab.list[OMPB_L_ENT].push_back(i);
         int rshift = 0;
-        while ((iv[i] << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)iv[i] << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
+        while ((iv[i] << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)iv[i] << (rshift + 1)) * 16 <= (size_t)sh[i].g.bel) ++rshift;
         szh_ompb_rec &r = tab.rec[i];
         r.intervals = iv[i]; r.rshift = rshift; r.count_in_hist = form == 3 ? 1 : 0;
         hist_lds = std::max(hist_lds, ((size_t)iv[i] << rshift) * 4);
         o_hb[i] = hb_bytes; hb_bytes += nb * iv[i] * 4;
     }
     const int n_ent = (int)tab.list[OMPB_L_ENT].size();
+    std::vector<int> box_runs[2];                               // different shapes: where the runs of equal boxes end in the lists of forms 4 and 5
+    if (mixed) { box_runs[0] = ompb_box_runs(tab.list[OMPB_L_F4], sh); box_runs[1] = ompb_box_runs(tab.list[OMPB_L_F5], sh); }
     if (shared) { d_codes = (uint16_t *)ctx->codes_nat.p; d_hist = (unsigned *)ctx->hist.p; }
     std::vector<std::vector<unsigned char>> hdr((size_t)count);
     std::vector<std::vector<u64>> packed((size_t)count);
@@ -213,7 +297,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         const int n3g = (int)tab.list[OMPB_L_F3G].size();
         std::vector<unsigned char> pairs;
         if (n3g) {
-            const size_t stride = up16(n * sizeof(T));
+            const size_t stride = up16(r0 * r1 * r2 * sizeof(T));
             TRY(ensure(ctx, ctx->in, (size_t)n3g * stride));
             pairs.resize((size_t)n3g * 16);
             u64 *pp = (u64 *)pairs.data();
@@ -236,21 +320,49 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         }
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         const int n3 = (int)tab.list[OMPB_L_F3].size(), n4 = (int)tab.list[OMPB_L_F4].size(), n5 = (int)tab.list[OMPB_L_F5].size();
-        const int rows = g.c0 * g.c1;
-        const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
-        // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
-        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), 0);
-        if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), 0);
-        if (n4) hipLaunchKernelGGL((k_ompb_box<T, false, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
-        if (n5) hipLaunchKernelGGL((k_ompb_box<T, false, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        if (mixed) {
+            // the column form: ONE launch for every item with 32 x 32 faces; the box forms: one launch per distinct box (the block is its face, the LDS its ring)
+            if (n3) hipLaunchKernelGGL((k_ompbs_col<T, 32, 32, false, false>), dim3((unsigned)(ompb_most_boxes(tab.list[OMPB_L_F3], 0, n3, sh) / 2), (unsigned)n3), dim3(64), 0, st, tab.d_rec(),
+                                       tab.d_geo(), tab.d_list(OMPB_L_F3));
+            S.quant_kernel_launches += n3 ? 1 : 0;
+            for (int form = 4; form <= 5; ++form) {
+                const int which = form == 4 ? OMPB_L_F4 : OMPB_L_F5;
+                int from = 0;
+                for (int to : box_runs[form - 4]) {
+                    const szh_omp_geom &gb = sh[tab.list[which][from]].g;
+                    const dim3 grid((unsigned)ompb_most_boxes(tab.list[which], from, to, sh), (unsigned)(to - from)), block((unsigned)(gb.c0 * gb.c1));
+                    const size_t lds = (size_t)4 * gb.c0 * gb.pitch * sizeof(T);
+                    if (form == 4) hipLaunchKernelGGL((k_ompbs_box<T, false, true>), grid, block, lds, st, tab.d_rec(), tab.d_geo(), tab.d_list(which) + from);
+                    else hipLaunchKernelGGL((k_ompbs_box<T, false, false>), grid, block, lds, st, tab.d_rec(), tab.d_geo(), tab.d_list(which) + from);
+                    ++S.quant_kernel_launches;
+                    from = to;
+                }
+            }
+        } else {
+            const size_t nb = (size_t)g.nb;
+            const int rows = g.c0 * g.c1;
+            const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
+            // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
+            if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), 0);
+            if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, false, false>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), 0);
+            if (n4) hipLaunchKernelGGL((k_ompb_box<T, false, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
+            if (n5) hipLaunchKernelGGL((k_ompb_box<T, false, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
+            S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
         S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
         // ---- 4. the boxes' histograms and every array's own: one launch, one read-back
-        const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
-        hipLaunchKernelGGL(k_ompb_hist_box, dim3((unsigned)((nb + hist_per_wg - 1) / hist_per_wg), (unsigned)n_ent), dim3(256), hist_lds, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT),
-                           (int)nb, hist_per_wg);
+        if (mixed) {
+            int gx = 1;
+            for (int i : tab.list[OMPB_L_ENT]) gx = std::max(gx, ((int)sh[i].nb + tab.geo[i].per_wg - 1) / tab.geo[i].per_wg);
+            hipLaunchKernelGGL(k_ompbs_hist_box, dim3((unsigned)gx, (unsigned)n_ent), dim3(256), hist_lds, st, tab.d_rec(), tab.d_geo(), tab.d_list(OMPB_L_ENT));
+        } else {
+            const size_t nb = (size_t)g.nb;
+            const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
+            hipLaunchKernelGGL(k_ompb_hist_box, dim3((unsigned)((nb + hist_per_wg - 1) / hist_per_wg), (unsigned)n_ent), dim3(256), hist_lds, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT),
+                               (int)nb, hist_per_wg);
+        }
         HIPCHK(hipGetLastError());
         TRY(ensure_pinned(ctx, (size_t)count * 1024 * 4 + 64));
         HIPCHK(hipMemcpyAsync(ctx->pinned, d_hist, (size_t)count * 1024 * 4, hipMemcpyDeviceToHost, st));
@@ -266,6 +378,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
             if (!hf) { state[i] = FAILED; items[i].rc = SZHIP_ERR_INTERNAL; snprintf(ctx->err, sizeof(ctx->err), "Huffman build failed"); continue; }
             const size_t tree_bytes = szhost_huff_tree_size(hf.get());
             total_bits[i] = hf->total_bits;
+            const size_t nb = sh[i].nb;
             const size_t hdr_len = meta_len + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes;
             szh_ompb_rec &r = tab.rec[i];
             r.hdr_len = (unsigned)hdr_len; r.maxlen = (int)maxlen;
@@ -279,7 +392,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
             hdr[i].assign(hdr_len, 0);
             unsigned char *q = hdr[i].data();
             memcpy(q, items[i].meta, meta_len); q += meta_len;
-            szhost_put_u32be(q, (uint32_t)g.nb); q += 4;
+            szhost_put_u32be(q, (uint32_t)nb); q += 4;
             if (sizeof(T) == 8) szhost_put_f64be(q, (double)(T)items[i].eb); else szhost_put_f32be(q, (float)items[i].eb);
             q += sizeof(T);
             szhost_put_u32be(q, iv[i]); q += 4;
@@ -336,11 +449,19 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         HIPCHK(hipMemsetAsync(d_blob, 0, pos + 64, st));
         TRY(tab.upload(2, extra));
         // ---- 7. / 8. every box its size and place inside its own stream; every stream's tables and payloads
-        hipLaunchKernelGGL(k_ompb_layout, dim3(1, (unsigned)n_pack), dim3(1024), 0, st, (int)nb, tab.d_rec(), tab.d_list(OMPB_L_PACK));
-        HIPCHK(hipGetLastError());
         const int n_packd = (int)tab.list[OMPB_L_PACKD].size(), n_packg = (int)tab.list[OMPB_L_PACKG].size();
-        if (n_packd) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packd), dim3(256), lds3_max, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD));
-        if (n_packg) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packg), dim3(256), lds3_max, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG));
+        if (mixed) {
+            hipLaunchKernelGGL(k_ompbs_layout, dim3(1, (unsigned)n_pack), dim3(1024), 0, st, tab.d_rec(), tab.d_geo(), tab.d_list(OMPB_L_PACK));
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL((k_ompbs_encode_box3<T>), dim3((unsigned)ompb_most_boxes(tab.list[OMPB_L_PACKD], 0, n_packd, sh), (unsigned)n_packd), dim3(256), lds3_max, st, tab.d_rec(),
+                               tab.d_geo(), tab.d_list(OMPB_L_PACKD));
+        } else {
+            const size_t nb = (size_t)g.nb;
+            hipLaunchKernelGGL(k_ompb_layout, dim3(1, (unsigned)n_pack), dim3(1024), 0, st, (int)nb, tab.d_rec(), tab.d_list(OMPB_L_PACK));
+            HIPCHK(hipGetLastError());
+            if (n_packd) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packd), dim3(256), lds3_max, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD));
+            if (n_packg) hipLaunchKernelGGL((k_ompb_encode_box3<T>), dim3((unsigned)nb, (unsigned)n_packg), dim3(256), lds3_max, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG));
+        }
         HIPCHK(hipGetLastError());
         if (n_spans) {
             hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)n_spans), dim3(256), 0, st, d_blob, (const u64 *)(tab.dev() + tab.o_extra + o_spans));
@@ -358,7 +479,7 @@ int compress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, 
         for (int i : tab.list[OMPB_L_PACK]) {
             const u64 *t = h_tot + 4 * (size_t)i;
             const u64 bytes = (total_bits[i] + 7) / 8;
-            if (t[1] != E[i] || (unsigned)t[2] != 0 || t[0] < bytes || t[0] > bytes + (u64)nb || off_pay[i] + (size_t)t[0] > cap_len[i]) {
+            if (t[1] != E[i] || (unsigned)t[2] != 0 || t[0] < bytes || t[0] > bytes + (u64)sh[i].nb || off_pay[i] + (size_t)t[0] > cap_len[i]) {
                 state[i] = FAILED; items[i].rc = SZHIP_ERR_INTERNAL;
                 snprintf(ctx->err, sizeof(ctx->err), "OpenMP container: entropy stage mismatch in array %d of the batch", i);
                 continue;
@@ -409,12 +530,22 @@ struct ompb_stream {
 // pitch0 / pitch1: the element pitches of the arrays the items' sub-boxes lie in (szhip_decompress_omp_batch_view; r1 * r2 and r2: contiguous arrays).  The mirror of the
 // compress call: a device view is written where it lies through the pitched geometry, or (omp_view_packs) decoded contiguous in the context's output buffer and placed
 // by ONE k_ompb_view_scatter launch for all such items -- those whose boxes all decoded.  A host view is decoded contiguous and its rows are copied out.
+// `shapes` (or null): stream i decodes into a contiguous array of shapes[i] (szhip_decompress_omp_batch_shapes; r0 .. pitch1 are not looked at, and there are no views).
+// A stream is batched when the grid of ITS thread_num divides ITS shape; without `shapes` the first such stream's box count is the batch's, as before.
 template <class T>
-int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int stream_on_device, size_t r0, size_t r1, size_t r2, int out_on_device, size_t pitch0, size_t pitch1,
-                              szhip_stats *stats)
+int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count, int stream_on_device, const szhip_batch_shape *shapes, size_t r0, size_t r1, size_t r2,
+                              int out_on_device, size_t pitch0, size_t pitch1, szhip_stats *stats)
 {
     call_base cb(ctx); szhip_stats &S = cb.S; const hipStream_t st = cb.st;
-    const size_t n = r0 * r1 * r2;
+    const bool mixed = shapes != nullptr;
+    if (mixed) r0 = r1 = r2 = pitch0 = pitch1 = 0;
+    const size_t n = r0 * r1 * r2;                              // (one shape)
+    std::vector<ompb_shape> sh((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        ompb_shape &s = sh[i];
+        s.r0 = mixed ? shapes[i].r0 : r0; s.r1 = mixed ? shapes[i].r1 : r1; s.r2 = mixed ? shapes[i].r2 : r2;
+        s.n = s.r0 * s.r1 * s.r2; s.nb = 0; s.thread_num = 0; s.rc = SZHIP_OK;
+    }
     const bool any_view = pitch1 != r2 || pitch0 != r1 * r2, view = any_view && out_on_device;
     const host_view hv = {r1, r2 * sizeof(T), pitch0 * sizeof(T), pitch1 * sizeof(T)};
     enum { BATCH, SINGLE, FAILED };
@@ -501,12 +632,17 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         p.node_count = (int)szhost_get_u32be(q);
         if (p.intervals < 4 || p.intervals > 65536 || !(p.eb > 0)) { fail(i, "bad OpenMP-container header"); want[i] = 0; continue; }
         if (p.node_count <= 0 || p.tree_bytes > items[i].stream_len || szhost_huff_serial_size(p.node_count) > p.tree_bytes) { fail(i, "truncated stream"); want[i] = 0; continue; }
-        if (!have_g) {
+        if (mixed || !have_g) {                                 // (different shapes: every stream's own grid; one shape: the first stream's that divides it)
             szh_omp_geom gi;
-            if (p.thread_num >= 1 && omp_box_grid(ctx, p.thread_num, r0, r1, r2, &gi) == SZHIP_OK && gi.nb == p.thread_num) { g = gi; have_g = true; batch_threads = p.thread_num; }
+            if (p.thread_num >= 1 && omp_box_grid(ctx, p.thread_num, sh[i].r0, sh[i].r1, sh[i].r2, &gi) == SZHIP_OK && gi.nb == p.thread_num) {
+                sh[i].g = gi; sh[i].nb = (size_t)gi.nb; sh[i].thread_num = p.thread_num;
+                if (!have_g) { g = gi; have_g = true; batch_threads = p.thread_num; }
+            }
         }
-        if (!have_g || p.thread_num != batch_threads) { state[i] = SINGLE; want[i] = 0; continue; }      // (another grid, or none: the single call says what is wrong with it)
-        p.off_ucount = p.fixed + p.tree_bytes; p.off_first = p.off_ucount + (size_t)g.nb * 4; p.off_unpred = p.off_first + (size_t)g.nb * sizeof(T);
+        if (!mixed && have_g && p.thread_num == batch_threads) { sh[i].g = g; sh[i].nb = (size_t)g.nb; sh[i].thread_num = batch_threads; }
+        if (sh[i].nb == 0) { state[i] = SINGLE; want[i] = 0; continue; }      // (another grid, or none: the single call says what is wrong with it)
+        const size_t nb = sh[i].nb;
+        p.off_ucount = p.fixed + p.tree_bytes; p.off_first = p.off_ucount + nb * 4; p.off_unpred = p.off_first + nb * sizeof(T);
         if (p.off_unpred > items[i].stream_len) { fail(i, "truncated stream"); want[i] = 0; continue; }
         want[i] = p.off_unpred;
     }
@@ -515,12 +651,12 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         if (state[i] != BATCH) { want[i] = 0; continue; }
         ompb_stream<T> &p = ps[i];
         if (!read_tree(hs(i) + p.fixed, p.node_count, p.intervals, p.D)) { fail(i, "bad Huffman tree"); want[i] = 0; continue; }
-        p.uoff.assign((size_t)g.nb + 1, 0);
+        p.uoff.assign(sh[i].nb + 1, 0);
         bool ok = true;
-        for (int b = 0; b < g.nb; ++b) { uint32_t c; memcpy(&c, hs(i) + p.off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)g.bel) { ok = false; break; } p.uoff[b + 1] = p.uoff[b] + c; }
+        for (int b = 0; b < sh[i].g.nb; ++b) { uint32_t c; memcpy(&c, hs(i) + p.off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)sh[i].g.bel) { ok = false; break; } p.uoff[b + 1] = p.uoff[b] + c; }
         if (!ok) { fail(i, "bad verbatim-value count"); want[i] = 0; continue; }
-        p.E = p.uoff[g.nb];
-        p.off_sizes = p.off_unpred + (size_t)p.E * sizeof(T); p.off_pay = p.off_sizes + (size_t)g.nb * 8;
+        p.E = p.uoff[sh[i].g.nb];
+        p.off_sizes = p.off_unpred + (size_t)p.E * sizeof(T); p.off_pay = p.off_sizes + sh[i].nb * 8;
         if (p.off_pay > items[i].stream_len) { fail(i, "truncated stream"); want[i] = 0; continue; }
         want[i] = p.off_pay;
     }
@@ -532,10 +668,10 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     for (int i = 0; i < count; ++i) {
         if (state[i] != BATCH) continue;
         ompb_stream<T> &p = ps[i];
-        p.bbytes.resize((size_t)g.nb); p.boff.resize((size_t)g.nb);
-        memcpy(p.bbytes.data(), hs(i) + p.off_sizes, (size_t)g.nb * 8);
+        p.bbytes.resize(sh[i].nb); p.boff.resize(sh[i].nb);
+        memcpy(p.bbytes.data(), hs(i) + p.off_sizes, sh[i].nb * 8);
         u64 acc = 0; bool ok = true;
-        for (int b = 0; b < g.nb; ++b) { p.boff[b] = acc; if (p.bbytes[b] > items[i].stream_len || p.bbytes[b] >= ((u64)1 << 28)) { ok = false; break; } acc += p.bbytes[b]; p.max_box = std::max(p.max_box, p.bbytes[b]); }
+        for (int b = 0; b < sh[i].g.nb; ++b) { p.boff[b] = acc; if (p.bbytes[b] > items[i].stream_len || p.bbytes[b] >= ((u64)1 << 28)) { ok = false; break; } acc += p.bbytes[b]; p.max_box = std::max(p.max_box, p.bbytes[b]); }
         if (!ok) { fail(i, "bad payload size"); continue; }
         if (p.off_pay + acc > items[i].stream_len) { fail(i, "truncated stream"); continue; }
         // the look-up-table decoder's conditions (omp_dec::huffman_decode), for this stream alone
@@ -543,7 +679,7 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
         const int tab_lds = (size_t)p.D.n_nodes * 8 <= 13 * 1024;
         const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds ? ((size_t)p.D.n_nodes * 8 + 15) / 16 * 16 : 0);
-        if (!(p.D.single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024)) { state[i] = SINGLE; continue; }
+        if (!(p.D.single_symbol < 0 && sh[i].g.bel % 8 == 0 && lds_lut <= 64 * 1024)) { state[i] = SINGLE; continue; }
         stage_max = std::max<size_t>(stage_max, stage_bytes);
         if (tab_lds) tab_max = std::max(tab_max, ((size_t)p.D.n_nodes * 8 + 15) / 16 * 16);
     }
@@ -555,8 +691,17 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     if (lds_lut > 64 * 1024) for (int i = 0; i < count; ++i) if (state[i] == BATCH) state[i] = SINGLE;
     cb.host_ms += now_ms() - h0;
     // ---- the arrays of the shared launches: their places, forms, records
-    ompb_table tab(ctx, count);
-    const size_t out_stride = up16(n * sizeof(T));
+    ompb_table tab(ctx, count, mixed);
+    // where item i's work arrays lie: its decoded copy (a host array, a gathered view), codes, first values, flag words -- behind those of the items before it, each
+    // at the alignment the single call gives it (a stream of the single call in front takes its places too: an odd length there shifts nobody off a boundary)
+    std::vector<size_t> o_out((size_t)count + 1, 0), o_code((size_t)count + 1, 0), o_first((size_t)count + 1, 0), o_flag((size_t)count + 1, 0);
+    std::vector<int> fws((size_t)count, 0);
+    auto flag_words = [](const szh_omp_geom &gi) { const int w = (gi.c0 * gi.c1 / (16 / (int)sizeof(T)) + 31) / 32; return w > OC_FLAG_WORDS ? 0 : w; };
+    for (int i = 0; i < count; ++i) {
+        if (sh[i].nb) fws[i] = flag_words(sh[i].g);
+        o_out[i + 1] = o_out[i] + up16(sh[i].n * sizeof(T)); o_code[i + 1] = o_code[i] + (sh[i].n + 7) / 8 * 8;
+        o_first[i + 1] = o_first[i] + up16(sh[i].nb * sizeof(T)); o_flag[i + 1] = o_flag[i] + sh[i].nb * (size_t)fws[i];
+    }
     szh_omp_geom gv = g;                                        // the geometry of the items that are written where they lie
     std::vector<char> gathered((size_t)count, 0);
     bool any_gathered = false;
@@ -564,25 +709,27 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         omp_view_pitches(&gv, pitch0, pitch1, sizeof(T));
         for (int i = 0; i < count; ++i) if (state[i] == BATCH && omp_view_packs(g, items[i].out, pitch0, pitch1, sizeof(T))) { gathered[i] = 1; any_gathered = true; }
     }
-    if (!out_on_device || any_gathered) TRY(ensure(ctx, ctx->out, (size_t)count * out_stride));
-    const size_t fp0 = view ? pitch0 : r1 * r2, fp1 = view ? pitch1 : r2;      // (what omp_form looks at)
+    if (!out_on_device || any_gathered) TRY(ensure(ctx, ctx->out, o_out[count]));
     size_t ex = 0, un_bytes = 0;
     std::vector<size_t> o_ex((size_t)count, 0), o_un((size_t)count, 0);
-    int fw = 0;
-    const size_t nb = have_g ? (size_t)g.nb : 0;
-    if (have_g) { TRY(ompb_limits(ctx, count, nb, n)); fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32; if (fw > OC_FLAG_WORDS) fw = 0; }
-    const size_t first_bytes = up16((size_t)count * nb * sizeof(T));
+    size_t sum_n = 0, sum_nb = 0;                               // (one shape: every stream counts with the batch's box count, as before)
+    for (int i = 0; i < count; ++i) { sum_n += sh[i].n; sum_nb += mixed ? sh[i].nb : have_g ? (size_t)g.nb : 0; }
+    const int fw = have_g && !mixed ? flag_words(g) : 0;       // (one shape: the flag words of the batch's grid)
+    if (have_g) TRY(ompb_limits(ctx, count, sum_nb, sum_n));
+    const size_t first_bytes = o_first[count];
     for (int i = 0; i < count; ++i) {
         if (state[i] != BATCH) continue;
         ompb_stream<T> &p = ps[i];
+        const size_t nb = sh[i].nb;
         tab.list[OMPB_L_ENT].push_back(i);
         o_ex[i] = ex;
         ex += up64(p.D.dtab.size() * 4) + SZH_LUT_BYTES + 64 + up16(nb * 8) * 2 + up16((nb + 1) * 8);
         o_un[i] = first_bytes + un_bytes; un_bytes += up16((size_t)p.E * sizeof(T));
         S.n_unpred += p.E; items[i].intervals = p.intervals; items[i].n_unpred = p.E; items[i].batched = 1;
+        if (mixed) { tab.geo[i].g = sh[i].g; tab.geo[i].fw = fws[i]; }
     }
     const int n_ent = (int)tab.list[OMPB_L_ENT].size();
-    S.n_elements = (uint64_t)count * n; S.n_blocks = (uint64_t)count * nb;
+    S.n_elements = (uint64_t)sum_n; S.n_blocks = (uint64_t)sum_nb;
     const u64 *h_tot = nullptr;
     if (n_ent > 0) {
         const size_t o_spans = ex;
@@ -590,10 +737,10 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         const size_t o_pairs = ex;                              // (the pairs {view, contiguous copy} of the final scatter: uploaded when it is known which items decoded)
         if (any_gathered) ex += (size_t)count * 16;
         TRY(tab.reserve(ex));
-        TRY(ensure(ctx, ctx->codes_nat, (size_t)count * n * 2 + 64));
+        TRY(ensure(ctx, ctx->codes_nat, o_code[count] * 2 + 64));
         TRY(ensure(ctx, ctx->unpred, first_bytes + un_bytes + 16));
         bool any_flags = false;
-        if (fw > 0) TRY(ensure(ctx, ctx->chunk_bits, (size_t)count * nb * fw * 4));
+        if (o_flag[count] > 0) TRY(ensure(ctx, ctx->chunk_bits, o_flag[count] * 4));
         std::vector<unsigned char> extra(ex, 0);
         u64 *sp = (u64 *)(extra.data() + o_spans);
         int n_spans = 0;
@@ -601,6 +748,7 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         for (int i : tab.list[OMPB_L_ENT]) {
             ompb_stream<T> &p = ps[i];
             szh_ompb_rec &r = tab.rec[i];
+            const size_t nb = sh[i].nb;
             unsigned char *dx = tab.dev() + tab.o_extra + o_ex[i], *hx = extra.data() + o_ex[i];
             size_t o = 0;
             memcpy(hx, p.D.dtab.data(), p.D.dtab.size() * 4); r.table = (const unsigned *)dx; o = up64(p.D.dtab.size() * 4);
@@ -608,33 +756,39 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
             memcpy(hx + o, p.bbytes.data(), nb * 8); r.box_bytes = (u64 *)(dx + o); o += up16(nb * 8);
             memcpy(hx + o, p.boff.data(), nb * 8); r.box_off = (u64 *)(dx + o); o += up16(nb * 8);
             memcpy(hx + o, p.uoff.data(), (nb + 1) * 8); r.uoff = (u64 *)(dx + o);
-            r.out = out_on_device && !gathered[i] ? items[i].out : (void *)((char *)ctx->out.p + (size_t)i * out_stride);
+            r.out = out_on_device && !gathered[i] ? items[i].out : (void *)((char *)ctx->out.p + o_out[i]);
             r.eb = (double)p.eb; r.recip = (double)(T)(1 / p.eb); r.intervals = p.intervals;
-            r.codes = (uint16_t *)ctx->codes_nat.p + (size_t)i * n;
-            r.first = d_un + (size_t)i * nb * sizeof(T); r.unpred = d_un + o_un[i];
+            r.codes = (uint16_t *)ctx->codes_nat.p + o_code[i];
+            r.first = d_un + o_first[i]; r.unpred = d_un + o_un[i];
             r.totals = tab.totals(i);
             r.payload = d_streams + p.pos + p.off_pay; r.bytes_before = (unsigned)std::min<size_t>(p.pos + p.off_pay, 0x7fffffffu);
             r.n_nodes = p.D.n_nodes; r.tab_lds = tabs_in_lds && (size_t)p.D.n_nodes * 8 <= 13 * 1024 ? 1 : 0;
-            const int form = gathered[i] ? 3 : omp_form(gv, r.out, sizeof(T), fp0, fp1);
+            const size_t fp0 = view ? pitch0 : sh[i].r1 * sh[i].r2, fp1 = view ? pitch1 : sh[i].r2;      // (what omp_form looks at)
+            const int form = gathered[i] ? 3 : omp_form(mixed ? sh[i].g : gv, r.out, sizeof(T), fp0, fp1);
             items[i].quant_kernel = form;
             tab.list[gathered[i] ? OMPB_L_F3G : form == 3 ? OMPB_L_F3 : form == 4 ? OMPB_L_F4 : OMPB_L_F5].push_back(i);
             if (form == 3 && p.E > 0) {
                 tab.list[gathered[i] ? OMPB_L_PACKG : OMPB_L_PACKD].push_back(i);      // (here: the arrays k_omp_scatter runs for)
-                if (fw > 0) { r.vflags = (unsigned *)ctx->chunk_bits.p + (size_t)i * nb * fw; any_flags = true; }
+                if (fws[i] > 0) { r.vflags = (unsigned *)ctx->chunk_bits.p + o_flag[i]; any_flags = true; }
             }
             // the first values and the verbatim values to aligned addresses (omp_dec::decode_boxes copies them out of the stream one by one)
-            *sp++ = (u64)(uintptr_t)(d_streams + p.pos + p.off_first); *sp++ = (u64)((size_t)i * nb * sizeof(T)); *sp++ = (u64)(nb * sizeof(T)); ++n_spans;
+            *sp++ = (u64)(uintptr_t)(d_streams + p.pos + p.off_first); *sp++ = (u64)o_first[i]; *sp++ = (u64)(nb * sizeof(T)); ++n_spans;
             if (p.E > 0) { *sp++ = (u64)(uintptr_t)(d_streams + p.pos + p.off_unpred); *sp++ = (u64)o_un[i]; *sp++ = (u64)p.E * sizeof(T); ++n_spans; }
         }
         // ---- 3. one upload; 4. / 5. the look-up tables, the Huffman decode
         TRY(tab.clear_totals());
-        if (any_flags) HIPCHK(hipMemsetAsync(ctx->chunk_bits.p, 0, (size_t)count * nb * fw * 4, st));
+        if (any_flags) HIPCHK(hipMemsetAsync(ctx->chunk_bits.p, 0, o_flag[count] * 4, st));
+        std::vector<int> box_runs[2];                           // different shapes: where the runs of equal boxes end in the lists of forms 4 and 5
+        if (mixed) { box_runs[0] = ompb_box_runs(tab.list[OMPB_L_F4], sh); box_runs[1] = ompb_box_runs(tab.list[OMPB_L_F5], sh); }
         TRY(tab.upload(0, extra));
         hipLaunchKernelGGL(k_ompb_fetch, dim3((unsigned)n_spans), dim3(256), 0, st, d_un, (const u64 *)(tab.dev() + tab.o_extra + o_spans));
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_ompb_build_lut, dim3(SZH_LUT_SIZE / 256, (unsigned)n_ent), dim3(256), 0, st, tab.d_rec(), tab.d_list(OMPB_L_ENT));
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_ompb_hdec_lut, dim3((unsigned)nb, (unsigned)n_ent), dim3(256), lds_lut, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT), (unsigned)stage_max);
+        const size_t nb = have_g ? (size_t)g.nb : 0;           // (one shape: the batch's box count)
+        if (mixed) hipLaunchKernelGGL(k_ompbs_hdec_lut, dim3((unsigned)ompb_most_boxes(tab.list[OMPB_L_ENT], 0, n_ent, sh), (unsigned)n_ent), dim3(256), lds_lut, st, tab.d_rec(), tab.d_geo(),
+                                      tab.d_list(OMPB_L_ENT), (unsigned)stage_max);
+        else hipLaunchKernelGGL(k_ompb_hdec_lut, dim3((unsigned)nb, (unsigned)n_ent), dim3(256), lds_lut, st, g.bel, tab.d_rec(), tab.d_list(OMPB_L_ENT), (unsigned)stage_max);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[1], st));
         // ---- 6. the verbatim values of the column-form arrays to their places, one sweep launch per form
@@ -643,16 +797,37 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         const int n3g = (int)tab.list[OMPB_L_F3G].size(), nsg = (int)tab.list[OMPB_L_PACKG].size();
         const int rows = g.c0 * g.c1;
         const size_t box_lds = (size_t)4 * g.c0 * g.pitch * sizeof(T);
-        // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
-        if (ns) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)ns), dim3(256), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD), fw);
-        if (nsg) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)nsg), dim3(256), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG), fw);
-        if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), fw);
-        if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), fw);
-        if (n4) hipLaunchKernelGGL((k_ompb_box<T, true, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
-        if (n5) hipLaunchKernelGGL((k_ompb_box<T, true, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
+        if (mixed) {                                          // (as in the compress call: one column launch, one box launch per distinct box of a form)
+            if (ns) hipLaunchKernelGGL((k_ompbs_scatter<T>), dim3((unsigned)ompb_most_boxes(tab.list[OMPB_L_PACKD], 0, ns, sh), (unsigned)ns), dim3(256), 0, st, tab.d_rec(), tab.d_geo(),
+                                       tab.d_list(OMPB_L_PACKD));
+            if (n3) hipLaunchKernelGGL((k_ompbs_col<T, 32, 32, true, true>), dim3((unsigned)(ompb_most_boxes(tab.list[OMPB_L_F3], 0, n3, sh) / 2), (unsigned)n3), dim3(64), 0, st, tab.d_rec(),
+                                       tab.d_geo(), tab.d_list(OMPB_L_F3));
+            S.quant_kernel_launches += n3 ? 1 : 0;
+            for (int form = 4; form <= 5; ++form) {
+                const int which = form == 4 ? OMPB_L_F4 : OMPB_L_F5;
+                int from = 0;
+                for (int to : box_runs[form - 4]) {
+                    const szh_omp_geom &gb = sh[tab.list[which][from]].g;
+                    const dim3 grid((unsigned)ompb_most_boxes(tab.list[which], from, to, sh), (unsigned)(to - from)), block((unsigned)(gb.c0 * gb.c1));
+                    const size_t lds = (size_t)4 * gb.c0 * gb.pitch * sizeof(T);
+                    if (form == 4) hipLaunchKernelGGL((k_ompbs_box<T, true, true>), grid, block, lds, st, tab.d_rec(), tab.d_geo(), tab.d_list(which) + from);
+                    else hipLaunchKernelGGL((k_ompbs_box<T, true, false>), grid, block, lds, st, tab.d_rec(), tab.d_geo(), tab.d_list(which) + from);
+                    ++S.quant_kernel_launches;
+                    from = to;
+                }
+            }
+        } else {
+            // (`gv`: the items where they lie -- `g` itself in a contiguous call; `g`: the contiguous copies of the gathered views)
+            if (ns) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)ns), dim3(256), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_PACKD), fw);
+            if (nsg) hipLaunchKernelGGL((k_ompb_scatter<T>), dim3((unsigned)nb, (unsigned)nsg), dim3(256), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_PACKG), fw);
+            if (n3) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3), dim3(64), 0, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F3), fw);
+            if (n3g) hipLaunchKernelGGL((k_ompb_col<T, 32, 32, true, true>), dim3((unsigned)(nb / 2), (unsigned)n3g), dim3(64), 0, st, g, tab.d_rec(), tab.d_list(OMPB_L_F3G), fw);
+            if (n4) hipLaunchKernelGGL((k_ompb_box<T, true, true>), dim3((unsigned)nb, (unsigned)n4), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F4));
+            if (n5) hipLaunchKernelGGL((k_ompb_box<T, true, false>), dim3((unsigned)nb, (unsigned)n5), dim3((unsigned)rows), box_lds, st, gv, tab.d_rec(), tab.d_list(OMPB_L_F5));
+            S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
-        S.quant_kernel_launches += (n3 ? 1 : 0) + (n3g ? 1 : 0) + (n4 ? 1 : 0) + (n5 ? 1 : 0);
         S.quant_kernel = items[tab.list[OMPB_L_ENT][0]].quant_kernel;
         // ---- 7. the arrays' error counts
         TRY(ensure_pinned(ctx, (size_t)count * 32));
@@ -664,12 +839,12 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
         hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); S.ms_quant = ms;
         for (int i : tab.list[OMPB_L_ENT]) if ((unsigned)h_tot[4 * (size_t)i + 2] != 0) fail(i, "boxes whose payload or verbatim-value count does not fit their codes");
         if (!out_on_device) {                                 // the decoded arrays to the callers' host arrays: one copy down, then those of the streams that decoded
-            std::vector<unsigned char> tmp((size_t)count * out_stride);
+            std::vector<unsigned char> tmp(o_out[count]);
             TRY(staged_copy(ctx, tmp.data(), ctx->out.p, tmp.size(), false));
             for (int i : tab.list[OMPB_L_ENT]) {
                 if (state[i] != BATCH) continue;
-                if (any_view) host_view_move(hv, (char *)items[i].out, (char *)tmp.data() + (size_t)i * out_stride, 0, n * sizeof(T), false);      // (the sub-box's rows alone)
-                else memcpy(items[i].out, tmp.data() + (size_t)i * out_stride, n * sizeof(T));
+                if (any_view) host_view_move(hv, (char *)items[i].out, (char *)tmp.data() + o_out[i], 0, n * sizeof(T), false);      // (the sub-box's rows alone)
+                else memcpy(items[i].out, tmp.data() + o_out[i], sh[i].n * sizeof(T));
             }
         }
         if (n3g) {                                            // the gathered views that decoded: their contiguous copies into the callers' arrays, ONE scatter launch
@@ -692,7 +867,7 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     for (int i = 0; i < count; ++i) {
         if (state[i] != SINGLE) continue;
         szhip_stats s1; memset(&s1, 0, sizeof(s1));
-        const int rc = decompress_omp_impl<T>(ctx, items[i].stream, stream_on_device, items[i].stream_len, items[i].body_off, r0, r1, r2, items[i].out, out_on_device,
+        const int rc = decompress_omp_impl<T>(ctx, items[i].stream, stream_on_device, items[i].stream_len, items[i].body_off, sh[i].r0, sh[i].r1, sh[i].r2, items[i].out, out_on_device,
                                                any_view ? pitch0 : 0, any_view ? pitch1 : 0, &s1);
         items[i].rc = rc; items[i].batched = 0;
         if (rc != SZHIP_OK) { hipStreamSynchronize(st); continue; }
@@ -701,7 +876,7 @@ int decompress_omp_batch_impl(szhip_ctx *ctx, szhip_batch_item *items, int count
     }
     int rc_all = SZHIP_OK;
     for (int i = 0; i < count; ++i) if (items[i].rc != SZHIP_OK && rc_all == SZHIP_OK) rc_all = items[i].rc;
-    S.out_bytes = (uint64_t)count * n * sizeof(T);
+    S.out_bytes = (uint64_t)sum_n * sizeof(T);
     S.ms_host = cb.host_ms; S.ms_total = now_ms() - cb.t_begin;
     if (stats) *stats = S;
     return rc_all;
