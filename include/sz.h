@@ -319,7 +319,7 @@ void SZ_hip_print_quality(const struct szhip_quality *q, size_t cmp_bytes, int i
  * szhip_compress_omp_batch_shapes; the decode puts every marked container, whatever its box count, through one szhip_decompress_omp_batch_shapes.  An item of at most
  * 20 values, with an extent below 2 or without a box grid takes SZ_compress_args' ordinary path from inside the call (batched[i] = 0) instead of refusing it; the
  * refusals of the whole call are otherwise those above, and an extent of 0 or an array of 2^32 values or more.
- * Not covered: the lossless stage, point-wise relative modes, the slab container, arrays of different shapes that are sub-boxes, of different types or not 3-D, the
+ * Not covered: the lossless stage, point-wise relative modes, the slab container, compressing arrays of different shapes that are sub-boxes (decoding sub-boxes of streams of any shapes: SZ_hip_decompress_batch_regions below), arrays of different types or not 3-D, the
  * error report over pairs of different lengths (SZ_hip_compare_batch is element-wise: group the pairs by shape); sub-boxes of one shape: the three *_region calls below. */
 int SZ_hip_compress_args_batch(int dataType, int count, const void *const *data, int data_on_device, int errBoundMode, double absErrBound, double relBoundRatio,
                                size_t r1, size_t r2, size_t r3, unsigned char **streams, size_t *comp_sizes, int *batched);
@@ -331,6 +331,21 @@ int SZ_hip_decompress_batch_shapes(int dataType, int count, unsigned char *const
                                    const size_t *dims);
 int SZ_hip_compare_batch(int dataType, int count, const void *const *ori, const void *const *dec, int on_device, size_t r1, size_t r2, size_t r3,
                          const double *absBound, const double *pwRelBound, int flags, struct szhip_quality *out);
+/* SUB-BOXES OF MANY STREAMS in one call: SZ_hip_decompress_region per item, into destinations that may be views -- the faces of neighbouring
+ * patches into ghost layers, slices through a level.  Item i: the host stream bytes[i] of byteLengths[i] bytes of an array of dims[3 i .. 3 i + 2] = r1, r2, r3 values
+ * (laid out as in SZ_hip_decompress_batch_shapes), its sub-box start[3 i ..] / end[3 i ..] (the dimension order of SZ_hip_decompress_region: slowest first, end
+ * exclusive), and the destination out[i] (host, or device with out_on_device; aligned to its element): contiguous when out_pitches is NULL, else with the two ELEMENT
+ * pitches out_pitches[2 i] (between planes) and out_pitches[2 i + 1] (between rows) of szhip.h's views.  The destination sub-box receives bit for bit that part of what
+ * SZ_decompress returns for the stream, and no other byte of the destination's allocation is written.
+ * Marked containers -- what SZ_compress_args writes under SZ_HIP_MODE=omp and the SZ_hip_compress_args_batch* calls write -- go through ONE
+ * szhip_decompress_omp_batch_region: only the boxes the regions meet are decoded, several regions of one stream (the same bytes[i]) share its header work, and the
+ * number of launches and synchronisations does not grow with `count`.  A constant stream (the batch compress calls write them for constant patches) fills its region
+ * with the value SZ_decompress gives.  A stream wrapped by the zstd or gzip stage is unwrapped WHOLE first.  Every other stream (SZ 2.1, SZ 1.4, point-wise relative,
+ * raw, not 3-D) is refused for that item alone with the printed reason of SZ_hip_decompress_region: the others are delivered and the call returns SZ_NSCS.
+ * SZ_NSCS with nothing written: null arguments, a type other than float or double, an empty or out-of-range box, pitches below the region's extents.
+ * Not covered: device-resident streams (szhip_decompress_omp_batch_region takes them), a type per item, the slab container. */
+int SZ_hip_decompress_batch_regions(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, const size_t *dims, const size_t *start,
+                                    const size_t *end, void *const *out, int out_on_device, const size_t *out_pitches);
 /* ---- the three calls above on ONE BOX [start, end) common to `count` 3-D parents of r1 x r2 x r3 values (r1 slowest; start / end as in SZ_hip_compress_region): the
  * interiors of patches with ghost layers.  parents[i] points at parent i's first value; the ghost cells are neither read into a stream or a
  * range nor written.

@@ -254,7 +254,8 @@ int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *
  * Costs (MI355X, 512^3 float32, device-resident): the direct calls on an aligned view 1.04 x / 1.03 x the contiguous calls and 0.85 x / 0.83 x pack + compress /
  * decompress + scatter; packing 0.15 ms, scattering 0.24 ms; SZ 2.1 from a view 1.11 x the contiguous call.
  * Many views of one shape in one call: szhip_compress_omp_batch_view / szhip_decompress_omp_batch_view, szhip_minmax_batch_view, szhip_compare_batch_view (below).
- * Not covered: a strided single-array szhip_minmax (szhip_minmax_batch_view with count 1 serves), region decode into a view, the slab container.
+ * Sub-boxes of many streams into views in one call: szhip_decompress_omp_batch_region (below; count 1 is region decode into a view).
+ * Not covered: a strided single-array szhip_minmax (szhip_minmax_batch_view with count 1 serves), the slab container.
  */
 int szhip_compress_omp_view(szhip_ctx *ctx, int dtype, const void *data, int data_on_device, size_t r0, size_t r1, size_t r2, size_t pitch0, size_t pitch1,
                             double eb, int thread_num, const szhip_params *params, const unsigned char *meta, size_t meta_len,
@@ -361,7 +362,7 @@ int szhip_decompress_omp_batch_view(szhip_ctx *ctx, int dtype, szhip_batch_item 
  * Errors: per-item rc as above.  An item whose shape the single call refuses (no dividing grid, a box face above 1024 rows) gets that rc and an empty stream; the rest
  * proceed.  SZHIP_ERR_ARG before anything is launched or written: count < 1, null `shapes`, an extent of 0 or above 2^31 - 1, thread_num < 1 (compress), and the
  * same-shape call's refusals.  SZHIP_ERR_UNSUP beyond: count <= 65535, boxes of all items <= 2^22, values of all items < 2^32.
- * Not covered: views (per-item pitches), mixed dtypes, items that are not 3-D, szhip_compare_batch on pairs of different lengths (it is element-wise: group by length).
+ * Not covered: compress from / full decode into views with per-item pitches (sub-boxes of streams into such views: szhip_decompress_omp_batch_region), mixed dtypes, items that are not 3-D, szhip_compare_batch on pairs of different lengths (it is element-wise: group by length).
  */
 typedef struct szhip_batch_shape { size_t r0, r1, r2; int thread_num; } szhip_batch_shape;
 int szhip_compress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, int count, int data_on_device,
@@ -373,6 +374,46 @@ int szhip_decompress_omp_batch_shapes(szhip_ctx *ctx, int dtype, szhip_batch_ite
  * boundary is accepted.  Limits: count <= 65535, fewer than 2^32 values in all. */
 int szhip_minmax_batch_lens(szhip_ctx *ctx, int dtype, const void *const *data, const size_t *lens, int count, int data_on_device, double *vmin, double *vmax,
                             szhip_stats *stats);
+/*
+ * SUB-BOXES OF MANY STREAMS in one call: the faces of neighbouring patches that fill ghost layers, slices through a level, the boxes a probe
+ * touches.  szhip_decompress_omp_region per item, with the per-call costs of szhip_decompress_omp_batch_shapes: item i names an OpenMP-container stream (items[i].stream,
+ * stream_len, body_off) of an array of shapes[i].r0 x r1 x r2 values -- the box count is read from the stream, shapes[i].thread_num is ignored --, the sub-box
+ * [regions[i].lo, regions[i].hi) of it (dim 0 slowest, hi exclusive) and a destination items[i].out (host or device, aligned to its element) with the two ELEMENT
+ * pitches of the VIEWS above (pitch1 >= hi[2] - lo[2], pitch0 >= (hi[1] - lo[1]) * pitch1, pitch0 need not be a multiple of pitch1; 0, 0: contiguous).
+ * The bar: the destination sub-box receives bit for bit the crop [lo, hi) of what szhip_decompress_omp writes for that stream -- NaN payloads and signed zeros
+ * included; what szhip_decompress_omp_region returns --, and NO other byte of any destination allocation is written: not between rows or planes, not in front or
+ * behind, not in ghost cells outside the sub-box.  Destinations are never read, streams never written.  Destinations of different items that overlap: undefined.
+ * Work: launches, synchronisations and copies grow with the number of KINDS of item, not with `count`.  Every item's "array" is the sub-array of the boxes its region
+ * meets: compact tables in sub-grid order and a sub-geometry per item, the k_ompbs_* launches of the different-shapes call over them.  The covered boxes' first values,
+ * verbatim values and payloads are fetched by ONE gather launch over all items' spans (device streams) or go up as ONE pinned blob (host streams); whole streams are
+ * not copied, and only header prefixes and tables reach the host.  Every item is swept into a staging array in the context -- form per item by the single region call's
+ * rule on the sub-geometry: the column form (3) needs 32 x 32 faces and an even covered-box count, anything else a box form (4 / 5); one sweep launch per distinct
+ * (form, box c0 x c1 x c2) --, and ONE placing launch (k_ompbr_place; stats->packing = 1) puts every region into its destination: 16 bytes per lane between the
+ * 16-byte boundaries of each destination row, a value-by-value head and tail, no read of the destination.  The placing launch reads the sweeps' error counts on the
+ * device: no synchronisation lies in front of it, and an item that fails leaves its destination untouched.  A host destination is placed contiguous into a device buffer
+ * by the same launch and its rows are copied out through the pitches; of a failed item nothing is copied.
+ * Items with the same (stream, stream_len, body_off) and shape share one header read, one table walk, one tree, one node table and one look-up-table build;
+ * regions[i].shares is the first such item.  Host header work and header fetches grow with the number of DISTINCT streams.
+ * Fallbacks PER ITEM (items[i].batched = 0, the rest stays batched; szhip_decompress_omp_region from inside the call, a view placed behind it): a one-symbol book, box
+ * points that are no multiple of 8, covered payloads plus tables beyond a workgroup's LDS, a stream whose grid does not divide its shape (the single call says what is
+ * wrong with it).
+ * Errors: per-item rc, the call returns the first non-zero one.  SZHIP_ERR_STREAM is found on the host in headers and tables and on the device in the payloads and
+ * verbatim-value counts of COVERED boxes only; boxes no region touches are not validated.  A failed item disturbs no other item -- not another region of the same
+ * stream whose boxes are sound.  SZHIP_ERR_ARG before anything is launched or written: count < 1; null shapes, regions, stream or out; a misaligned out; lo[d] >= hi[d]
+ * or hi[d] beyond the extent; pitches that break the view rule.  SZHIP_ERR_UNSUP beyond: count <= 65535, covered boxes of all items <= 2^22, staged values (covered
+ * boxes x box points) of all items < 2^32.
+ * stats: n_elements the values delivered, n_blocks the boxes decoded, n_unpred their verbatim values (the sums of what szhip_decompress_omp_region reports per item);
+ * quant_kernel_launches the sweep launches, packing the placing launches (0 or 1); items[i].quant_kernel / intervals / n_unpred per item.
+ * Not covered: a direct form (the sweeps writing straight into a destination whose region ends on box boundaries -- every item goes through the staging array), a dtype per item.
+ */
+typedef struct szhip_batch_region {
+    /* in  */ size_t lo[3], hi[3];      /* the sub-box of THIS item's array, dim 0 slowest, hi exclusive */
+              size_t pitch0, pitch1;    /* element pitches of the destination; 0, 0: contiguous (hi-lo extents) */
+    /* out */ uint64_t n_boxes;         /* boxes decoded for this item */
+              int shares;               /* index of the first item that names the same stream (i itself otherwise) */
+} szhip_batch_region;
+int szhip_decompress_omp_batch_region(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, szhip_batch_region *regions, int count,
+                                      int stream_on_device, int out_on_device, szhip_stats *stats);
 
 /*
  * Point-wise relative bounds (PW_REL and its AND/OR combinations) in their log-domain form: the `_pwr_pre_log` functions of

@@ -18,5 +18,5 @@ from .api import (  # noqa: F401
     szhip_quality, Quality, SZHIP_Q_CORR, NO_INDEX, SZ_hip_compare, SZ_hip_compare_device, SZ_hip_print_quality,
     SZ_hip_compress_args_batch, SZ_hip_decompress_batch, SZ_hip_compare_batch,
     SZ_hip_compress_args_batch_region, SZ_hip_decompress_batch_into_region, SZ_hip_compare_batch_region,
-    SZ_hip_compress_args_batch_shapes, SZ_hip_decompress_batch_shapes,
+    SZ_hip_compress_args_batch_shapes, SZ_hip_decompress_batch_shapes, SZ_hip_decompress_batch_regions,
 )

@@ -66,6 +66,11 @@ class szhip_batch_shape(ctypes.Structure):  # include/szhip.h: the shape (dim 0 
     _fields_ = [("r0", ctypes.c_size_t), ("r1", ctypes.c_size_t), ("r2", ctypes.c_size_t), ("thread_num", ctypes.c_int)]
 
 
+class szhip_batch_region(ctypes.Structure):  # include/szhip.h: the sub-box and destination pitches of one item of szhip_decompress_omp_batch_region
+    _fields_ = [("lo", ctypes.c_size_t * 3), ("hi", ctypes.c_size_t * 3), ("pitch0", ctypes.c_size_t), ("pitch1", ctypes.c_size_t),
+                ("n_boxes", ctypes.c_uint64), ("shares", ctypes.c_int)]
+
+
 class szhip_book_record(ctypes.Structure):  # include/szhip.h
     _fields_ = [("n_nodes", ctypes.c_uint32), ("tree_bytes", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("status", ctypes.c_uint32),
                 ("total_bits", ctypes.c_uint64), ("total_unpred", ctypes.c_uint64)]
@@ -206,6 +211,13 @@ def _bind(L):
         L.szhip_minmax_batch_lens.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(szhip_stats)]
         L.szhip_minmax_batch_lens.restype = ctypes.c_int
+    if hasattr(L, "szhip_decompress_omp_batch_region"):
+        L.szhip_decompress_omp_batch_region.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(szhip_batch_item), ctypes.POINTER(szhip_batch_shape),
+                                                        ctypes.POINTER(szhip_batch_region), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(szhip_stats)]
+        L.szhip_decompress_omp_batch_region.restype = ctypes.c_int
+        L.SZ_hip_decompress_batch_regions.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                                      ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(sz)]
+        L.SZ_hip_decompress_batch_regions.restype = ctypes.c_int
     if hasattr(L, "SZ_hip_compress_args_batch_shapes"):
         L.SZ_hip_compress_args_batch_shapes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                                         ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]
@@ -593,6 +605,27 @@ def SZ_hip_decompress_batch_shapes(streams, out_ptrs, out_on_device, shapes, dty
     return rc
 
 
+def SZ_hip_decompress_batch_regions(streams, shapes, los, his, out_ptrs, out_on_device, dtype, pitches=None, raise_on_error=True):
+    """include/sz.h: the sub-box [los[i], his[i]) of the array of shapes[i] = (r1, r2, r3) in streams[i] (bytes; the SAME bytes object given twice is one stream) into
+    out_ptrs[i] (host, or device with out_on_device); pitches: None (contiguous destinations) or pitches[i] = (pitch0, pitch1) in elements.  Returns rc: SZ_NSCS when
+    any item failed (the others are delivered)."""
+    dt = SZ_FLOAT if np.dtype(dtype) == np.float32 else SZ_DOUBLE
+    count = len(streams)
+    keep = {}
+    for s in streams:
+        if id(s) not in keep:
+            keep[id(s)] = ctypes.create_string_buffer(bytes(s), len(s))
+    c_streams = (ctypes.c_void_p * max(count, 1))(*[ctypes.addressof(keep[id(s)]) for s in streams])
+    c_sizes = (ctypes.c_size_t * max(count, 1))(*[len(s) for s in streams])
+    c_out = (ctypes.c_void_p * max(count, 1))(*out_ptrs)
+    flat = lambda rows, k: (ctypes.c_size_t * max(k * count, k))(*[int(v) for r in rows for v in r])
+    c_pitches = flat(pitches, 2) if pitches is not None else None
+    rc = lib().SZ_hip_decompress_batch_regions(dt, count, c_streams, c_sizes, flat(shapes, 3), flat(los, 3), flat(his, 3), c_out, 1 if out_on_device else 0, c_pitches)
+    if rc != SZ_SCES and raise_on_error:
+        raise SZError(f"SZ_hip_decompress_batch_regions failed ({rc})")
+    return rc
+
+
 def SZ_hip_compare_batch(ori_ptrs, dec_ptrs, on_device, shape, dtype, absBounds, pwRelBounds=None, corr=False):
     """include/sz.h: `len(ori_ptrs)` pairs of arrays of `shape` / `dtype` (host, or device with on_device), pair i against absBounds[i] (and pwRelBounds[i]): a list
     of Quality, record i byte for byte SZ_hip_compare's for pair i."""
@@ -965,6 +998,29 @@ class HipContext:
         if rc and raise_on_error:
             self._err(rc, "szhip_decompress_omp_batch_shapes")
         return rc, items, st
+
+    def decompress_omp_batch_region(self, streams, stream_on_device, body_off, shapes, dtype, regions, out_ptrs, out_on_device, raise_on_error=True):
+        """szhip_decompress_omp_batch_region: the sub-box regions[i] = (lo, hi[, (pitch0, pitch1)]) of the array of shapes[i] = (r0, r1, r2) in streams[i] = (address,
+        length) into out_ptrs[i]; pitches in elements, absent or (0, 0): a contiguous destination.  Items that name the same (address, length) share the stream's header
+        work.  Returns (rc, items, regions, stats): regions[i].n_boxes the boxes decoded, regions[i].shares the first item of the same stream."""
+        count = len(streams)
+        items = (szhip_batch_item * max(count, 1))()
+        for i in range(count):
+            items[i].stream, items[i].stream_len, items[i].body_off, items[i].out = streams[i][0], streams[i][1], body_off, out_ptrs[i]
+        c_shapes = (szhip_batch_shape * max(count, 1))(*[szhip_batch_shape(s[0], s[1], s[2], 0) for s in shapes]) if shapes is not None else None
+        c_regions = None
+        if regions is not None:
+            c_regions = (szhip_batch_region * max(count, 1))()
+            for i, r in enumerate(regions):
+                c_regions[i].lo[:] = [int(v) for v in r[0]]
+                c_regions[i].hi[:] = [int(v) for v in r[1]]
+                c_regions[i].pitch0, c_regions[i].pitch1 = (int(r[2][0]), int(r[2][1])) if len(r) > 2 and r[2] is not None else (0, 0)
+        st = szhip_stats()
+        rc = lib().szhip_decompress_omp_batch_region(self._h, 0 if np.dtype(dtype) == np.float32 else 1, items, c_shapes, c_regions, count, int(stream_on_device),
+                                                     int(out_on_device), ctypes.byref(st))
+        if rc and raise_on_error:
+            self._err(rc, "szhip_decompress_omp_batch_region")
+        return rc, items, c_regions, st
 
     def compress_omp_batch_view(self, ptrs, on_device, shape3, pitches, dtype, bounds, thread_num, metas, params=None, out_on_device=False, raise_on_error=True):
         """szhip_compress_omp_batch_view: compress_omp_batch on len(ptrs) sub-boxes of shape3 values, ptrs[i] the first value of sub-box i inside its parent array,

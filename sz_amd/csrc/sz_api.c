@@ -1902,6 +1902,113 @@ int SZ_hip_decompress_batch_shapes(int dataType, int count, unsigned char *const
     return decompress_batch_at("SZ_hip_decompress_batch_shapes", dataType, count, bytes, byteLengths, out, out_on_device, 0, 0, 0, 0, 0, dims);
 }
 
+/* a contiguous host array of e[0] x e[1] x e[2] values into the destination (host: its rows copied; device: staged and scattered): 1, or 0 with the reason printed */
+static int place_region(const char *who, szhip_ctx *ctx, int dataType, int i, const void *src, const size_t e[3], void *out, int out_on_device, size_t pitch0, size_t pitch1)
+{
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8;
+    if (!out_on_device) {
+        for (size_t k = 0; k < e[0]; k++)
+            for (size_t j = 0; j < e[1]; j++) memcpy((char *)out + (k * pitch0 + j * pitch1) * esz, (const char *)src + (k * e[1] + j) * e[2] * esz, e[2] * esz);
+        return 1;
+    }
+    void *d = NULL;
+    if (szhip_stage_input(ctx, src, e[0] * e[1] * e[2] * esz, &d) == SZHIP_OK &&
+        szhip_scatter_view(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, d, e[0], e[1], e[2], out, 1, pitch0, pitch1) == SZHIP_OK) return 1;
+    printf("Error: %s: region %d could not be placed: %s\n", who, i, szhip_last_error(ctx));
+    return 0;
+}
+
+int SZ_hip_decompress_batch_regions(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, const size_t *dims, const size_t *start,
+                                    const size_t *end, void *const *out, int out_on_device, const size_t *out_pitches)
+{
+    static const char *const who = "SZ_hip_decompress_batch_regions";
+    static const char *const only = "SZ_hip_decompress_batch_regions reads the OpenMP containers that SZ_compress_args writes for 3-D float / double arrays under SZ_HIP_MODE=omp";
+    /* ---- the refusals of the whole call: nothing is written */
+    if (count < 1 || !bytes || !byteLengths || !dims || !start || !end || !out) { printf("Error: %s: null argument.\n", who); return SZ_NSCS; }
+    if (dataType != SZ_FLOAT && dataType != SZ_DOUBLE) { printf("Error: %s: float and double arrays only.\n", who); return SZ_NSCS; }
+    const size_t esz = dataType == SZ_FLOAT ? 4 : 8, body = 4 + (size_t)MetaDataByteLength;
+    for (int i = 0; i < count; ++i) {
+        const size_t *d = dims + 3 * (size_t)i, *lo = start + 3 * (size_t)i, *hi = end + 3 * (size_t)i;
+        if (!bytes[i] || !out[i]) { printf("Error: %s: null argument (item %d).\n", who, i); return SZ_NSCS; }
+        if (((uintptr_t)out[i] & (esz - 1)) != 0) { printf("Error: %s: item %d: destination %p is not aligned to its %zu-byte elements.\n", who, i, out[i], esz); return SZ_NSCS; }
+        if (d[0] < 1 || d[1] < 1 || d[2] < 1 || d[0] > 0x7fffffff || d[1] > 0x7fffffff || d[2] > 0x7fffffff || (double)d[0] * (double)d[1] * (double)d[2] >= 4294967296.0) {
+            printf("Error: %s: array %d: extents %zu x %zu x %zu.\n", who, i, d[0], d[1], d[2]); return SZ_NSCS;
+        }
+        for (int k = 0; k < 3; k++)
+            if (lo[k] >= hi[k] || hi[k] > d[k]) { printf("Error: %s: item %d: region [%zu, %zu) of dimension %d is empty or beyond its extent %zu.\n", who, i, lo[k], hi[k], k, d[k]); return SZ_NSCS; }
+        if (out_pitches) {
+            const size_t p0 = out_pitches[2 * (size_t)i], p1 = out_pitches[2 * (size_t)i + 1];
+            if (p1 < hi[2] - lo[2] || p1 > ((size_t)1 << 48) || p0 > ((size_t)1 << 48) || p0 / p1 < hi[1] - lo[1]) {
+                printf("Error: %s: item %d: pitches %zu / %zu below the region's extents (pitch1 >= e3, pitch0 >= e2 * pitch1).\n", who, i, p0, p1); return SZ_NSCS;
+            }
+        }
+    }
+    szhip_ctx *ctx = get_ctx();
+    if (!ctx) return SZ_NSCS;
+    szhip_batch_item *items = (szhip_batch_item *)calloc((size_t)count, sizeof(szhip_batch_item));
+    szhip_batch_shape *shp = (szhip_batch_shape *)calloc((size_t)count, sizeof(szhip_batch_shape));
+    szhip_batch_region *reg = (szhip_batch_region *)calloc((size_t)count, sizeof(szhip_batch_region));
+    unsigned char **own = (unsigned char **)calloc((size_t)count, sizeof(unsigned char *));
+    int *idx = (int *)malloc((size_t)count * sizeof(int));
+    if (!items || !shp || !reg || !own || !idx) { free(items); free(shp); free(reg); free(own); free(idx); return SZ_NSCS; }
+    int rc_all = SZ_SCES, nb = 0;
+    szhip_stats bstats; memset(&bstats, 0, sizeof(bstats));
+    for (int i = 0; i < count; ++i) {
+        const size_t *d = dims + 3 * (size_t)i, *lo = start + 3 * (size_t)i, *hi = end + 3 * (size_t)i;
+        const size_t e[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]}, dataLength = d[0] * d[1] * d[2];
+        const size_t p1 = out_pitches ? out_pitches[2 * (size_t)i + 1] : e[2], p0 = out_pitches ? out_pitches[2 * (size_t)i] : e[1] * e[2];
+        /* a stream wrapped by the lossless stage is unwrapped whole first, as sz_hip_region_try does */
+        fresh_dec_state();
+        unsigned char *sz; size_t szlen; int owned;
+        if (!unwrap_lossless(dataType, bytes[i], byteLengths[i], dataLength, &sz, &szlen, &owned)) { printf("Error: %s: stream %d failed.\n", who, i); rc_all = SZ_NSCS; continue; }
+        const char *what = NULL;
+        if (dataLength <= MIN_NUM_OF_ELEMENTS || szlen <= body + 4) what = "a raw copy or too short";
+        else if (d[0] < 2 || d[1] < 2 || d[2] < 2) what = "not 3-D";
+        else if (!(sz[3] & 0x80) || (sz[3] & 0x31) || sz[19] != SZH_OMP_MARK)
+            what = (sz[3] & 0x01) ? "constant data" : (sz[3] & 0x10) ? "a lossless copy" : !(sz[3] & 0x80) ? "SZ 1.4" : (sz[3] & 0x20) ? "point-wise relative" : "SZ 2.1";
+        if (!what) {                                           /* a marked container: into the one batched call */
+            items[nb].stream = sz + body; items[nb].stream_len = szlen - body; items[nb].body_off = 0; items[nb].out = out[i];
+            shp[nb].r0 = d[0]; shp[nb].r1 = d[1]; shp[nb].r2 = d[2];
+            for (int k = 0; k < 3; k++) { reg[nb].lo[k] = lo[k]; reg[nb].hi[k] = hi[k]; }
+            reg[nb].pitch0 = p0; reg[nb].pitch1 = p1;
+            if (owned) own[nb] = sz;
+            idx[nb++] = i;
+            continue;
+        }
+        if ((sz[3] & 0x01) && dataLength > MIN_NUM_OF_ELEMENTS) {                  /* a constant stream: the region filled with the value SZ_decompress gives */
+            if (owned) free(sz);
+            void *o = SZ_decompress(dataType, bytes[i], byteLengths[i], 0, 0, d[0], d[1], d[2]);
+            void *crop = o ? malloc(e[0] * e[1] * e[2] * esz) : NULL;
+            int ok = crop != NULL;
+            if (ok) {
+                for (size_t k = 0; k < e[0]; k++)
+                    for (size_t j = 0; j < e[1]; j++)
+                        memcpy((char *)crop + (k * e[1] + j) * e[2] * esz, (char *)o + (((lo[0] + k) * d[1] + lo[1] + j) * d[2] + lo[2]) * esz, e[2] * esz);
+                ok = place_region(who, ctx, dataType, i, crop, e, out[i], out_on_device, p0, p1);
+            }
+            free(o); free(crop);
+            if (!ok) { printf("Error: %s: stream %d failed.\n", who, i); rc_all = SZ_NSCS; }
+            continue;
+        }
+        if (owned) free(sz);
+        printf("Error: %s; stream %d (%s) is none.\n", only, i, what);
+        rc_all = SZ_NSCS;
+    }
+    if (nb > 0) {
+        fresh_dec_state();
+        const int rc = szhip_decompress_omp_batch_region(ctx, dataType == SZ_FLOAT ? SZHIP_F32 : SZHIP_F64, items, shp, reg, nb, 0, out_on_device, &bstats);
+        if (rc != SZHIP_OK) {
+            rc_all = SZ_NSCS;
+            for (int k = 0; k < nb; ++k) if (items[k].rc != SZHIP_OK) printf("Error: %s: stream %d failed (%d).\n", who, idx[k], items[k].rc);
+            printf("Error: szhip_decompress_omp_batch_region failed (%d): %s\n", rc, szhip_last_error(ctx));
+        }
+        g_last_stats = bstats;
+    }
+    for (int k = 0; k < count; ++k) free(own[k]);
+    free(items); free(shp); free(reg); free(own); free(idx);
+    return rc_all;
+}
+
 int SZ_hip_decompress_batch_into_region(int dataType, int count, unsigned char *const *bytes, const size_t *byteLengths, void *const *parents, int out_on_device,
                                         size_t r1, size_t r2, size_t r3, const size_t start[3], const size_t end[3])
 {

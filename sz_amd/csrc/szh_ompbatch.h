@@ -259,3 +259,54 @@ __global__ __launch_bounds__(256) void k_ompbs_scatter(const szh_ompb_rec *__res
     const szh_ompb_rec &r = recs[a];
     omp_scatter_body<T>(e.g, r.codes, r.uoff, (const T *)r.unpred, (T *)r.out, (unsigned *)(r.totals + 2), r.vflags, e.fw);
 }
+
+// =====================================================================================================================
+// SUB-BOXES of many streams in one call (szhip_decompress_omp_batch_region).  Every item's "array" is the sub-array of the boxes its region
+// meets: the decode and the sweeps are the k_ompbs_* kernels above over compact tables and a sub-geometry per item, into a staging array in the context.  What is new
+// is the step behind them: ONE launch that puts every item's region out of its staging array into its destination -- a contiguous array, a view of a padded parent
+// (a ghost layer), or a contiguous device buffer that the host then copies out through the pitches.
+// A third per-item record, read uniformly per workgroup through list[blockIdx.y] as the other two.  The grid's first dimension is sized to the item with the most
+// pieces; the surplus workgroups of a smaller item return at once.  A workgroup whose item's error counter (the sweeps' totals[2]) is not zero returns without writing:
+// no host synchronisation lies between the sweeps and the placement, and a damaged item leaves its destination as it was.
+struct szh_ompb_place {
+    const void *src;                           // the region's FIRST VALUE inside the item's staging array (staging base + the region's offset in its covered boxes)
+    void *dst;                                 // the destination's first value
+    int64_t s0, s1, d0, d1;                    // element pitches of the staging array (those of the covered boxes) and of the destination
+    int e0, e1, e2, ppr;                       // the region's extents; pieces per row: the head and (e2 + VW - 1) / VW more
+    const u64 *err;                            // the item's error counter
+    u64 pad_;
+};
+// Piece `idx` of an item: the discipline of view_scatter_body -- every row is cut at the 16-byte boundaries of its DESTINATION, whole pieces are one uint4 store, a
+// head and a tail go value by value, nothing outside a row's e2 values is written and no value of the destination is read -- with a source that is itself strided:
+// row (k, i) starts at src + k s0 + i s1, which in general sits at another offset modulo 16 than the destination's row.  The source side of a whole piece is one
+// uint4 load where its address happens to be aligned, else VW element loads: the lanes of a wavefront read neighbouring pieces of a row, so the element loads of a
+// piece hit the lines its neighbours fetch; it is the store that must not straddle a boundary or touch a byte outside the row.
+template <class T>
+__device__ __forceinline__ void ompb_place_body(const szh_ompb_place &r, int64_t idx)
+{
+    constexpr int VW = 16 / (int)sizeof(T);
+    const int64_t row = idx / r.ppr, k = row / r.e1;
+    const int p = (int)(idx - row * r.ppr), i = (int)(row - k * r.e1), e2 = r.e2;
+    const T *s = (const T *)r.src + k * r.s0 + (int64_t)i * r.s1;
+    T *d = (T *)r.dst + k * r.d0 + (int64_t)i * r.d1;
+    int head = (int)(((16u - (unsigned)((uintptr_t)d & 15u)) & 15u) / (unsigned)sizeof(T));      // (`d` is aligned to its element)
+    if (head > e2) head = e2;
+    const int j0 = p == 0 ? 0 : head + (p - 1) * VW, j1 = p == 0 ? head : (j0 + VW < e2 ? j0 + VW : e2);
+    if (p > 0 && j1 - j0 == VW) {
+        uint4 v;
+        if ((((uintptr_t)(s + j0)) & 15u) == 0) v = *reinterpret_cast<const uint4 *>(s + j0);
+        else { T t[VW]; for (int q = 0; q < VW; ++q) t[q] = s[j0 + q]; __builtin_memcpy(&v, t, 16); }
+        *reinterpret_cast<uint4 *>(d + j0) = v;
+    } else
+        for (int j = j0; j < j1; ++j) d[j] = s[j];
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_ompbr_place(const szh_ompb_place *__restrict__ places, const int *__restrict__ list)
+{
+    const szh_ompb_place &r = places[list[blockIdx.y]];
+    const int64_t pieces = (int64_t)r.e0 * r.e1 * r.ppr;
+    if ((int64_t)blockIdx.x * 256 >= pieces) return;            // (uniform: a smaller item than the launch's largest)
+    if ((unsigned)r.err[0] != 0u) return;                       // (uniform: a box of this item did not decode)
+    const int64_t idx = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (idx < pieces) ompb_place_body<T>(r, idx);
+}

@@ -187,6 +187,7 @@ namespace {
 #include "szhip_pwr.inc"     // point-wise relative bounds
 #include "szhip_omp.inc"     // the reference's OpenMP container
 #include "szhip_ompbatch.inc" // ... over many same-shape arrays in one call
+#include "szhip_ompregion.inc" // ... sub-boxes of many streams in one call
 #include "szhip_rangebatch.inc" // the value range of many arrays in one launch
 #include "szhip_quality.inc" // an array against its decoded copy: the error report, for one pair and for many
 
@@ -697,6 +698,32 @@ int szhip_decompress_omp_region(szhip_ctx *ctx, int dtype, const unsigned char *
     TRY(check_alignment_set_device(ctx, dtype, out));
     return synced_on_failure(ctx,
                BY_DTYPE(dtype, decompress_omp_region_impl, ctx, stream, stream_on_device, stream_len, body_off, r0, r1, r2, lo, hi, out, out_on_device, stats));
+}
+
+// ---- sub-boxes of many streams in one call.  SZHIP_ERR_ARG before anything is launched or written: the batch calls' refusals, an empty region or
+// one beyond its item's extents, pitches that break the view rule
+int szhip_decompress_omp_batch_region(szhip_ctx *ctx, int dtype, szhip_batch_item *items, const szhip_batch_shape *shapes, szhip_batch_region *regions, int count,
+                                      int stream_on_device, int out_on_device, szhip_stats *stats)
+{
+    if (!regions) return SZHIP_ERR_ARG;
+    TRY(batch_args(ctx, dtype, items, count, 1, 1, 1, false));
+    TRY(batch_shapes_args(ctx, shapes, count, false));
+    for (int i = 0; i < count; ++i) {
+        const szhip_batch_region &rg = regions[i];
+        const size_t r[3] = {shapes[i].r0, shapes[i].r1, shapes[i].r2};
+        for (int k = 0; k < 3; ++k)
+            if (rg.lo[k] >= rg.hi[k] || rg.hi[k] > r[k]) {
+                snprintf(ctx->err, sizeof(ctx->err), "item %d of the batch: region [%zu, %zu) of dimension %d is empty or beyond its extent %zu", i, rg.lo[k], rg.hi[k], k, r[k]);
+                return SZHIP_ERR_ARG;
+            }
+        if (rg.pitch0 != 0 || rg.pitch1 != 0) TRY(check_view(ctx, rg.hi[0] - rg.lo[0], rg.hi[1] - rg.lo[1], rg.hi[2] - rg.lo[2], rg.pitch0, rg.pitch1));
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return SZHIP_ERR_NODEVICE;
+    for (int i = 0; i < count; ++i) {
+        items[i].rc = SZHIP_OK; items[i].intervals = 0; items[i].n_unpred = 0; items[i].quant_kernel = 0; items[i].batched = 0;
+        regions[i].n_boxes = 0; regions[i].shares = i;
+    }
+    return synced_on_failure(ctx, BY_DTYPE(dtype, decompress_omp_batch_region_impl, ctx, items, shapes, regions, count, stream_on_device, out_on_device, stats));
 }
 
 // ---- views (szhip.h): a sub-box of r0 x r1 x r2 values whose planes lie pitch0 and whose rows pitch1 elements apart
