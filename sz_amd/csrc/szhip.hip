@@ -185,6 +185,7 @@ namespace {
 #include "szhip_sz21.inc"    // SZ 2.1: the hot path (SZ_compress_args / SZ_decompress of float and double arrays)
 #include "szhip_sz14.inc"    // SZ 1.4 container, MSST19
 #include "szhip_pwr.inc"     // point-wise relative bounds
+#include "szhip_omprules.inc" // the OpenMP container's rules, once, for the three files below
 #include "szhip_omp.inc"     // the reference's OpenMP container
 #include "szhip_ompbatch.inc" // ... over many same-shape arrays in one call
 #include "szhip_ompregion.inc" // ... sub-boxes of many streams in one call

@@ -1,10 +1,7 @@
 // szhip_omp.inc -- part of szhip.hip (one translation unit; included inside its anonymous namespace): the reference's OpenMP container.
 // =====================================================================================================================
-// The reference's OpenMP container for 3-D arrays (szh_omp.h; sz/src/sz_omp.c:63-358, inverse :366-566).  Stream, behind the caller's
-// 4 + MetaDataByteLength parameter bytes (`meta`):
-//   u32be thread_num | T eb (big endian) | u32be intervals | u32be tree_bytes | u32be nodes | tree
-//   | u32 ucount[nb] | T first[nb] | the boxes' verbatim values, box after box | u64 payload_bytes[nb] | the boxes' Huffman payloads
-// (the tables behind the tree in the host's byte order, as the reference memcpy's them).
+// The reference's OpenMP container for 3-D arrays (szh_omp.h; sz/src/sz_omp.c:63-358, inverse :366-566).  The stream's layout and every rule of the format that
+// the batch calls share with the calls below: szhip_omprules.inc.
 // =====================================================================================================================
 static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, size_t r2, szh_omp_geom *g)
 {
@@ -24,7 +21,7 @@ static int omp_box_grid(szhip_ctx *ctx, int thread_num, size_t r0, size_t r1, si
     g->d0 = (int64_t)(r1 * r2); g->d1 = (int64_t)r2;
     g->nb = (int)(nx * ny * nz);
     const size_t bel = (size_t)g->c0 * g->c1 * g->c2;
-    if ((size_t)g->c0 * g->c1 > SZH_OMP_MAX_ROWS || bel >= ((size_t)1 << 28))
+    if ((size_t)g->c0 * g->c1 > SZH_OMP_MAX_ROWS || bel >= OMP_BOX_LIMIT)
         FAIL(SZHIP_ERR_UNSUP, "OpenMP container: a box face of %d x %d rows (at most %d; raise thread_num)", g->c0, g->c1, SZH_OMP_MAX_ROWS);
     g->bel = (int)bel;
     g->cpb = (int)((bel + SZH_ENC_CHUNK - 1) / SZH_ENC_CHUNK);
@@ -105,7 +102,7 @@ struct omp_call : call_base {
     // ---- the code book and the stream's layout
     std::vector<u64> tab_code; std::vector<uint8_t> tab_len; unsigned maxlen = 0; u64 total_bits = 0, E = 0;
     std::vector<unsigned char> hdr;
-    size_t hdr_len = 0, off_ucount = 0, off_first = 0, off_unpred = 0, off_sizes = 0, off_pay = 0, cap_len = 0;
+    omp_layout<T> L{0, 0, 0, 0, 0};
 
     // ---- the array staged; interval count (sz_omp.c:73-82: optimize_intervals_float_3D_opt over the whole array when it is not fixed)
     int choose_intervals(const void *data, int data_on_device) {
@@ -131,7 +128,7 @@ struct omp_call : call_base {
         d_ucount = (unsigned *)ctx->zcnt.p; d_first = (T *)ctx->samples.p;
         d_ucount64 = (u64 *)ctx->col_zeros64.p; d_uoff = (u64 *)ctx->col_off.p;
         const int rows = g.c0 * g.c1, box_threads = rows;      // one lane per row
-        box_hist = intervals <= 1024 && (size_t)g.nb * intervals * 4 <= ((size_t)64 << 20) && g.bel % 8 == 0;
+        box_hist = omp_box_hist_book(intervals, (size_t)g.nb) && omp_box_hist_shape(g.bel);
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         if (omp_col_applies(g, d_in, row_bytes, plane_bytes)) {             // the column-per-lane sweep (szh_ompcol.h): a wavefront per pair of boxes
             szh_oc::sweep_args<T> oa;
@@ -161,11 +158,7 @@ struct omp_call : call_base {
         if (box_hist) {
             TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * intervals * 4));
             d_hist_box = (unsigned *)ctx->chunk_bits.p;
-            // lane-private copies of the bins against same-address atomics -- but no more copies than the box has codes to spread over them
-            // (a box of 4096 codes with 64 copies of 32 bins spent its time clearing and summing 32 KB: 0.40 ms for 32 768 such boxes)
-            int rshift = 0;
-            while ((intervals << (rshift + 1)) <= 8192u && rshift < 6 && ((size_t)intervals << (rshift + 1)) * 16 <= (size_t)g.bel) ++rshift;
-            const int hist_per_wg = std::max(1, std::min(16, 32768 / std::max(1, g.bel)));
+            const int rshift = omp_hist_rshift(intervals, g.bel), hist_per_wg = omp_hist_per_wg(g.bel);
             hipLaunchKernelGGL(k_omp_hist_box, dim3((unsigned)((g.nb + hist_per_wg - 1) / hist_per_wg)), dim3(256), ((size_t)intervals << rshift) * 4, st, g.bel, (const uint16_t *)d_codes, intervals, rshift,
                                d_hist_box, d_hist, sweep_counted ? (unsigned *)nullptr : d_ucount, sweep_counted ? (u64 *)nullptr : d_ucount64, g.nb, hist_per_wg);
             HIPCHK(hipGetLastError());
@@ -181,44 +174,33 @@ struct omp_call : call_base {
         if (!hf) FAIL(SZHIP_ERR_INTERNAL, "Huffman build failed");
         const size_t tree_bytes = szhost_huff_tree_size(hf.get());
         total_bits = hf->total_bits;
-        hdr_len = meta_len + 4 + sizeof(T) + 4 + 4 + 4 + tree_bytes;
-        off_ucount = hdr_len; off_first = off_ucount + (size_t)g.nb * 4; off_unpred = off_first + (size_t)g.nb * sizeof(T);
-        off_sizes = off_unpred + (size_t)E * sizeof(T); off_pay = off_sizes + (size_t)g.nb * 8;
-        cap_len = off_pay + (size_t)((total_bits + 7) / 8) + (size_t)g.nb;
-        hdr.assign(hdr_len, 0);
-        unsigned char *q = hdr.data();
-        memcpy(q, meta, meta_len); q += meta_len;
-        szhost_put_u32be(q, (uint32_t)g.nb); q += 4;              // (`thread_num` after the grid has been cut: sz_omp.c:122)
-        if (sizeof(T) == 8) szhost_put_f64be(q, (double)eb); else szhost_put_f32be(q, (float)eb);
-        q += sizeof(T);
-        szhost_put_u32be(q, intervals); q += 4;
-        szhost_put_u32be(q, (uint32_t)tree_bytes); q += 4;
-        szhost_put_u32be(q, (uint32_t)hf->n_nodes); q += 4;
-        szhost_huff_tree_write(hf.get(), q);
+        L = omp_layout<T>(meta_len, (size_t)g.nb, E, tree_bytes, total_bits);
+        hdr.assign(L.hdr_len, 0);
+        omp_write_header<T>(hdr.data(), meta, meta_len, (size_t)g.nb, eb, intervals, hf.get(), tree_bytes);
         host_ms += now_ms() - h0;
         return SZHIP_OK;
     }
     // ---- packing: the boxes' payloads and every table of the stream into the stream buffer
     int pack() {
-        TRY(ensure(ctx, ctx->stream_buf, cap_len + 64));
+        TRY(ensure(ctx, ctx->stream_buf, L.cap_len + 64));
         d_stream = (unsigned char *)ctx->stream_buf.p;
-        HIPCHK(hipMemsetAsync(d_stream, 0, cap_len + 64, st));
+        HIPCHK(hipMemsetAsync(d_stream, 0, L.cap_len + 64, st));
         TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8));
         d_box_bytes = (u64 *)ctx->reg_flags.p; d_box_off = (u64 *)ctx->reg_rank.p;
-        const size_t lds3 = (size_t)intervals * 8 + ((size_t)SZH_OMP_R3 * maxlen / 32 + 4) * 4 + 16;
-        const bool fast = box_hist && maxlen <= 32 && intervals <= 2048 && lds3 <= 60 * 1024;
+        const size_t lds3 = omp_fast_lds3(intervals, maxlen);
+        const bool fast = box_hist && intervals <= 2048 && omp_fast_packs(maxlen, lds3);      // (`intervals <= 2048`: this call's own; box_hist has asked for 1024 already)
         return fast ? pack_fast(lds3) : pack_general();
     }
     // the usual case (code words of at most 32 bits, a histogram per box): ONE upload -- the header and the packed code table
     // `code << 8 | len` --, one launch for the boxes' sizes and places (k_omp_layout), one that packs the codes and writes every table
     // of the stream itself (k_omp_encode_box3).  (Round 4, first form: 8 copies / fills and 8 small launches here, ~0.1 ms of gaps.)
     int pack_fast(size_t lds3) {
-        const size_t hdr_pad = (hdr_len + 7) / 8 * 8, blob = hdr_pad + (size_t)intervals * 8;
+        const size_t hdr_pad = (L.hdr_len + 7) / 8 * 8, blob = hdr_pad + (size_t)intervals * 8;
         TRY(ensure_pinned3(ctx, blob));
         unsigned char *hb = (unsigned char *)ctx->pinned3;
-        memcpy(hb, hdr.data(), hdr_len);
+        memcpy(hb, hdr.data(), L.hdr_len);
         u64 *hp = (u64 *)(hb + hdr_pad);
-        for (unsigned s2 = 0; s2 < intervals; ++s2) hp[s2] = ((tab_code[s2] & (tab_len[s2] >= 64 ? ~0ull : (1ull << tab_len[s2]) - 1)) << 8) | tab_len[s2];
+        omp_packed_table(tab_code, tab_len, intervals, hp);
         TRY(ensure(ctx, ctx->code_tab, blob));
         TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
         HIPCHK(hipMemcpyAsync(ctx->code_tab.p, hb, blob, hipMemcpyHostToDevice, st));
@@ -229,37 +211,37 @@ struct omp_call : call_base {
                            sm + SM_SCRATCH, sm + SM_TOTAL_UNPRED, many);
         HIPCHK(hipGetLastError());
         szh_omp_tables tb;
-        tb.stream = d_stream; tb.hdr = (const unsigned char *)ctx->code_tab.p; tb.hdr_len = (unsigned)hdr_len;
-        tb.off_ucount = off_ucount; tb.off_first = off_first; tb.off_unpred = off_unpred; tb.off_sizes = off_sizes; tb.first = d_first;
+        tb.stream = d_stream; tb.hdr = (const unsigned char *)ctx->code_tab.p; tb.hdr_len = (unsigned)L.hdr_len;
+        tb.off_ucount = L.off_ucount; tb.off_first = L.off_first; tb.off_unpred = L.off_unpred; tb.off_sizes = L.off_sizes; tb.first = d_first;
         hipLaunchKernelGGL((k_omp_encode_box3<T>), dim3((unsigned)g.nb), dim3(256), lds3, st, g, d_in, (const uint16_t *)d_codes, d_packed, intervals, maxlen, (const u64 *)d_box_off,
-                           (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8, (unsigned *)d_stream,
+                           (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)L.off_pay * 8, (unsigned *)d_stream,
                            (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR), tb);
         HIPCHK(hipGetLastError());
         // (the verbatim values go through an aligned buffer: their table lies at whatever byte offset the tree's size gives it, and byte
         //  stores from the kernel were half of its 0.1 ms for them)
-        if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + L.off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
         return SZHIP_OK;
     }
     // the first form: tables copied one by one; the boxes' payload sizes (from their histograms, or one more pass over the codes), their places, then
     // ONE pass that packs every box's codes behind a running bit position and drops its verbatim values into the table on the way
     int pack_general() {
         TRY(upload_code_tables(ctx, tab_code, tab_len));
-        HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_stream + off_ucount, d_ucount, (size_t)g.nb * 4, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_stream + off_first, d_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_stream, hdr.data(), L.hdr_len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_stream + L.off_ucount, d_ucount, (size_t)g.nb * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_stream + L.off_first, d_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
         if (box_hist) TRY(scan_u64(ctx, (const u64 *)d_ucount64, g.nb, d_uoff, sm + SM_TOTAL_UNPRED));
         TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
         if (box_hist) hipLaunchKernelGGL(k_omp_box_bits_h, dim3((unsigned)((g.nb + 3) / 4)), dim3(256), 0, st, g.nb, intervals, (const unsigned *)d_hist_box, (const uint8_t *)ctx->len_tab.p, d_box_bytes);
         else hipLaunchKernelGGL(k_omp_box_bits_c, dim3((unsigned)g.nb), dim3(256), 0, st, g.bel, (const uint16_t *)d_codes, (const uint8_t *)ctx->len_tab.p, d_box_bytes);
         HIPCHK(hipGetLastError());
         TRY(scan_u64(ctx, (const u64 *)d_box_bytes, g.nb, d_box_off, sm + SM_SCRATCH));
-        HIPCHK(hipMemcpyAsync(d_stream + off_sizes, d_box_bytes, (size_t)g.nb * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_stream + L.off_sizes, d_box_bytes, (size_t)g.nb * 8, hipMemcpyDeviceToDevice, st));
         const bool tab_lds = intervals <= 2048;                  // the code table in LDS when it fits
         hipLaunchKernelGGL((tab_lds ? k_omp_encode_box<T, true> : k_omp_encode_box<T, false>), dim3((unsigned)g.nb), dim3(256), (tab_lds ? (size_t)intervals * 9 : 0) + 16, st, g, d_in, (const uint16_t *)d_codes,
-                           (const u64 *)ctx->code_tab.p, (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)d_box_off, (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)off_pay * 8,
+                           (const u64 *)ctx->code_tab.p, (const uint8_t *)ctx->len_tab.p, intervals, (const u64 *)d_box_off, (const u64 *)d_box_bytes, (const u64 *)d_uoff, (const unsigned *)d_ucount, (u64)L.off_pay * 8,
                            (unsigned *)d_stream, (T *)ctx->unpred.p, (unsigned *)(sm + SM_ERR));
         HIPCHK(hipGetLastError());
-        if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (E > 0) HIPCHK(hipMemcpyAsync(d_stream + L.off_unpred, ctx->unpred.p, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
         return SZHIP_OK;
     }
     // ---- the end of the entropy stage; the device's counts against the book's, delivery, the statistics
@@ -268,11 +250,10 @@ struct omp_call : call_base {
         u64 h_small[SM_COUNT];
         HIPCHK(hipMemcpyAsync(h_small, sm, SM_COUNT * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (h_small[SM_TOTAL_UNPRED] != E || (unsigned)h_small[SM_ERR] != 0 ||
-            h_small[SM_SCRATCH] < (total_bits + 7) / 8 || h_small[SM_SCRATCH] > (total_bits + 7) / 8 + (u64)g.nb)
+        if (!omp_totals_ok(h_small[SM_TOTAL_UNPRED], h_small[SM_ERR], h_small[SM_SCRATCH], E, total_bits, (size_t)g.nb))
             FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: entropy stage mismatch");
-        const size_t total_len = off_pay + (size_t)h_small[SM_SCRATCH];
-        if (total_len > cap_len) FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: payloads larger than their bound");
+        const size_t total_len = L.off_pay + (size_t)h_small[SM_SCRATCH];
+        if (total_len > L.cap_len) FAIL(SZHIP_ERR_INTERNAL, "OpenMP container: payloads larger than their bound");
         TRY(deliver_stream(ctx, d_stream, total_len, out_on_device, out, out_size, false, true));
         if (!out_on_device && hipStreamSynchronize(st) != hipSuccess) FAIL_PUBLISHED(SZHIP_ERR_NODEVICE, "copying the stream to the host failed");
         compress_times(ctx, S, host_ms, t_begin, total_len);
@@ -312,48 +293,32 @@ struct omp_dec : call_base {
     bool packed = false;
     size_t pitch0 = 0, pitch1 = 0;                             // a view (szhip_decompress_omp_view): the element pitches of the array `out` lies in; 0: contiguous
     // ---- the header and the tables behind it
-    szh_omp_geom g; int64_t n = 0; T eb = 0; unsigned intervals = 0; u64 E = 0;
-    size_t off_first = 0, off_unpred = 0, off_pay = 0;
-    dec_table D;
-    std::vector<u64> uoff, bbytes, boff;
+    omp_stream<T> s;
+    szh_omp_geom g; int64_t n = 0; u64 E = 0;                   // (`g`, `E`: of the boxes the sweep runs over -- a region call's are its sub-grid's)
     // ---- device arrays
     u64 *sm = nullptr; uint16_t *d_codes = nullptr; T *d_out = nullptr;
     const u64 *d_uoff = nullptr; const T *d_first = nullptr, *d_unpred = nullptr;      // per box: ranks of its verbatim values, its first value; the verbatim values
 
     // ---- the stream taken in; the fixed fields, the box grid, the tree, the boxes' counts of verbatim values and payload sizes: on the host
     int read_header() {
+        const char *why;
         TRY(in.open());
-        const size_t fixed = body_off + 4 + sizeof(T) + 12;
-        TRY(in.fetch(fixed));
-        const unsigned char *q = in.hs + body_off;
-        const int thread_num = (int)szhost_get_u32be(q); q += 4;
-        eb = sizeof(T) == 8 ? (T)szhost_get_f64be(q) : (T)szhost_get_f32be(q); q += sizeof(T);
-        intervals = szhost_get_u32be(q); q += 4;
-        const size_t tree_bytes = szhost_get_u32be(q); q += 4;
-        const int node_count = (int)szhost_get_u32be(q); q += 4;
-        if (intervals < 4 || intervals > 65536 || !(eb > 0)) FAIL(SZHIP_ERR_STREAM, "bad OpenMP-container header");
-        if (node_count <= 0 || tree_bytes > stream_len || szhost_huff_serial_size(node_count) > tree_bytes) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-        TRY(omp_box_grid(ctx, thread_num, r0, r1, r2, &g));
-        if (g.nb != thread_num) FAIL(SZHIP_ERR_STREAM, "thread_num %d is not a box grid", thread_num);
+        if ((why = s.begin(body_off, stream_len))) FAIL(SZHIP_ERR_STREAM, "%s", why);
+        TRY(in.fetch(s.fixed));
+        if ((why = s.read_fixed(in.hs))) FAIL(SZHIP_ERR_STREAM, "%s", why);
+        TRY(omp_box_grid(ctx, s.thread_num, r0, r1, r2, &g));
+        if (g.nb != s.thread_num) FAIL(SZHIP_ERR_STREAM, "thread_num %d is not a box grid", s.thread_num);
         n = (int64_t)r0 * r1 * r2;
-        S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb; S.intervals = intervals;
-        const size_t off_ucount = fixed + tree_bytes;
-        off_first = off_ucount + (size_t)g.nb * 4; off_unpred = off_first + (size_t)g.nb * sizeof(T);
-        TRY(in.fetch(off_unpred));
-        if (!read_tree(in.hs + fixed, node_count, intervals, D)) FAIL(SZHIP_ERR_STREAM, "bad Huffman tree");
-        uoff.assign((size_t)g.nb + 1, 0);
-        for (int b = 0; b < g.nb; ++b) { uint32_t c; memcpy(&c, in.hs + off_ucount + (size_t)b * 4, 4); if (c > (uint32_t)g.bel) FAIL(SZHIP_ERR_STREAM, "bad verbatim-value count"); uoff[b + 1] = uoff[b] + c; }
-        E = uoff[g.nb];
+        S.n_elements = (uint64_t)n; S.n_blocks = (uint64_t)g.nb; S.intervals = s.intervals;
+        if ((why = s.place_tables(g))) FAIL(SZHIP_ERR_STREAM, "%s", why);
+        TRY(in.fetch(s.off_unpred));
+        if ((why = s.read_tree_and_counts(in.hs, g))) FAIL(SZHIP_ERR_STREAM, "%s", why);
+        E = s.E;
         S.n_unpred = E;
-        const size_t off_sizes = off_unpred + (size_t)E * sizeof(T);
-        off_pay = off_sizes + (size_t)g.nb * 8;
-        if (off_pay > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
-        bbytes.resize((size_t)g.nb); boff.resize((size_t)g.nb);
-        if (in.on_device) { HIPCHK(hipMemcpyAsync(bbytes.data(), in.d_stream + off_sizes, (size_t)g.nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
-        else memcpy(bbytes.data(), in.stream_in + off_sizes, (size_t)g.nb * 8);
-        u64 acc = 0;
-        for (int b = 0; b < g.nb; ++b) { boff[b] = acc; if (bbytes[b] > stream_len || bbytes[b] >= ((u64)1 << 28)) FAIL(SZHIP_ERR_STREAM, "bad payload size"); acc += bbytes[b]; }
-        if (off_pay + acc > stream_len) FAIL(SZHIP_ERR_STREAM, "truncated stream");
+        u64 *sizes = s.size_table(g);
+        if (in.on_device) { HIPCHK(hipMemcpyAsync(sizes, in.d_stream + s.off_sizes, (size_t)g.nb * 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
+        else memcpy(sizes, in.stream_in + s.off_sizes, (size_t)g.nb * 8);
+        if ((why = s.walk_sizes())) FAIL(SZHIP_ERR_STREAM, "%s", why);
         return SZHIP_OK;
     }
     // ---- device tables: payload offsets / sizes, ranks of the verbatim values, first values and verbatim values at aligned addresses; then the Huffman decode,
@@ -362,36 +327,32 @@ struct omp_dec : call_base {
         TRY(clear_small(ctx, &sm));
         TRY(ensure(ctx, ctx->reg_flags, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->reg_rank, (size_t)g.nb * 8)); TRY(ensure(ctx, ctx->col_off, (size_t)g.nb * 8 + 8));
         TRY(ensure(ctx, ctx->samples, (size_t)g.nb * sizeof(T))); TRY(ensure(ctx, ctx->unpred, (size_t)E * sizeof(T) + 16));
-        TRY(ensure(ctx, ctx->dec_tab, (D.dtab.size() * 4 + 63) / 64 * 64 + SZH_LUT_BYTES + 16));
-        HIPCHK(hipMemcpyAsync(ctx->reg_flags.p, bbytes.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->reg_rank.p, boff.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->col_off.p, uoff.data(), ((size_t)g.nb + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, D.dtab.data(), D.dtab.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->samples.p, in.d_stream + off_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
-        if (E > 0) HIPCHK(hipMemcpyAsync(ctx->unpred.p, in.d_stream + off_unpred, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
+        TRY(ensure(ctx, ctx->dec_tab, up64(s.D.dtab.size() * 4) + SZH_LUT_BYTES + 16));
+        HIPCHK(hipMemcpyAsync(ctx->reg_flags.p, s.bbytes.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->reg_rank.p, s.boff.data(), (size_t)g.nb * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->col_off.p, s.uoff.data(), ((size_t)g.nb + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, s.D.dtab.data(), s.D.dtab.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->samples.p, in.d_stream + s.off_first, (size_t)g.nb * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (E > 0) HIPCHK(hipMemcpyAsync(ctx->unpred.p, in.d_stream + s.off_unpred, (size_t)E * sizeof(T), hipMemcpyDeviceToDevice, st));
         d_uoff = (const u64 *)ctx->col_off.p; d_first = (const T *)ctx->samples.p; d_unpred = (const T *)ctx->unpred.p;
         TRY(ensure(ctx, ctx->codes_nat, (size_t)n * 2 + 64));
         d_codes = (uint16_t *)ctx->codes_nat.p;
-        u64 max_box = 0;
-        for (int b = 0; b < g.nb; ++b) max_box = std::max(max_box, bbytes[b]);
-        return huffman_decode(g.nb, in.d_stream + off_pay, (unsigned)off_pay, (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, max_box);
+        return huffman_decode(g.nb, in.d_stream + s.off_pay, (unsigned)s.off_pay, (const u64 *)ctx->reg_rank.p, (const u64 *)ctx->reg_flags.p, s.max_box);
     }
     // the Huffman decode of `nb` boxes into d_codes, box after box: their payloads at payload + box_off[b] (`bytes_before` bytes of the buffer lie in front of
     // `payload`, 64 behind the last one), the largest of `max_box` bytes; the node table is in ctx->dec_tab
     int huffman_decode(int nb, const unsigned char *payload, unsigned bytes_before, const u64 *box_off, const u64 *box_bytes, u64 max_box) {
-        // the look-up-table decoder (hdec_run_lut) when a box's payload, the table and the node table fit a workgroup's LDS
-        const unsigned stage_bytes = (unsigned)((max_box + 30 + 15) / 16 * 16 + 16);
-        const size_t stage_lds = ((size_t)SZH_HDEC_SWZ((stage_bytes + 16) / 4) * 4 + 15) / 16 * 16;
-        const int tab_lds_lut = (size_t)D.n_nodes * 8 <= 13 * 1024;
-        const size_t lds_lut = stage_lds + SZH_LUT_BYTES + (tab_lds_lut ? ((size_t)D.n_nodes * 8 + 15) / 16 * 16 : 0);
-        if (D.single_symbol < 0 && g.bel % 8 == 0 && lds_lut <= 64 * 1024) {
-            const size_t lut_off = (D.dtab.size() * 4 + 63) / 64 * 64;
+        const dec_table &D = s.D;
+        const hdec_fit fit = hdec_lut_fit(max_box, D.n_nodes, D.single_symbol, g.bel);
+        if (fit.takes) {
+            hdec_launch hl; hl.add(fit); hl.close();
+            const size_t lut_off = up64(D.dtab.size() * 4);
             TRY(ensure(ctx, ctx->dec_tab, lut_off + SZH_LUT_BYTES));          // (grown before the table went up: above)
             hipLaunchKernelGGL(k_hdec_build_lut, dim3(SZH_LUT_SIZE / 256), dim3(256), 0, st, (const unsigned *)ctx->dec_tab.p, (uint4 *)((char *)ctx->dec_tab.p + lut_off));
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)nb), dim3(256), lds_lut, st, g.bel, payload, bytes_before,
-                               box_off, box_bytes, (const unsigned *)ctx->dec_tab.p, D.n_nodes, tab_lds_lut,
-                               (const uint4 *)((char *)ctx->dec_tab.p + lut_off), stage_bytes, d_codes, (unsigned *)(sm + SM_ERR));
+            hipLaunchKernelGGL(k_omp_hdec_lut, dim3((unsigned)nb), dim3(256), hl.lds_lut, st, g.bel, payload, bytes_before,
+                               box_off, box_bytes, (const unsigned *)ctx->dec_tab.p, D.n_nodes, hl.tab_lds(D.n_nodes),
+                               (const uint4 *)((char *)ctx->dec_tab.p + lut_off), fit.stage_bytes, d_codes, (unsigned *)(sm + SM_ERR));
         } else {
             const int tab_lds = D.dtab.size() * 4 <= 16384;            // node table and payload in LDS when they are small (the usual case: 2 - 3 bits per code)
             const unsigned pay_cap = (unsigned)std::min<u64>(max_box, 24576);
@@ -419,9 +380,8 @@ struct omp_dec : call_base {
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         if (omp_col_applies(g, d_out, row_bytes, plane_bytes)) {
             // the verbatim values go to their places in the output first (boxes that have any); the sweep picks them up where a code is zero
-            int fw = (g.c0 * g.c1 / (16 / (int)sizeof(T)) + 31) / 32;        // flag words per box: a bit per group of rows one load of the sweep covers
+            const int fw = omp_flag_words<T>(g);
             unsigned *d_vflags = nullptr;
-            if (fw > OC_FLAG_WORDS) fw = 0;
             if (E > 0) {
                 if (fw > 0) {
                     TRY(ensure(ctx, ctx->chunk_bits, (size_t)g.nb * fw * 4));
@@ -434,11 +394,11 @@ struct omp_dec : call_base {
             }
             szh_oc::sweep_args<T> oa;
             oa.vflags = d_vflags; oa.fw = fw;
-            oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = eb; oa.recip = (T)(1 / eb); oa.intervals = (int)intervals; oa.codes = d_codes;
+            oa.g = g; oa.data = nullptr; oa.out = d_out; oa.eb = s.eb; oa.recip = (T)(1 / s.eb); oa.intervals = (int)s.intervals; oa.codes = d_codes;
             oa.ucount = (unsigned *)(sm + SM_ERR); oa.ucount64 = nullptr; oa.first = const_cast<T *>(d_first); oa.uoff = d_uoff;
             hipLaunchKernelGGL((k_omp_col<T, 32, 32, true>), dim3((unsigned)(g.nb / 2)), dim3(64), 0, st, oa);
         } else hipLaunchKernelGGL((g.vec ? k_omp_box<T, true, true> : k_omp_box<T, true, false>), dim3((unsigned)g.nb), dim3((unsigned)box_threads), (size_t)4 * g.c0 * g.pitch * sizeof(T), st, g, (const T *)nullptr,
-                                  d_out, eb, (T)(1 / eb), (int)intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, const_cast<T *>(d_first), d_unpred, d_uoff);
+                                  d_out, s.eb, (T)(1 / s.eb), (int)s.intervals, d_codes, (unsigned *)(sm + SM_ERR), (u64 *)nullptr, const_cast<T *>(d_first), d_unpred, d_uoff);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->ev[3], st));
         S.quant_kernel = omp_col_applies(g, d_out, row_bytes, plane_bytes) ? 3 : (g.vec ? 4 : 5);
@@ -482,103 +442,68 @@ template <class T>
 struct omp_region {
     omp_dec<T> &d; const size_t *const lo, *const hi;
     szhip_ctx *const ctx = d.ctx; const hipStream_t st = d.st;
-    int b0[3], cn[3]; int nbc = 0; size_t ext[3], n_out = 0; bool direct = false;
+    omp_subgrid<T> c;                                          // the covered sub-grid, its compact tables and pieces, the sub-geometry
     // the call's device blob: [payload sizes][payload offsets][ranks + 1][spans] | [first values][verbatim values][64 bytes, the payloads, 64 zero bytes]
     size_t o_bytes = 0, o_off = 0, o_uoff = 0, o_spans = 0, o_first = 0, o_unp = 0, o_pay = 0, blob_len = 0, n_spans = 0;
-    u64 Ec = 0, max_box = 0;
     unsigned char *d_blob = nullptr; T *d_stage = nullptr, *d_crop = nullptr;
 
     // ---- the covered sub-grid; the compact tables and, of a host stream, the covered boxes' values and payloads: one blob, one upload.  Of a device
-    // stream the spans go up instead and k_omp_gather fetches them.  (For a fixed (dim 0, dim 1) box coordinate the covered boxes are consecutive: a run.)
+    // stream the spans go up instead and k_omp_gather fetches them.
     int tables() {
-        const szh_omp_geom &g = d.g;
-        const int c[3] = {g.c0, g.c1, g.c2};
-        direct = true;
-        for (int k = 0; k < 3; ++k) {
-            b0[k] = (int)(lo[k] / c[k]); cn[k] = (int)((hi[k] - 1) / c[k]) + 1 - b0[k]; ext[k] = hi[k] - lo[k];
-            if (lo[k] % c[k] || hi[k] % c[k]) direct = false;
-        }
-        nbc = cn[0] * cn[1] * cn[2]; n_out = ext[0] * ext[1] * ext[2];
-        const size_t runs = (size_t)cn[0] * cn[1];
-        std::vector<u64> cbytes((size_t)nbc), coff((size_t)nbc), cu((size_t)nbc + 1, 0), spans;
-        struct piece { size_t src, dst, len; };
-        std::vector<piece> pieces; pieces.reserve(runs * 3);
-        u64 pos = 0;
         const bool dev = d.in.on_device != 0;
-        for (size_t r = 0; r < runs; ++r) {
-            const int bi = b0[0] + (int)(r / cn[1]), bj = b0[1] + (int)(r % cn[1]);
-            const size_t bf = ((size_t)bi * g.ny + bj) * g.nz + b0[2], i0 = r * cn[2];
-            for (int q = 0; q < cn[2]; ++q) {
-                cbytes[i0 + q] = d.bbytes[bf + q]; max_box = std::max(max_box, d.bbytes[bf + q]);
-                cu[i0 + q + 1] = cu[i0 + q] + (d.uoff[bf + q + 1] - d.uoff[bf + q]);
-            }
-            // the run's payloads lie one behind the other in the stream; in the blob they start at the source's place modulo 16 (k_omp_gather)
-            const size_t src = d.off_pay + (size_t)d.boff[bf], len = (size_t)(d.boff[bf + cn[2] - 1] + d.bbytes[bf + cn[2] - 1] - d.boff[bf]);
-            if (dev) pos += (((uintptr_t)(d.in.stream_in + src) & 15u) - (pos & 15u)) & 15u;
-            for (int q = 0; q < cn[2]; ++q) coff[i0 + q] = pos + (d.boff[bf + q] - d.boff[bf]);
-            pieces.push_back({d.off_first + bf * sizeof(T), i0 * sizeof(T), (size_t)cn[2] * sizeof(T)});
-            pieces.push_back({d.off_unpred + (size_t)d.uoff[bf] * sizeof(T), (size_t)cu[i0] * sizeof(T), (size_t)(cu[i0 + cn[2]] - cu[i0]) * sizeof(T)});
-            pieces.push_back({src, (size_t)pos, len});
-            pos += len;
-        }
-        Ec = cu[(size_t)nbc];
-        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        o_bytes = 0; o_off = up16(o_bytes + (size_t)nbc * 8); o_uoff = up16(o_off + (size_t)nbc * 8); o_spans = up16(o_uoff + ((size_t)nbc + 1) * 8);
-        n_spans = dev ? pieces.size() : 0;
-        o_first = up16(o_spans + n_spans * 24); o_unp = up16(o_first + (size_t)nbc * sizeof(T)); o_pay = up16(o_unp + (size_t)Ec * sizeof(T)) + 64;
-        blob_len = o_pay + (size_t)pos + 64;
-        for (size_t p = 0; p < pieces.size(); ++p) pieces[p].dst += p % 3 == 0 ? o_first : p % 3 == 1 ? o_unp : o_pay;
+        c.cover(d.g, lo, hi, d.s, dev ? d.in.stream_in : nullptr);
+        const size_t nbc = (size_t)c.nbc;
+        o_bytes = 0; o_off = up16(o_bytes + nbc * 8); o_uoff = up16(o_off + nbc * 8); o_spans = up16(o_uoff + (nbc + 1) * 8);
+        n_spans = dev ? c.pieces.size() : 0;
+        o_first = up16(o_spans + n_spans * 24); o_unp = up16(o_first + nbc * sizeof(T)); o_pay = up16(o_unp + (size_t)c.Ec * sizeof(T)) + 64;
+        blob_len = o_pay + c.pay_len + 64;
+        c.place_pieces(o_first, o_unp, o_pay);
         TRY(ensure(ctx, ctx->seg_hist, blob_len));
         d_blob = (unsigned char *)ctx->seg_hist.p;
         const size_t up_len = dev ? o_first : blob_len;
         TRY(ensure_pinned3(ctx, up_len));
         unsigned char *hb = (unsigned char *)ctx->pinned3;
-        memcpy(hb + o_bytes, cbytes.data(), (size_t)nbc * 8); memcpy(hb + o_off, coff.data(), (size_t)nbc * 8); memcpy(hb + o_uoff, cu.data(), ((size_t)nbc + 1) * 8);
+        memcpy(hb + o_bytes, c.cbytes.data(), nbc * 8); memcpy(hb + o_off, c.coff.data(), nbc * 8); memcpy(hb + o_uoff, c.cu.data(), (nbc + 1) * 8);
         if (dev) {
             u64 *sp = (u64 *)(hb + o_spans);
-            for (size_t p = 0; p < pieces.size(); ++p) { sp[3 * p] = pieces[p].src; sp[3 * p + 1] = pieces[p].dst; sp[3 * p + 2] = pieces[p].len; }
+            for (size_t p = 0; p < c.pieces.size(); ++p) { sp[3 * p] = c.pieces[p].src; sp[3 * p + 1] = c.pieces[p].dst; sp[3 * p + 2] = c.pieces[p].len; }
             HIPCHK(hipMemcpyAsync(d_blob, hb, up_len, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemsetAsync(d_blob + blob_len - 64, 0, 64, st));
             hipLaunchKernelGGL(k_omp_gather, dim3((unsigned)n_spans), dim3(256), 0, st, d.in.stream_in, d_blob, (const u64 *)(d_blob + o_spans));
             HIPCHK(hipGetLastError());
         } else {
-            for (const piece &pc : pieces) memcpy(hb + pc.dst, d.in.stream_in + pc.src, pc.len);
+            for (const auto &pc : c.pieces) memcpy(hb + pc.dst, d.in.stream_in + pc.src, pc.len);
             memset(hb + blob_len - 64, 0, 64);
             HIPCHK(hipMemcpyAsync(d_blob, hb, up_len, hipMemcpyHostToDevice, st));
         }
-        d.S.n_blocks = (uint64_t)nbc; d.S.n_elements = (uint64_t)n_out; d.S.n_unpred = Ec;
+        d.S.n_blocks = (uint64_t)c.nbc; d.S.n_elements = (uint64_t)c.n_out; d.S.n_unpred = c.Ec;
         return SZHIP_OK;
     }
     // ---- the covered boxes' codes (compact, box after box), then the sweeps over the sub-geometry, then the crop
     int decode() {
         const szh_omp_geom g = d.g;
+        const dec_table &D = d.s.D;
         TRY(clear_small(ctx, &d.sm));
-        TRY(ensure(ctx, ctx->dec_tab, (d.D.dtab.size() * 4 + 63) / 64 * 64 + SZH_LUT_BYTES + 16));
-        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, d.D.dtab.data(), d.D.dtab.size() * 4, hipMemcpyHostToDevice, st));
-        TRY(ensure(ctx, ctx->codes_nat, (size_t)nbc * g.bel * 2 + 64));
+        TRY(ensure(ctx, ctx->dec_tab, up64(D.dtab.size() * 4) + SZH_LUT_BYTES + 16));
+        HIPCHK(hipMemcpyAsync(ctx->dec_tab.p, D.dtab.data(), D.dtab.size() * 4, hipMemcpyHostToDevice, st));
+        TRY(ensure(ctx, ctx->codes_nat, (size_t)c.nbc * g.bel * 2 + 64));
         d.d_codes = (uint16_t *)ctx->codes_nat.p;
         d.d_uoff = (const u64 *)(d_blob + o_uoff); d.d_first = (const T *)(d_blob + o_first); d.d_unpred = (const T *)(d_blob + o_unp);
-        TRY(d.huffman_decode(nbc, d_blob + o_pay, (unsigned)o_pay, (const u64 *)(d_blob + o_off), (const u64 *)(d_blob + o_bytes), max_box));
-        // the sub-geometry: the sub-grid's box counts, the pitches of an array of exactly these boxes
-        szh_omp_geom gs = g;
-        gs.nx = cn[0]; gs.ny = cn[1]; gs.nz = cn[2]; gs.nb = nbc;
-        gs.d1 = (int64_t)cn[2] * g.c2; gs.d0 = (int64_t)cn[1] * g.c1 * gs.d1;
-        gs.vec = g.c2 % 4 == 0 ? 1 : 0;
-        const size_t n_stage = (size_t)nbc * g.bel;
-        if (direct) TRY(device_out(ctx, d.out, d.out_on_device, n_out, &d_crop));        // (n_stage == n_out)
+        TRY(d.huffman_decode(c.nbc, d_blob + o_pay, (unsigned)o_pay, (const u64 *)(d_blob + o_off), (const u64 *)(d_blob + o_bytes), c.max_box));
+        const size_t n_stage = (size_t)c.nbc * g.bel;
+        if (c.direct) TRY(device_out(ctx, d.out, d.out_on_device, c.n_out, &d_crop));        // (n_stage == n_out)
         else {
             TRY(ensure(ctx, ctx->out, n_stage * sizeof(T)));
             d_stage = (T *)ctx->out.p;
             d_crop = (T *)d.out;
-            if (!d.out_on_device) { TRY(ensure(ctx, ctx->codes_blk, n_out * sizeof(T))); d_crop = (T *)ctx->codes_blk.p; }
+            if (!d.out_on_device) { TRY(ensure(ctx, ctx->codes_blk, c.n_out * sizeof(T))); d_crop = (T *)ctx->codes_blk.p; }
         }
-        d.g = gs; d.E = Ec; d.d_out = direct ? d_crop : d_stage;
+        d.g = c.gs; d.E = c.Ec; d.d_out = c.direct ? d_crop : d_stage;
         TRY(d.sweep());
-        if (!direct) {
-            const int cpr = (int)((ext[2] + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
-            const int64_t total = (int64_t)(ext[0] * ext[1]) * cpr;
-            const T *src = d_stage + (int64_t)(lo[0] - (size_t)b0[0] * g.c0) * gs.d0 + (int64_t)(lo[1] - (size_t)b0[1] * g.c1) * gs.d1 + (int64_t)(lo[2] - (size_t)b0[2] * g.c2);
-            hipLaunchKernelGGL((k_omp_crop<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, gs.d0, gs.d1, d_crop, (int)ext[1], (int)ext[2], cpr, total);
+        if (!c.direct) {
+            const int cpr = (int)((c.ext[2] + 16 / sizeof(T) - 1) / (16 / sizeof(T)));
+            const int64_t total = (int64_t)(c.ext[0] * c.ext[1]) * cpr;
+            hipLaunchKernelGGL((k_omp_crop<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T *)d_stage + c.lo_off, c.gs.d0, c.gs.d1, d_crop, (int)c.ext[1], (int)c.ext[2], cpr, total);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(ctx->ev[3], st));
         }
@@ -588,10 +513,10 @@ struct omp_region {
     int finish() {
         unsigned bad = 0;
         HIPCHK(hipMemcpyAsync(&bad, d.sm + SM_ERR, 4, hipMemcpyDeviceToHost, st));
-        TRY(return_out(ctx, d.out, d.out_on_device, d_crop, n_out));
+        TRY(return_out(ctx, d.out, d.out_on_device, d_crop, c.n_out));
         HIPCHK(hipStreamSynchronize(st));
         if (bad) FAIL(SZHIP_ERR_STREAM, "%u boxes of the region whose payload or verbatim-value count does not fit their codes", bad);
-        decompress_times(ctx, d.S, d.host_ms, d.t_begin, n_out * sizeof(T));
+        decompress_times(ctx, d.S, d.host_ms, d.t_begin, c.n_out * sizeof(T));
         return SZHIP_OK;
     }
 };
